@@ -3,7 +3,7 @@
 (single column per GPU, 10 000 bins x 100 layers x 20 Gauss points, premixed corr-k table,
 isotropic scattering, fp64), synthetic tables per SURVEY.md section 8(d).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the radiation_loop body (reference source/computation.py:851-984): interface
@@ -454,6 +454,8 @@ def self_launch(args):
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    if args.dump_outputs is not None:      # (the ranks run in this directory, not the caller's)
+        cmd += ["--dump-outputs", args.dump_outputs]
     raise SystemExit(subprocess.run(cmd, cwd=ROOT).returncode)
 
 
@@ -549,10 +551,56 @@ def kernel_roofline(rt, c, wname, ncol, run, start, profile_steps, step_s):
     return roofline
 
 
+DUMP_LIMIT = 64 << 20     # bytes that --dump-outputs may write, all files together
+DUMP_SEED = 20240         # of the element sample taken from outputs too large to be written whole
+
+
+def dump_plan(sizes, ncol, limit=DUMP_LIMIT):
+    """which elements of each per-column output --dump-outputs writes.  `sizes`: {name: float64 elements per column};
+    every one of the `ncol` columns gives the same elements.  Everything when it all fits `limit`; otherwise the arrays in
+    ascending size, each whole where it fits an equal share of what is left and else a fixed seeded sample of that many
+    elements (sorted indices).  Returns {name: None (all) or the index array}."""
+    left = (limit - 4096 * len(sizes)) // (8 * ncol)      # float64 elements per column (4 KB per file for the .npy header)
+    rng = np.random.default_rng(DUMP_SEED)
+    plan = {}
+    names = sorted(sizes, key=lambda k: (sizes[k], k))
+    for j, name in enumerate(names):
+        share, n = left // (len(names) - j), sizes[name]
+        plan[name] = None if n <= share else np.sort(rng.choice(n, share, replace=False))
+        left -= min(n, share)
+    return plan
+
+
+def dump_outputs(rt, c, ncol, ranks, out_dir):
+    """--dump-outputs: what the timed path computed in its last step, read back as a caller of the batch receives it
+    (hx_rt_get, the reference's layouts) -- temperatures, total and band fluxes, the emission spectrum (upward band flux at
+    the top) -- for every column of the run in global column order, [columns, elements] in float64; rank 0 writes
+    out_dir/<name>.npy.  Outputs too large for DUMP_LIMIT are dump_plan()'s fixed sample of their elements."""
+    X, L, I = c.nbin, c.nlayer, c.nlayer + 1
+    sizes = {"T_lay": L + 1, "T_int": I, "F_up_tot": I, "F_down_tot": I, "F_net": I, "F_net_diff": L,
+             "F_up_band": X * I, "F_down_band": X * I, "spectrum": X}
+    if c.dir_beam:
+        sizes["F_dir_band"] = X * I
+    plan = dump_plan(sizes, ncol * ranks.world)
+    local = {k: [] for k in sizes}
+    for i in range(ncol):
+        for k in sizes:
+            v = rt.get(k, i) if k != "spectrum" else rt.get("F_up_band", i)[X * (I - 1):]   # reference layout [x + X*i]
+            local[k].append(v if plan[k] is None else v[plan[k]])
+    from helios_amd.parallel import gather_spectra
+    out = {k: gather_spectra(np.array(v), ranks.dist, device=ranks.coll_device) for k, v in local.items()}
+    if ranks.rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        for k, v in out.items():
+            np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v, np.float64))
+
+
 def measure(ctx, ranks, wname, ncol, steps, warmup, seed, phase="radiative", profile_steps=20, steady_state=False,
-            device_warmup_ms=25.0):
+            device_warmup_ms=25.0, dump_dir=None):
     """one workload on this rank's GPU: W warm-up steps, K timed steps between barriers (max over ranks), roofline
-    passes, the gather of the emission spectra.  Returns the fields of its line."""
+    passes, the gather of the emission spectra.  Returns the fields of its line.  `dump_dir`: the outputs of the last
+    timed step go there (dump_outputs()), and the device warm-up is a fixed number of iterations instead of a time, so that
+    two runs with the same arguments do the same iterations."""
     import torch
     w = WORKLOADS[wname]
     rank, world = ranks.rank, ranks.world
@@ -606,7 +654,8 @@ def measure(ctx, ranks, wname, ncol, steps, warmup, seed, phase="radiative", pro
         device_warmup = (-warmup) % 10 + 10
         run(warmup, device_warmup)
         ctx.synchronize()
-    while time.perf_counter() - tw < device_warmup_ms * 1e-3 and device_warmup < 200:
+    while (device_warmup_ms > 0 and (dump_dir is not None or time.perf_counter() - tw < device_warmup_ms * 1e-3)
+           and device_warmup < 200):
         run(warmup + device_warmup, 10)
         ctx.synchronize()
         device_warmup += 10
@@ -626,6 +675,8 @@ def measure(ctx, ranks, wname, ncol, steps, warmup, seed, phase="radiative", pro
     dt = max(all_dt)
     rank_ms = [t / steps * 1e3 for t in all_dt]
     done = [int(rt.get("done", i)[0]) for i in range(ncol)]
+    if dump_dir is not None:      # before the roofline passes below iterate further
+        dump_outputs(rt, c, ncol, ranks, dump_dir)
 
     roofline = None
     if profile_steps > 0:
@@ -822,9 +873,15 @@ def main():
     ap.add_argument("--phase", default="radiative", choices=["radiative", "convection"],
                     help="which loop a step is taken from: radiation_loop (default, the headline number) or "
                          "convection_loop (convective adjustment + sweeps + temperature step, all on the device)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the headline workload's last timed step computed to DIR/<name>.npy (float64, at most "
+                         "64 MB in all; a fixed sample of larger outputs).  The device warm-up is then a fixed number of "
+                         "iterations, so that runs with the same arguments can be compared output for output")
     args = ap.parse_args()
     knobs = env_knobs(args.allow_debug_knobs)
 
+    if args.dump_outputs is not None:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args)
     rank = int(os.environ.get("RANK", "0"))
@@ -837,6 +894,8 @@ def main():
     heavy = bool(w.get("nspecies")) and w["nbin"] >= 5000
     steps = args.steps if args.steps is not None else (20 if heavy else 200)
     warmup = args.warmup if args.warmup is not None else (10 if heavy else 20)
+    if steps < 1 or warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     ncol = args.columns_per_gpu or w.get("columns_per_gpu", 1)
     if args.secondary in ("default", "all"):
         # (config 4 with the SAME shape at every N: one GPU's share of the 512-column sweep, 64 columns in one batch)
@@ -886,7 +945,7 @@ def main():
     seed = 20240 + 2
     ctx = Context(device_index)
     head = measure(ctx, ranks, wname, ncol, steps, warmup, seed, phase=args.phase, profile_steps=args.profile_steps,
-                   steady_state=True, device_warmup_ms=args.device_warmup_ms)
+                   steady_state=True, device_warmup_ms=args.device_warmup_ms, dump_dir=args.dump_outputs)
     line = {"metric": "rad-conv iterations/sec x (lambda-bins x layers)", "value": head.pop("value"),
             "unit": head.pop("unit"), "n_gpus": world, "steps": head.pop("steps"), "warmup": head.pop("warmup"),
             "device_warmup_iterations": head.pop("device_warmup_iterations"), "ms_per_step": head.pop("ms_per_step"),

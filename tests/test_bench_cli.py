@@ -94,3 +94,31 @@ def test_bench_knows_when_it_runs_under_a_profiler():
     assert not bench.under_a_profiler({"PATH": "/usr/bin", "LD_PRELOAD": "/usr/lib/libjemalloc.so"})
     assert bench.under_a_profiler({"LD_PRELOAD": "/opt/rocm/lib/rocprofiler-sdk/librocprofiler-sdk-tool.so:/opt/rocm/lib/librocprofiler-sdk.so"})
     assert bench.under_a_profiler({"ROCPROF_OUTPUT_PATH": "/tmp/x"}) and bench.under_a_profiler({"ROCPROFILER_LIBRARY_CTOR": "1"})
+
+
+def test_dump_plan_fits_the_limit_and_is_fixed():
+    """--dump-outputs: small outputs whole, large ones as the same seeded sample of each column's elements, the whole set
+    under bench.DUMP_LIMIT at one column and at 512"""
+    import numpy as np
+    import bench
+    sizes = {"T_lay": 101, "F_net": 101, "F_net_diff": 100, "spectrum": 10000, "F_up_band": 1010000, "F_down_band": 1010000}
+    assert all(v is None for v in bench.dump_plan(sizes, 1).values())
+    for ncol in (64, 512):
+        plan = bench.dump_plan(sizes, ncol)
+        again = bench.dump_plan(sizes, ncol)
+        total = 0
+        for k, n in sizes.items():
+            idx = plan[k]
+            if idx is None:
+                total += n
+                continue
+            assert np.array_equal(idx, again[k]) and len(np.unique(idx)) == len(idx) and idx.min() >= 0 and idx.max() < n
+            total += len(idx)
+        assert plan["T_lay"] is None and plan["F_up_band"] is not None
+        assert 8 * ncol * total + 4096 * len(sizes) <= bench.DUMP_LIMIT
+
+
+def test_bench_refuses_zero_steps():
+    p = subprocess.run([sys.executable, "bench.py", "--steps", "0", "--live-counters", "off"], cwd=ROOT, capture_output=True,
+                       text=True, timeout=120)
+    assert p.returncode != 0 and "--steps" in p.stderr

@@ -204,47 +204,49 @@ def test_bench_secondary_workload_under_a_launcher():
     assert bench.WORKLOADS["c4"]["columns_per_gpu"] * 8 == 512
 
 
-def test_bench_eight_ranks_rehearsal_on_one_gpu():
-    """the 8-GPU launch of the driver, rehearsed on this box's one GPU through the gloo hook: eight ranks, each with its own
-    context, column and start profile; per-rank arrays of length 8, the process group echoed into the line, the sharded
-    sweep as secondary workload -- and the spectra, gathered from device tensors, in global column order: the same eight
-    columns as ONE batch in one process give the same per-column checksums in the same order"""
+def test_bench_four_ranks_rehearsal_on_one_gpu():
+    """the multi-GPU launch of the driver, rehearsed on one GPU through the gloo hook: four ranks (with this process, five
+    processes hold the GPU -- the most a shared machine allows is six), each with its own context, column and start
+    profile; per-rank arrays of length 4, the process group echoed into the line, the sharded sweep as secondary workload
+    -- and the spectra, gathered from device tensors, in global column order: the same four columns as ONE batch in one
+    process give the same per-column checksums in the same order"""
     env = dict(os.environ, HELIOS_BENCH_BACKEND="gloo")
     common = ["--steps", "10", "--warmup", "10", "--workload", "c2small", "--profile-steps", "0", "--device-warmup-ms", "0",
               "--no-cpu-baseline"]
-    p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
-                        "--master-addr", "127.0.0.1", "--master-port", "29541", "bench.py", "--gpus", "8", "--secondary",
+    p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
+                        "--master-addr", "127.0.0.1", "--master-port", "29541", "bench.py", "--gpus", "4", "--secondary",
                         "c4small"] + common, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
-    # the N = 8 line itself: within the size limit, with what the first real 8-GPU run will be read for
+    # the N = 4 line itself: within the size limit, with what a real multi-GPU run will be read for
     short = _last_json(p.stdout, detail=False)
-    assert short["n_gpus"] == 8 and len(short["per_rank_ms_per_step"]) == 8 and 0 <= short["rank_imbalance"] < 1
+    assert short["n_gpus"] == 4 and len(short["per_rank_ms_per_step"]) == 4 and 0 <= short["rank_imbalance"] < 1
     assert short["spectra_gather_ms"] > 0 and short["secondary"]["c4small"]["value"] > 0
     spg = short["process_group"]
-    assert spg["world_size"] == 8 and len(spg["numa_node_per_rank"]) == 8 and len(spg["cpus_per_rank"]) == 8
+    assert spg["world_size"] == 4 and len(spg["numa_node_per_rank"]) == 4 and len(spg["cpus_per_rank"]) == 4
     assert spg["init_s"] > 0 and spg["roll_call_s"] >= 0 and spg["first_collective_s"] >= 0
     line = _last_json(p.stdout)
-    assert line["n_gpus"] == 8 and line["config"]["columns_total"] == 8 and line["config"]["columns_per_gpu"] == 1
-    assert len(line["per_rank_ms_per_step"]) == 8 and all(v > 0 for v in line["per_rank_ms_per_step"])
+    assert line["n_gpus"] == 4 and line["config"]["columns_total"] == 4 and line["config"]["columns_per_gpu"] == 1
+    assert len(line["per_rank_ms_per_step"]) == 4 and all(v > 0 for v in line["per_rank_ms_per_step"])
     pg = line["process_group"]
-    assert pg["backend"] == "gloo" and pg["world_size"] == 8 and pg["ranks_seen_by_all_gather"] == 8 and pg["rccl_world"] is None
+    assert pg["backend"] == "gloo" and pg["world_size"] == 4 and pg["ranks_seen_by_all_gather"] == 4 and pg["rccl_world"] is None
     cs = line["spectrum_checksum_per_column"]
-    assert len(cs) == 8 and len(set(cs)) == 8
+    assert len(cs) == 4 and len(set(cs)) == 4
     assert abs(sum(cs) - line["spectrum_checksum"]) <= 1e-9 * abs(line["spectrum_checksum"])
     sec = line["secondary"]["c4small"]
-    assert sec["config"]["columns_total"] == 48 and len(sec["per_rank_ms_per_step"]) == 8 and sec["spectra_gather_ms"] is not None
-    assert len(sec["spectrum_checksum_per_column"]) == 48
-    one = subprocess.run([sys.executable, "bench.py", "--columns-per-gpu", "8", "--secondary", "none"] + common, cwd=ROOT,
+    assert sec["config"]["columns_total"] == 24 and len(sec["per_rank_ms_per_step"]) == 4 and sec["spectra_gather_ms"] is not None
+    assert len(sec["spectrum_checksum_per_column"]) == 24
+    one = subprocess.run([sys.executable, "bench.py", "--columns-per-gpu", "4", "--secondary", "none"] + common, cwd=ROOT,
                          capture_output=True, text=True, timeout=900)
     assert one.returncode == 0, one.stderr[-3000:]
     one = _last_json(one.stdout)
-    assert one["config"]["columns_total"] == 8 and one["process_group"] is None
+    assert one["config"]["columns_total"] == 4 and one["process_group"] is None
     for a, b in zip(cs, one["spectrum_checksum_per_column"]):        # column k of the batch = the column of rank k
         assert abs(a - b) <= 1e-9 * abs(b), (cs, one["spectrum_checksum_per_column"])
 
 
-def test_sweep_work_list_is_exhausted_by_eight_ranks(tmp_path):
-    """HELIOS_SWEEP_PARTITION=dynamic:1 with eight ranks (gloo hook: all on GPU 0) and twelve columns: the ranks claim
+def test_sweep_work_list_is_exhausted_by_four_ranks(tmp_path):
+    """HELIOS_SWEEP_PARTITION=dynamic:1 with four ranks (gloo hook: all on GPU 0; with this process five hold the GPU, the
+    most a shared machine allows is six) and twelve columns: the ranks claim
     columns one at a time until the list is exhausted -- every column is run exactly once, by whichever rank got there
     first -- and the spectra arrive in sweep order and equal the one-process sweep"""
     import numpy as np
@@ -257,15 +259,51 @@ def test_sweep_work_list_is_exhausted_by_eight_ranks(tmp_path):
     cols, spectra = sweep.main(["-sweep", spec] + base + ["-output_directory", str(tmp_path) + "/one/"])
     assert len(cols) == 12
     env = dict(os.environ, HELIOS_BENCH_BACKEND="gloo", HELIOS_SWEEP_PARTITION="dynamic:1")
-    p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
+    p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
                         "--master-addr", "127.0.0.1", "--master-port", "29543", "sweep.py", "-sweep", spec] + base +
-                       ["-output_directory", str(tmp_path) + "/eight/"], cwd=ROOT, env=env, capture_output=True, text=True,
+                       ["-output_directory", str(tmp_path) + "/four/"], cwd=ROOT, env=env, capture_output=True, text=True,
                        timeout=1500)
     assert p.returncode == 0, p.stderr[-6000:]
-    assert "Load over 8 ranks" in p.stdout
-    z = np.load(os.path.join(str(tmp_path), "eight", "wl8_sweep_spectra.npz"))
+    assert "Load over 4 ranks" in p.stdout
+    z = np.load(os.path.join(str(tmp_path), "four", "wl8_sweep_spectra.npz"))
     np.testing.assert_allclose(z["F_up_TOA"], spectra, rtol=1e-12)
     for k in range(12):
         a = open(os.path.join(str(tmp_path), "one", "wl8_%d" % k, "wl8_%d_tp.dat" % k)).read()
-        b = open(os.path.join(str(tmp_path), "eight", "wl8_%d" % k, "wl8_%d_tp.dat" % k)).read()
+        b = open(os.path.join(str(tmp_path), "four", "wl8_%d" % k, "wl8_%d_tp.dat" % k)).read()
         assert a == b, k
+
+
+def test_dump_outputs_repeat_and_gather_in_column_order(tmp_path):
+    """--dump-outputs: float64 arrays of the last timed step, one row per column, under bench.DUMP_LIMIT; the same
+    arguments give the same outputs, and two ranks (gloo hook, both on GPU 0) dump what one process computes for the
+    same two columns as one batch"""
+    import numpy as np
+    import bench
+    common = ["--workload", "c2small", "--steps", "20", "--warmup", "5", "--secondary", "none", "--no-cpu-baseline",
+              "--live-counters", "off", "--profile-steps", "0"]
+    dirs = {}
+    for tag in ("a", "b"):
+        dirs[tag] = tmp_path / tag
+        p = subprocess.run([sys.executable, "bench.py", "--columns-per-gpu", "2", "--dump-outputs", str(dirs[tag])] + common,
+                           cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert _last_json(p.stdout, detail=False)["steps"] == 20
+    env = dict(os.environ, HELIOS_BENCH_BACKEND="gloo")
+    dirs["ranks"] = tmp_path / "ranks"
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--dump-outputs", str(dirs["ranks"])] + common, cwd=ROOT,
+                       env=env, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-2000:]
+    names = sorted(f for f in os.listdir(str(dirs["a"])))
+    assert "spectrum.npy" in names and "T_lay.npy" in names and "F_up_band.npy" in names
+    assert sum(os.path.getsize(str(dirs["a"] / f)) for f in names) <= bench.DUMP_LIMIT
+    w = bench.WORKLOADS["c2small"]
+    for f in names:
+        a, b, r = (np.load(str(dirs[t] / f)) for t in ("a", "b", "ranks"))
+        assert a.dtype == np.float64 and a.shape[0] == 2 and np.all(np.isfinite(a)), f
+        np.testing.assert_array_equal(a, b, err_msg=f)
+        np.testing.assert_allclose(r, a, rtol=1e-9, atol=0, err_msg=f)
+    a = {f: np.load(str(dirs["a"] / f)) for f in ("T_lay.npy", "F_up_band.npy", "spectrum.npy")}
+    X, I = w["nbin"], w["nlayer"] + 1
+    assert a["T_lay.npy"].shape == (2, I) and a["F_up_band.npy"].shape == (2, X * I)
+    np.testing.assert_array_equal(a["spectrum.npy"], a["F_up_band.npy"][:, X * (I - 1):])
+    assert not np.array_equal(a["T_lay.npy"][0], a["T_lay.npy"][1])      # two different columns
