@@ -424,6 +424,24 @@ class Compute(object):
                   "kernels (still on the GPU, same results, about 5-10 times slower per iteration).")
         return self.use_fused and why is None
 
+    def _tell_stagewise_is_double(self, quant):
+        # `precision = single` is a property of the device-resident loop's coefficient planes: the per-stage kernels have
+        # none and compute in double precision -- said once per run
+        if getattr(quant, "prec", "double") == "single" and not getattr(self, "_told_fp64_planes", False):
+            self._told_fp64_planes = True
+            print("\nhelios_amd: precision = single -- the per-stage kernels have no fp32 coefficient planes; this run "
+                  "computes in double precision.")
+
+    @staticmethod
+    def _why_fp64_planes(q):
+        """why a batch asked for fp32 coefficient planes got fp64 ones (hx_rt_create: the matrix method keeps fp64 planes;
+        fp32 variants exist for the sweeps' tilings without scratch, columns of up to 416 layers, 512 isothermal)"""
+        if q.flux_calc_method == "matrix":
+            return "the matrix method's direct solve keeps fp64 coefficient planes"
+        if _i(q.nlayer) > (512 if q.iso == 1 else 416):
+            return "%d layers have no fp32 coefficient planes in the device-resident loop" % _i(q.nlayer)
+        return "this batch's tiling (set by the HELIOS_RT_K / HELIOS_RT_GENERIC_SCANS tuning knobs) has no fp32 variant"
+
     @staticmethod
     def _rt_flags(q):
         return dict(scat=_i(q.scat), dir_beam=_i(q.dir_beam), clouds=_i(q.clouds), scat_corr=_i(q.scat_corr),
@@ -433,7 +451,8 @@ class Compute(object):
                     singlewalk=_i(q.singlewalk), matrix=1 if q.flux_calc_method == "matrix" else 0, epsi=_f(q.epsi),
                     epsi2=_f(q.epsi2), g_0=_f(q.g_0), i2s_transition=_f(q.i2s_transition),
                     w_0_limit=_f(q.w_0_limit), w_0_scat_limit=_f(q.w_0_scat_limit),
-                    delta_tau_limit=_f(q.delta_tau_limit), debug=_i(q.debug or 0))
+                    delta_tau_limit=_f(q.delta_tau_limit), debug=_i(q.debug or 0),
+                    coef_fp32=1 if getattr(q, "prec", "double") == "single" else 0)
 
     @staticmethod
     def _rt_column(q):
@@ -468,6 +487,10 @@ class Compute(object):
         rt = RTBatch(self._ctx_of(q), _i(q.nbin), _i(q.ny), _i(q.nlayer), len(quants), _i(q.ntemp), _i(q.npress),
                      _i(q.plancktable_dim), _i(q.plancktable_step), self._rt_flags(q),
                      [self._rt_column(c) for c in quants], nspecies=nspecies)
+        if rt.flags.coef_fp32 and rt.coef_plane_bytes() != 4 and not getattr(self, "_told_fp64_planes", False):
+            # the library chose fp64 planes: say why, once
+            self._told_fp64_planes = True
+            print("\nhelios_amd: precision = single -- " + self._why_fp64_planes(q) + "; this run computes in double precision.")
         try:
             self._fill_rt_batch(rt, quants, on_the_fly)
         except Exception:
@@ -668,6 +691,7 @@ class Compute(object):
 
     def _radiation_loop_stagewise(self, quant, write=None, read=None, rt_plot=None):
         """the reference's loop, stage by stage (isothermal layers, post-processing run type, ...)"""
+        self._tell_stagewise_is_double(quant)
         L = _i(quant.nlayer)
         condition1 = condition2 = condition3 = True
         self.ctx.timer_start()
@@ -813,6 +837,7 @@ class Compute(object):
                           "combination either); set 'isothermal layers = no' or 'convective adjustment = no'")
         if self._fused_supported(quant) and quant.rt is not None and quant.physical_tstep == 0:
             return self._convection_loop_fused(quant, write, read)
+        self._tell_stagewise_is_double(quant)
         if quant.rt is not None:      # the per-stage loop continues from the fused state
             self.sync_store_from_rt(quant, flux_state=True)
         L = _i(quant.nlayer)

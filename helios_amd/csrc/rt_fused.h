@@ -22,7 +22,7 @@ struct TileGeom {
     int nplane;       // coefficient planes per tile: alpha, beta, u' [, v'] [, dd, du]
     int has_vp, pl_vp, pl_dd;
     size_t tile_rows; // ROWS
-    size_t coef_elems_per_col, flux_elems_per_col;  // doubles
+    size_t coef_elems_per_col, flux_elems_per_col;  // elements (coefficient planes: double, or float with coef_fp32)
 };
 
 struct Species {
@@ -116,6 +116,8 @@ struct hx_rt {
     double* F_dir_band_n = nullptr;                                                   // [x][i], X*I
     double* Bn = nullptr;       // node Planck [x][H+3]
     double* coef = nullptr;     // coefficient tiles
+    float* coef32 = nullptr;    // the same tiles in fp32 (hx_rt_flags.coef_fp32 and an fp32 tiling): then `coef` stays null
+    int coef_bytes = 8;         // bytes per coefficient-plane element in use (hx_rt_get "coef_plane_bytes")
     double* Utile = nullptr;    // up-flux state tiles
     double* Dtile = nullptr;    // down-flux tiles (only with keep_down)
     double *U0 = nullptr, *boaK = nullptr, *Fdir0 = nullptr;  // per spectral point, Y*X

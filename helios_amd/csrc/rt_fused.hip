@@ -268,6 +268,14 @@ void launch_flux(hx_rt* rt, const KArgs& a) {
         const long long keep = (long long)(rt->state_cache_mb * 1048576.0 / per_wg);
         f.cache_state_from = (int)std::max(0LL, total - keep);
     }
+    if (rt->coef32) {   // `precision = single`: the same kernel on fp32 planes (rt_fused_f32.hip)
+        if (rt->matrix_scan) {
+            f.reverse = 0;
+            f.cache_state_from = INT_MAX;
+        }
+        launch_flux_f32(rt, f, dim3(g.nblk_x, rt->C), shmem);
+        return;
+    }
     const bool generic = rt->generic_scans;
     if constexpr (ROWS > 16) {   // (only on 64 lanes: choose_geometry)
         if (rt->matrix_scan) {
@@ -323,6 +331,10 @@ void launch_coef_tpb(hx_rt* rt, KArgs a) {
     const size_t cloud_image = 3 * (size_t)rt->H * NBX * sizeof(double);
     a.cloud_lds = a.clouds == 1 && rt->cloud_lds && shmem + cloud_image <= 80 * 1024;  // keep two workgroups per CU
     if (a.cloud_lds) shmem += cloud_image;
+    if (rt->coef32) {   // `precision = single` (rt_fused_f32.hip)
+        launch_coef_f32(rt, a, TPB, dim3((ntiles + TPB - 1) / TPB, rt->C), shmem);
+        return;
+    }
     if (shmem > 64 * 1024 && !rt->coef_shmem_raised) {
         (void)hipFuncSetAttribute((const void*)k_rt_coef<ROWS, TPB>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)shmem);
@@ -408,6 +420,7 @@ int set_flux_shmem_limits(hx_rt* rt) {
     if (shmem <= 64 * 1024) return 0;
     DISPATCH_ROWS(raise_flux_shmem, rt, (int)shmem);
     HX_HIP(rt->ctx, rt->shmem_rc);
+    if (rt->coef_bytes == 4) HX_HIP(rt->ctx, raise_flux_shmem_f32(rt, (int)shmem));
     return 0;
 }
 
@@ -471,6 +484,11 @@ static int rt_create_into(hx_rt* rt, hx_context* ctx, const hx_rt_dims* dims, co
     // a small grid keeps at least 32 chunks (of >= 8 bins) so that the first level still spreads over the chip
     rt->nchunk = std::max(1, std::min(512, std::max((rt->X + 47) / 48, std::min(32, (rt->X + 7) / 8))));
     if (const char* e = getenv("HELIOS_RT_GENERIC_SCANS")) rt->generic_scans = atoi(e) != 0;  // read per batch: tests
+    // `precision = single`: fp32 coefficient planes for the sweeps where the tiling has an fp32 instantiation
+    // (rt_fused_f32.hip).  The matrix method keeps fp64 planes: its direct solve of a nearly conservative column (w0 at
+    // w_0_limit, thin layers) took the planes' fp32 rounding to 2e-3 on spectral up-fluxes, the sweeps stayed within 1e-5
+    // (DESIGN.md); the per-stage matrix solver has no planes at all.  The caller reads the width through "coef_plane_bytes"
+    rt->coef_bytes = flags->coef_fp32 && !rt->matrix && coef_fp32_tiling(rt->g.ROWS, rt->g.k, rt->generic_scans) ? 4 : 8;
     if (const char* e = getenv("HELIOS_RT_CLOUD_LDS")) rt->cloud_lds = atoi(e) != 0;  // 0: k_rt_coef's fallback path (tests)
     // tiles per workgroup of k_rt_coef: 16 spectral points staged side by side (128-byte runs of the k-table) -- 4 tiles
     // at k = 16, 8 at k = 32 (config 5, same box: 2 tiles 6.4 ms, 4 tiles 4.5 ms, 8 tiles 3.4 ms per refresh)
@@ -551,7 +569,8 @@ static int rt_create_into(hx_rt* rt, hx_context* ctx, const hx_rt_dims* dims, co
         RT_ALLOC(m.pb_lay, C * X * (L + 2)); RT_ALLOC(m.pb_int, C * X * I);
         RT_ALLOC(m.c_prime, nc * (halves * 2 * I)); RT_ALLOC(m.d_prime, nc * (halves * 2 * I));
     } else {
-        RT_ALLOC(rt->coef, C * rt->g.coef_elems_per_col);
+        if (rt->coef_bytes == 4) RT_ALLOC(rt->coef32, C * rt->g.coef_elems_per_col);
+        else RT_ALLOC(rt->coef, C * rt->g.coef_elems_per_col);
         RT_ALLOC(rt->Utile, C * rt->g.flux_elems_per_col);
     }
     RT_ALLOC(rt->U0, C * nc); RT_ALLOC(rt->boaK, C * nc); RT_ALLOC(rt->Fdir0, C * nc);
@@ -1654,6 +1673,12 @@ static int materialize_opac(hx_rt* rt) {
 
 int hx_rt_get(hx_rt* rt, int col, const char* name, void* out, size_t out_bytes) {
     if (!rt) return HX_E_ARG;  // e.g. a call after hx_rt_destroy
+    if (strcmp(name, "coef_plane_bytes") == 0) {   // host-side, any column (-1): int32, 4 (fp32 planes) or 8
+        HX_REQUIRE(rt->ctx, out_bytes == sizeof(int32_t), HX_E_ARG, "coef_plane_bytes is one int32");
+        const int32_t v = rt->coef_bytes;
+        memcpy(out, &v, sizeof(v));
+        return 0;
+    }
     HX_REQUIRE(rt->ctx, col >= 0 && col < rt->C, HX_E_ARG, "column index out of range");
     if (strncmp(name, "opac_wg_", 8) == 0) {
         int rc = materialize_opac(rt);
@@ -1941,16 +1966,17 @@ int hx_rt_traffic_model(hx_rt* rt, double* step_alg, double* step_act, double* r
     const double BT = 8.0 * Y * X * (2 * L + 1) * (S > 0 ? 4.0 * S + 1.0 : 5.0);
     // what this implementation actually moves (per column)
     const TileGeom& g = rt->g;
-    const double tiles = (double)g.nblk * g.NW * 64.0 * g.ROWS * 8.0;  // one plane
+    const double tiles = (double)g.nblk * g.NW * 64.0 * g.ROWS * 8.0;  // one fp64 plane (the state)
+    const double planes = tiles / 8.0 * rt->coef_bytes * g.nplane;     // the coefficient planes, fp64 or fp32
     // (the matrix method's direct solve reads the same planes and keeps no flux state)
     const double state_planes = rt->matrix_scan ? (rt->matrix_keep_state ? 1.0 : 0.0) : 2.0;
-    const double flux_k = tiles * (g.nplane + state_planes + (rt->keep_down ? 1.0 : 0.0))   // coef + U read/write
+    const double flux_k = planes + tiles * (state_planes + (rt->keep_down ? 1.0 : 0.0))     // coef + U read/write
                           + 8.0 * X * (rt->H + 3) * 2.0                            // node Planck write+read
                           + 8.0 * X * 2.0 * (L + 1) * 2.0                          // band arrays w + r
                           + 8.0 * X * Y * 2.0;                                     // U0
     const double premixed = 8.0 * Y * X * (2 * L + 1) * 5.0;
     const double species = 8.0 * Y * X * (2 * L + 1) * (4.0 * S + 1.0);  // table corners of every absorber + one write
-    const double coef_k = tiles * g.nplane + 8.0 * Y * X * (2 * L + 1);
+    const double coef_k = planes + 8.0 * Y * X * (2 * L + 1);
     if (step_alg) *step_alg = BE * rt->C;
     if (step_act) *step_act = flux_k * rt->C;
     if (refresh_alg) *refresh_alg = BT * rt->C;

@@ -12,11 +12,14 @@
 // each lane keeps its ROWS half-layers in registers across all 3*scat+1 sweeps.
 // Since u + v = M + N - P in both branches, v' = K (1 - alpha - beta) - u'; without the improved
 // two-stream correction E == 1 and K = 2 pi eps is a constant, so the v' plane is not stored then.
+// rt_fused_f32.hip includes this header with HX_PLANE_KERNELS_ONLY defined, for the templates of k_rt_coef and k_rt_flux:
+// the other kernels are defined once, in rt_fused.hip.
 #pragma once
 #include "rt_fused.h"
 #include "conv_adjust.h"
 #include "temp_step.h"
 #include "two_stream.h"
+#include "plane_code.h"
 
 namespace hx {
 
@@ -41,7 +44,7 @@ struct KArgs {
     double *T_int, *Bn, *coef, *Utile, *Dtile, *U0, *boaK, *Fdir0;
     double *dtau_u, *dtau_l;
     double *F_down_band_n, *F_up_band_n, *tot_part, *F_up_tot, *F_down_tot, *F_net;
-    size_t coef_col, flux_col;  // per-column strides (doubles) of coef / Utile / Dtile
+    size_t coef_col, flux_col;  // per-column strides (elements) of coef / Utile / Dtile
     const int* done;
     // premixed table look-up fused into the coefficient kernel
     const double *ktable, *crosstable, *ktemp, *kpress;
@@ -76,7 +79,7 @@ __device__ __forceinline__ double interface_T(const double* T, int i, int L) {
 }
 
 // Tile planes hold ROWS rows of 64 lanes, [row][lane]: every wavefront load/store of a row is one
-// contiguous 512-byte segment.  (A paired-row layout with 16-byte accesses per lane was measured: the
+// contiguous 512-byte segment (256 bytes with fp32 planes, `precision = single`).  (A paired-row layout with 16-byte accesses per lane was measured: the
 // 16-byte register alignment pushed k_rt_flux<13> from 218 to 256+ VGPRs with scratch spills and made
 // it 40 % slower, so rows stay scalar.)  Offset of (row r, lane) inside a plane:
 __host__ __device__ __forceinline__ size_t plane_off(int r, int lane, int ROWS) {
@@ -84,6 +87,7 @@ __host__ __device__ __forceinline__ size_t plane_off(int r, int lane, int ROWS) 
     return (size_t)r * 64 + lane;
 }
 
+#ifndef HX_PLANE_KERNELS_ONLY
 // ---- per iteration: interface temperatures + Planck function at every node ------------------
 // Bn[col][x][n], n in [0, H+3): nodes 0..H, then H+1 = stellar row, H+2 = surface (T_lay[L]).
 __global__ void __launch_bounds__(256) k_rt_nodes(KArgs a) {
@@ -128,6 +132,7 @@ __global__ void __launch_bounds__(256) k_rt_nodes(KArgs a) {
     }
 }
 
+#endif  // HX_PLANE_KERNELS_ONLY
 // ---- neighbour-lane moves for the scans --------------------------------------------------------
 // Distances 1, 2, 4, 8 stay inside a 16-lane DPP row: `row_shr:n` / `row_shl:n` move a register across
 // lanes in the VALU (a few cycles) instead of going through the LDS crossbar (ds_bpermute, ~100 cycles
@@ -361,6 +366,7 @@ __device__ __forceinline__ double group_first_lane(double v, int lane) {  // lan
 // tiny_abs with the threshold as data: 1e-100 where the reference applies it, 0.0 (never true) where it does not
 __device__ __forceinline__ double tiny_abs_below(double F, double thr) { return fabs(F) < thr ? fabs(F) : F; }
 
+#ifndef HX_PLANE_KERNELS_ONLY
 // ---- per refresh: band quantities of the half-layers, bin-major ---------------------------------
 // grid (ceil(X/32), ceil(H/32), C), 256 threads.  The band arrays are level-major ([i][x], the reference's layout); a
 // workgroup of k_rt_coef needs ALL half-layers of one or two bins, which there is one 64-byte sector per double.  This
@@ -400,285 +406,37 @@ __global__ void __launch_bounds__(256) k_rt_half_bands(KArgs a) {
     }
 }
 
+#endif  // HX_PLANE_KERNELS_ONLY
+// the coding of the fp32 coefficient planes: plane_code.h
+
 // ---- per refresh: compact coefficient tiles ---------------------------------------------------
 // grid (ceil(ntiles / COEF_TPB), C), COEF_TPB wavefronts per workgroup, one tile each.  The opacities
 // live in the reference's layout [y + ny*x + ny*nbin*level] (level slowest), so the spectral points of
 // one tile are only 64/k doubles apart per level: the workgroup first stages the opacities of ALL its
 // tiles' spectral points (consecutive in memory when a tile row holds one bin) for every level into
 // LDS with >= 128-byte contiguous reads, then every lane builds the coefficients of its half-layers.
-template <int ROWS, int COEF_TPB>
-__global__ void __launch_bounds__(64 * COEF_TPB) k_rt_coef(KArgs a) {
-    extern __shared__ __align__(16) double smem[];
-    const int col = blockIdx.y;
-    if (a.done[col]) return;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int ntiles = a.nblk_x * a.nparts * a.NW;
-    const int TS = COEF_TPB * a.S;                  // spectral points staged per workgroup
-    const int TSP = TS;                             // row pitch of the staged opacities (padding it was measured: slower)
-    const int NBX = a.coef_nbx;                     // bins this workgroup's tiles can touch (upper bound)
-    double* sh_lay = smem;                          // [L][TSP]  opacity at layer centres
-    double* sh_int = sh_lay + (size_t)a.L * TSP;    // [I][TSP]  opacity at interfaces
-    double* sh_ray = sh_int + (size_t)a.I * TSP;    // [H][NBX]  Rayleigh cross-section of the half-layers
-    double* sh_mu = sh_ray + (size_t)a.H * NBX;     // [H]       mean molecular mass of the half-layers
-    double* sh_dc = sh_mu + a.H;                    // [H]       column mass of the half-layers
-    // clouds: asymmetry parameter, absorption and scattering cross-sections of the half-layers, [H][NBX] each.  They do
-    // not depend on the Gauss point; read per lane from the band arrays (level-strided: one 64-byte sector per double)
-    // they were 18 scattered loads per half-layer -- config 5's k_rt_coef 7.4 ms per refresh against 2.9 ms expected
-    // from config 2's rate
-    const size_t ncl = a.cloud_lds ? (size_t)a.H * NBX : 0;
-    double* sh_g0 = sh_dc + a.H;
-    double* sh_cab = sh_g0 + ncl;
-    double* sh_csc = sh_cab + ncl;
-    int* c_of_q = (int*)(sh_csc + ncl);             // [TS] global spectral-point index or -1
-    int* x_of_q = c_of_q + TS;
-    const size_t nc = (size_t)a.Y * a.X;
-    const size_t wgI = nc * a.I;
-    const int x_base = (blockIdx.x * COEF_TPB) / (a.NW * a.nparts) * a.nxb;  // first bin of the first tile
-    // spectral points of this workgroup's tiles
-    for (int q = threadIdx.x; q < TS; q += blockDim.x) {
-        const int tl = blockIdx.x * COEF_TPB + q / a.S, s_in_wave = q % a.S;
-        int c = -1, xq = x_base;
-        if (tl < ntiles) {
-            const int wv = tl % a.NW, part = (tl / a.NW) % a.nparts, bx = tl / (a.NW * a.nparts);
-            const int s_local = wv * a.S + s_in_wave;
-            const int xl = s_local / a.ypb, yl = s_local - xl * a.ypb;
-            const int x = bx * a.nxb + xl, y = part * a.ypb + yl;
-            if (s_local < a.G && x < a.X) { c = y + a.Y * x; xq = x; }
-        }
-        c_of_q[q] = c;
-        x_of_q[q] = xq;
-    }
-    // per-level quantities of the half-layers.  Lower half h = 2i averages (interface i, centre i),
-    // upper half h = 2i+1 (centre i, interface i+1); the sums are commutative, so one form serves both.
-    {
-        const double* mml = a.mmm_lay + (size_t)col * a.I;
-        const double* mmi = a.mmm_int + (size_t)col * a.I;
-        const double* dcu = a.dcol_u + (size_t)col * a.L;
-        const double* dcl = a.dcol_l + (size_t)col * a.L;
-        const double* pint = a.p_int + (size_t)col * a.I;
-        const double grav = a.colpar[col].g;
-        for (int h = threadIdx.x; h < a.H; h += blockDim.x) {
-            if (a.iso) {  // whole layers (calc_trans_iso, kernels.cu:1015-1104): delta_colmass of host_functions.py:733
-                sh_mu[h] = mml[h];
-                sh_dc[h] = (pint[h] - pint[h + 1]) / grav;
-            } else {
-                const int i = h >> 1, ii = i + (h & 1);
-                sh_mu[h] = (mmi[ii] + mml[i]) / 2.0;
-                sh_dc[h] = (h & 1) ? dcu[i] : dcl[i];
-            }
-        }
-        // bin-major rows written by k_rt_half_bands: consecutive threads read consecutive half-layers of a bin
-        for (int t = threadIdx.x; t < a.H * NBX; t += blockDim.x) {
-            const int xs = t / a.H, h = t - xs * a.H, x = min(x_base + xs, a.X - 1);
-            const size_t src = ((size_t)col * a.X + x) * a.H + h;
-            sh_ray[(size_t)h * NBX + xs] = a.half_ray[src];
-            if (a.cloud_lds) {
-                sh_g0[(size_t)h * NBX + xs] = a.half_g0[src];
-                sh_cab[(size_t)h * NBX + xs] = a.half_cab[src];
-                sh_csc[(size_t)h * NBX + xs] = a.half_csc[src];
-            }
-        }
-    }
-    __syncthreads();
-    {
-        // thread -> (staged point q0, a run of consecutive levels): consecutive levels mostly fall into
-        // the same (T, P) cell of the table, whose four corners then stay in registers.  TS divides the
-        // workgroup size (both are powers of two).
-        const int q0 = threadIdx.x % TS, nrun = blockDim.x / TS, run = threadIdx.x / TS;
-        const int cq = c_of_q[q0];
-        if (a.from_table) {
-            // premixed k-table look-up done while staging (kernels.cu:561-608): the opacity arrays of
-            // the reference are not materialised on this path (hx_rt_get rebuilds them on demand)
-            const size_t sp = nc, st = nc * a.npress;
-            for (int pass = 0; pass < (a.iso ? 1 : 2); pass++) {
-                const int nlev = pass == 0 ? a.L : a.I;
-                const TPIndex* tp = (pass == 0 ? a.tp_lay : a.tp_int) + (size_t)col * a.I;
-                double* dst = pass == 0 ? sh_lay : sh_int;
-                const int per = (nlev + nrun - 1) / nrun;
-                const int l0 = run * per, l1 = min(nlev, l0 + per);
-                int ktd = -1, ktu = -1, kpd = -1, kpu = -1;
-                double c00 = 0, c01 = 0, c10 = 0, c11 = 0;
-                // (the cell of the next level is requested while this level's corners are on their way: the look-up was a
-                // chain of two dependent requests per level)
-                TPIndex knext = tp[min(l0, nlev - 1)];
-                for (int lev = l0; lev < l1; lev++) {
-                    double v = 0.0;
-                    const TPIndex k = knext;
-                    knext = tp[min(lev + 1, nlev - 1)];
-                    if (cq >= 0) {
-                        if (k.tdown != ktd || k.tup != ktu || k.pdown != kpd || k.pup != kpu) {
-                            const double* t0 = a.ktable + (size_t)cq + st * k.tdown;
-                            const double* t1 = a.ktable + (size_t)cq + st * k.tup;
-                            c00 = t0[sp * k.pdown];
-                            c01 = t0[sp * k.pup];
-                            c10 = t1[sp * k.pdown];
-                            c11 = t1[sp * k.pup];
-                            ktd = k.tdown; ktu = k.tup; kpd = k.pdown; kpu = k.pup;
-                        }
-                        v = blend_tp(c00, c01, c10, c11, k, false);
-                    }
-                    dst[(size_t)lev * TSP + q0] = v;
-                }
-            }
-        } else {
-            const double* opl = a.opac_wg_lay + col * wgI;
-            const double* opi = a.opac_wg_int + col * wgI;
-            for (int lev = run; lev < a.L; lev += nrun)
-                sh_lay[(size_t)lev * TSP + q0] = cq >= 0 ? opl[(size_t)cq + nc * lev] : 0.0;
-            if (!a.iso)
-                for (int lev = run; lev < a.I; lev += nrun)
-                    sh_int[(size_t)lev * TSP + q0] = cq >= 0 ? opi[(size_t)cq + nc * lev] : 0.0;
-        }
-    }
-    __syncthreads();
-    const int tl = blockIdx.x * COEF_TPB + wave;
-    if (tl >= ntiles) return;
-    const int j = lane % a.k, q = wave * a.S + lane / a.k;
-    const int c = c_of_q[q], x = x_of_q[q], xs = x - x_base;
-    const bool valid = c >= 0;
-    const hx_rt_column cp = a.colpar[col];
-    double* ctile = a.coef + col * a.coef_col + (size_t)tl * a.nplane * ROWS * 64;
-    const double nmu = -cp.mu_star;
-    const bool plain = a.clouds != 1 && a.scat_corr != 1 && a.g_0 == 0.0 && a.dir_beam != 1;
-    // The beam at the nodes of this lane's half-layers.  Half-layer h spans the nodes h (bottom) and h + 1 (top) -- even
-    // nodes are interfaces (F_dir_wg), odd ones layer centres (Fc_dir_wg); isothermal: node = interface -- so the top value
-    // of one row is the bottom value of the next: ONE load per row instead of two, requested a whole row of arithmetic
-    // (divisions, exp, sqrt) before it is used.  (Loaded where they were used, the compiler sent all of a tile's beam
-    // loads through one register pair, each waited for in turn: DESIGN.md section 4, tools/code_object_notes.py.)
-    const double* Fd = a.F_dir_wg + col * wgI;
-    const double* Fc = a.Fc_dir_wg + col * wgI;
-    auto beam_at_node = [&](int n) -> double {
-        if (!(a.dir_beam == 1 && valid && n <= a.H)) return 0.0;
-        if (a.iso) return Fd[(size_t)c + nc * n];
-        return (n & 1) ? Fc[(size_t)c + nc * (n >> 1)] : Fd[(size_t)c + nc * (n >> 1)];
-    };
-    double F_here = beam_at_node(j * ROWS), F_above = beam_at_node(j * ROWS + 1);
-    // `flux calculation method = matrix`: a spectral point none of whose (half-)layers scatters (w0 <= w_0_scat_limit in all
-    // of them: scat_trigger stays 0, kernels.cu:1102, :1240-1241) takes the solver's pure-absorption branch (:1969-2021,
-    // :2286-2421): F_out = T F_in + 2 pi eps P' -- the same affine form with alpha = T, beta = 0 and sources that are again
-    // u' B_near + v' B_far, so the planes serve both branches.  The trigger is a property of the whole column: the k lanes of a
-    // point vote before any of them writes a coefficient.
-    bool scatters = true;
-    if (a.matrix) {
-        bool mine = false;
-#pragma unroll 1
-        for (int r = 0; r < ROWS; r++) {
-            const int h = j * ROWS + r;
-            if (valid && h < a.H) {
-                const int i = a.iso ? h : h >> 1;
-                const bool lower = a.iso || (h & 1) == 0;
-                const int ii = lower ? i : i + 1;
-                double ray = 0.0, csc = 0.0, cab = 0.0;
-                if (a.cloud_lds) {
-                    cab = sh_cab[(size_t)h * NBX + xs];
-                    csc = sh_csc[(size_t)h * NBX + xs];
-                } else if (a.clouds == 1) {
-                    const size_t src = ((size_t)col * a.X + x) * a.H + h;
-                    cab = a.half_cab[src];
-                    csc = a.half_csc[src];
-                }
-                if (a.scat == 1) ray = sh_ray[(size_t)h * NBX + xs];
-                const double o_l = sh_lay[(size_t)i * TSP + q], o_i = a.iso ? o_l : sh_int[(size_t)ii * TSP + q];
-                const double kap = a.iso ? o_l : (lower ? (o_i + o_l) / 2.0 : (o_l + o_i) / 2.0);
-                mine = mine || single_scat_albedo(ray + csc, kap * sh_mu[h] + cab, a.w_0_limit) > a.w_0_scat_limit;
-            }
-        }
-        const unsigned long long votes = __ballot(mine);
-        const unsigned long long group = a.k >= 64 ? ~0ull : ((1ull << a.k) - 1ull) << (lane - j);
-        scatters = (votes & group) != 0ull;
-        if (valid && j == 0) a.trigger[col * nc + c] = scatters ? 1 : 0;
-    }
-    for (int r = 0; r < ROWS; r++) {
-        const int h = j * ROWS + r;
-        double alpha = 1.0, beta = 0.0, up = 0.0, vp = 0.0, dd = 0.0, du = 0.0;
-        const double Fbot = F_here, Ftop = F_above;
-        F_here = F_above;
-        F_above = beam_at_node(h + 2);      // the next row's top node: in flight during this row's arithmetic
-        if (valid && h < a.H) {
-            const int i = a.iso ? h : h >> 1;
-            const bool lower = a.iso || (h & 1) == 0;
-            // lower half averages (interface i, centre i); upper half (centre i, interface i+1); isothermal layers take
-            // the layer-centre values as they are
-            const int ii = lower ? i : i + 1;
-            double g0 = a.g_0, ray = 0.0, csc = 0.0, cab = 0.0;
-            if (a.cloud_lds) {
-                g0 = sh_g0[(size_t)h * NBX + xs];
-                cab = sh_cab[(size_t)h * NBX + xs];
-                csc = sh_csc[(size_t)h * NBX + xs];
-            } else if (a.clouds == 1) {  // the staged image would not fit the LDS: from the bin-major rows
-                const size_t src = ((size_t)col * a.X + x) * a.H + h;
-                g0 = a.half_g0[src];
-                cab = a.half_cab[src];
-                csc = a.half_csc[src];
-            }
-            if (a.scat == 1) ray = sh_ray[(size_t)h * NBX + xs];
-            const double o_l = sh_lay[(size_t)i * TSP + q], o_i = a.iso ? o_l : sh_int[(size_t)ii * TSP + q];
-            const double kap = a.iso ? o_l : (lower ? (o_i + o_l) / 2.0 : (o_l + o_i) / 2.0);
-            const double mu = sh_mu[h], dcol = sh_dc[h];
-            const double w0 = single_scat_albedo(ray + csc, kap * mu + cab, a.w_0_limit);
-            const double dtau_gas = dcol * (kap + ray / mu);
-            // `plain` (wave-uniform): no clouds, no I2S correction, g0 = 0, no beam -- the cloud term is an exact zero and
-            // E (1 - w0 g0) an exact one: the general formulas minus their no-ops, same bits (two_stream.h)
-            const double dtau = plain ? dtau_gas : dtau_gas + dcol * (cab + csc) / mu;
-            const Slab s = plain ? slab_coeffs_plain(w0, dtau, a.epsi)
-                                 : slab_coeffs(w0, dtau, g0, a.epsi, a.epsi2, cp.mu_star, a.scat_corr, a.i2s, a.dir_beam == 1);
-            if (a.diag != nullptr && a.dir_beam == 1) {  // G_limiter's warning (kernels.cu:217-231) as a count
-                const int nlim = (fabs(s.Gp) >= 1e8 ? 1 : 0) + (fabs(s.Gm) >= 1e8 ? 1 : 0);
-                if (nlim) atomicAdd(a.diag + HX_DIAG_G_LIMITED, (unsigned long long)nlim);
-            }
-            double invM = 1.0 / s.M;
-            alpha = s.P * invM;
-            beta = -s.N * invM;
-            double K = 2.0 * HX_PI * a.epsi * (1.0 - w0) / (s.E - w0);
-            double u, v;
-            if (!scatters) {
-                // pure absorption (matrix method, see above): down P' = B_b - T B_t + eps (T - 1) (B_b - B_t) / dtau, up the
-                // same with the nodes exchanged (kernels.cu:2300-2316, :2376-2411); thin or isothermal: (1 - T) (B_b + B_t) / 2
-                alpha = s.trans;
-                beta = 0.0;
-                invM = 1.0;
-                K = 2.0 * HX_PI * a.epsi;
-                if (a.iso || dtau < a.dtau_limit) {
-                    u = v = (1.0 - s.trans) / 2.0;
-                } else {
-                    const double gq = a.epsi * (s.trans - 1.0) / dtau;
-                    u = 1.0 + gq;
-                    v = -s.trans - gq;
-                }
-            } else if (a.iso || dtau < a.dtau_limit) {  // isothermal source: B (N + M - P) (kernels.cu:1442, :1640-1643)
-                u = v = (s.N + s.M - s.P) / 2.0;
-            } else {
-                const double qq = (plain ? a.epsi : a.epsi / (s.E * (1.0 - w0 * g0))) * (s.P - s.M + s.N) / dtau;
-                u = (s.M + s.N) + qq;
-                v = -s.P - qq;
-            }
-            up = K * u * invM;
-            vp = K * v * invM;
-            if (a.dir_beam == 1 && scatters) {
-                // beam at node h (bottom) and h+1 (top) of this half-layer: Fbot, Ftop from above
-                const double dn = Fbot / nmu * (s.Gm * s.M + s.Gp * s.N) - Ftop / nmu * s.Gm * s.P;
-                const double upw = Ftop / nmu * (s.Gm * s.N + s.Gp * s.M) - Fbot / nmu * s.P * s.Gp;
-                dd = dmin(0.0, dn) * invM;
-                du = dmin(0.0, upw) * invM;
-            }
-            if (h == 0) {
-                a.boaK[col * nc + c] = scatters ? (1.0 - w0) / (s.E - w0) : 1.0;   // (pure absorption: (1 - A) pi B_surf, :2349)
-                a.Fdir0[col * nc + c] = a.dir_beam == 1 ? (a.F_dir_wg + col * wgI)[c] : 0.0;
-            }
-        }
-        const size_t off = plane_off(r, lane, ROWS);
-        // written once per refresh, streamed by k_rt_flux afterwards: past the L2
-        __builtin_nontemporal_store(alpha, ctile + 0 * ROWS * 64 + off);
-        __builtin_nontemporal_store(beta, ctile + 1 * ROWS * 64 + off);
-        __builtin_nontemporal_store(up, ctile + 2 * ROWS * 64 + off);
-        if (a.has_vp) __builtin_nontemporal_store(vp, ctile + (size_t)a.pl_vp * ROWS * 64 + off);
-        if (a.dir_beam == 1) {
-            __builtin_nontemporal_store(dd, ctile + (size_t)a.pl_dd * ROWS * 64 + off);
-            __builtin_nontemporal_store(du, ctile + (size_t)(a.pl_dd + 1) * ROWS * 64 + off);
-        }
-    }
-}
+#define HX_COEF_KERNEL k_rt_coef
+#define HX_PLANE_T double
+#define HX_PLANE_ARG
+#define HX_PLANES a.coef
+#include "rt_coef_kernel.inc"
+#undef HX_COEF_KERNEL
+#undef HX_PLANE_T
+#undef HX_PLANE_ARG
+#undef HX_PLANES
+// fp32 planes (hx_rt_flags.coef_fp32).  The typed plane pointer is a kernel argument of its own: the fp64 kernels keep
+// their argument block as it was.  Instantiated in rt_fused_f32.hip only.
+#define HX_COEF_KERNEL k_rt_coef_f32
+#define HX_PLANE_T float
+#define HX_PLANE_ARG , float* coef32
+#define HX_PLANES coef32
+#include "rt_coef_kernel.inc"
+#undef HX_COEF_KERNEL
+#undef HX_PLANE_T
+#undef HX_PLANE_ARG
+#undef HX_PLANES
 
+#ifndef HX_PLANE_KERNELS_ONLY
 // gas optical depths of the half-layers in the reference's layout (needed by the direct beam only)
 __global__ void __launch_bounds__(256) k_rt_dtau_halves(KArgs a) {
     const int col = blockIdx.z, i = blockIdx.y;
@@ -711,6 +469,7 @@ __global__ void __launch_bounds__(256) k_rt_dtau_halves(KArgs a) {
     a.dtau_u[col * wgL + k] = a.dcol_u[(size_t)col * a.L + i] * (kap_up + ray_up / mu_up);
     a.dtau_l[col * wgL + k] = a.dcol_l[(size_t)col * a.L + i] * (kap_low + ray_low / mu_low);
 }
+#endif  // HX_PLANE_KERNELS_ONLY
 
 // ---- `flux calculation method = matrix`: the direct solve as three scans ------------------------------------------------------
 // The reference solves, per spectral point, the tridiagonal system of the down and up equations of all half-layers with the
@@ -811,367 +570,27 @@ __device__ __forceinline__ void moebius_scan_up(Moebius& P, int j, int k) {
                                  // (0: 320-thread workgroups, two wavefronts per SIMD, scratch; profiles/r06_deep_columns.txt)
 #endif
 constexpr bool flux_one_wave(int rows) { return rows >= 15 && HX_BIG_ROWS_ONE_WAVE; }
+#define HX_FLUX_HEAD __global__ void __launch_bounds__(flux_one_wave(ROWS) ? 64 : 320) k_rt_flux(FluxArgs a)
+#define HX_PLANE_T double
+#define HX_PLANES a.coef
+#include "rt_flux_kernel.inc"
+#undef HX_FLUX_HEAD
+#undef HX_PLANE_T
+#undef HX_PLANES
+#define HX_FLUX_HEAD __device__ __forceinline__ void rt_flux_f32_body(FluxArgs a, const float* coef32)
+#define HX_PLANE_T float
+#define HX_PLANES coef32
+#include "rt_flux_kernel.inc"
+#undef HX_FLUX_HEAD
+#undef HX_PLANE_T
+#undef HX_PLANES
+// fp32 planes (see k_rt_coef_f32); instantiated in rt_fused_f32.hip for the tilings without scratch only
 template <int ROWS, int K = 0, bool MATRIX = false>
-__global__ void __launch_bounds__(flux_one_wave(ROWS) ? 64 : 320) k_rt_flux(FluxArgs a) {
-    extern __shared__ __align__(16) double smem[];
-    const int col = a.reverse ? (int)(gridDim.y - 1 - blockIdx.y) : (int)blockIdx.y;
-    if (a.done[col]) return;
-    const int bx = a.reverse ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x;
-    // the workgroups this launch dispatches last leave their up-flux state in the Infinity Cache for the next launch
-    const bool keep_state_cached = (int)(blockIdx.y * gridDim.x + blockIdx.x) >= a.cache_state_from;
-    const int NN = a.H + 3, I = a.I;
-    double* sB = smem;                               // [nxb][NN]  Planck function at the nodes
-    double* acc = sB + (size_t)a.nxb * NN;           // [nxb][2][I] band fluxes being accumulated
-    double* stage = acc + (size_t)a.nxb * 2 * I;     // [ypb][nxb][2][I]
-    const hx_rt_column cp = a.colpar[col];
-    const size_t nc = (size_t)a.Y * a.X;
-    const int k = K ? K : a.k;
-
-    for (int t = threadIdx.x; t < a.nxb * NN; t += blockDim.x) {
-        const int xl = t / NN, n = t - xl * NN, x = bx * a.nxb + xl;
-        sB[t] = x < a.X ? a.Bn[((size_t)col * a.X + x) * NN + n] : 0.0;
-    }
-    for (int t = threadIdx.x; t < a.nxb * 2 * I; t += blockDim.x) acc[t] = 0.0;
-    __syncthreads();
-
-    for (int part = 0; part < a.nparts; part++) {
-        const LaneMap m = lane_map(a, bx, part, opaque_tid());
-        // coefficient planes and up-flux state -> registers.  The tiles are streamed once per launch: non-temporal
-        // loads AND stores together keep them from displacing the node and band arrays the neighbouring kernels and
-        // the next workgroups find in the L2 (same-box A/B: k_rt_flux 400 -> 386 us, k_rt_nodes 16 -> 14.4,
-        // k_rt_totals_a 16 -> 12.7; either hint alone changes nothing)
-        const size_t toff = m.tile * (size_t)ROWS * 64 + m.lane;
-        const double* ctile = a.coef + col * a.coef_col + m.tile * (size_t)a.nplane * ROWS * 64 + m.lane;
-        double* utile = a.Utile + col * a.flux_col + toff;
-        double al[ROWS], be[ROWS], sd[ROWS], su[ROWS], Uo[ROWS], Do[ROWS];
-#pragma unroll
-        for (int r = 0; r < ROWS; r++) {
-            al[r] = __builtin_nontemporal_load(ctile + (0 * ROWS + r) * 64);
-            be[r] = __builtin_nontemporal_load(ctile + (1 * ROWS + r) * 64);
-            sd[r] = __builtin_nontemporal_load(ctile + (2 * ROWS + r) * 64);  // u' for now
-            if (!MATRIX) Uo[r] = __builtin_nontemporal_load(utile + r * 64);
-        }
-        if (a.has_vp) {
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) su[r] = __builtin_nontemporal_load(ctile + (a.pl_vp * ROWS + r) * 64);  // v' for now
-        } else {
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) su[r] = a.Kconst * ((1.0 - al[r]) - be[r]) - sd[r];
-        }
-        double U0 = 0.0, boaK = 0.0, Fdir0 = 0.0, albedo = 0.0;
-        if (m.valid && m.j == 0) {
-            if (!MATRIX) U0 = a.U0[col * nc + m.sp];
-            boaK = a.boaK[col * nc + m.sp];
-            Fdir0 = a.Fdir0[col * nc + m.sp];
-            albedo = a.surf_albedo[(size_t)col * a.X + m.x];
-        }
-        // the quadrature weight is requested here, with the tiles: asked for after the sweeps it was a dependent load
-        // into a saturated memory system, several microseconds per tile with nothing to hide behind
-        const double w = m.valid ? 0.5 * a.gauss_w[m.y] : 0.0;
-        const double* Bx = sB + (size_t)(m.valid ? m.xl : 0) * NN;
-#pragma unroll
-        for (int r = 0; r < ROWS; r++) {
-            const int h = min(m.j * ROWS + r, a.H - 1);
-            const double Bb = Bx[h], Bt = a.iso ? Bb : Bx[h + 1], upc = sd[r], vpc = su[r];
-            sd[r] = upc * Bb + vpc * Bt;
-            su[r] = upc * Bt + vpc * Bb;
-        }
-        if (a.dir_beam == 1) {
-            // The rows of the two beam planes are requested in groups that are in flight together, and only then added: left
-            // to the scheduler, the loads came out as ONE register pair loaded and added once per row -- 14 (7 rows) or 26
-            // (13 rows) dependent memory round trips per tile; k_rt_flux<7, 64> took 3.70 instead of 3.40 ms per launch at
-            // config 5 (whether it happened depended on unrelated code: round 3's build had the 14 in flight together).
-            // Up to 8 rows per lane all at once; 13 rows in groups of BEAM_GROUP (the register file is full there).
-            constexpr int BEAM_GROUP = ROWS <= 8 ? ROWS : HX_BEAM_GROUP;
-#pragma unroll
-            for (int r0 = 0; r0 < ROWS; r0 += BEAM_GROUP) {
-                double bd[BEAM_GROUP], bu[BEAM_GROUP];
-#pragma unroll
-                for (int u = 0; u < BEAM_GROUP; u++)
-                    if (r0 + u < ROWS) {
-                        bd[u] = __builtin_nontemporal_load(ctile + (a.pl_dd * ROWS + r0 + u) * 64);
-                        bu[u] = __builtin_nontemporal_load(ctile + ((a.pl_dd + 1) * ROWS + r0 + u) * 64);
-                    }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int u = 0; u < BEAM_GROUP; u++)
-                    if (r0 + u < ROWS) {
-                        sd[r0 + u] += bd[u];
-                        su[r0 + u] += bu[u];
-                    }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        const double rs = cp.R_star / cp.a;
-        const double D_toa = (1.0 - a.dir_beam) * cp.f_factor * (rs * rs) * HX_PI * Bx[a.H + 1];
-        const double B_surf = Bx[a.H + 2];
-
-        // rows (r even, r odd) of this lane whose up-flux the reference makes positive when it is tiny: the odd nodes
-        const bool odd0 = (m.j * ROWS) & 1;
-        const double thr_even = (a.iso || odd0) ? 1e-100 : 0.0, thr_odd = (a.iso || !odd0) ? 1e-100 : 0.0;
-        if constexpr (MATRIX) {
-            // which values the reference makes positive: with scattering (Thomas, non-isothermal) every x < 1e-100 of the back-
-            // substitution becomes |x| (kernels.cu:2268), with isothermal layers none (:1967); in the pure-absorption sweeps tiny
-            // values do (:2329, :2351, :2418, and -- isothermal -- :1990, :2018), the up-flux at the layer centres excepted (:2394)
-            const bool scatters = m.valid ? a.trigger[col * nc + m.sp] != 0 : false;
-            const bool flip_negative = scatters && !a.iso;
-            const double tiny_d = scatters ? 0.0 : 1e-100;
-            const double tiny_u_even = scatters ? 0.0 : ((a.iso || odd0) ? 1e-100 : 0.0), tiny_u_odd = scatters ? 0.0 : ((a.iso || !odd0) ? 1e-100 : 0.0);
-            auto patch = [&](double v, double tiny) { return flip_negative ? (v < 1e-100 ? fabs(v) : v) : tiny_abs_below(v, tiny); };
-            // ---------------- rho: surface -> TOA ----------------
-            // (the tiles' padding rows and lanes hold alpha = 1, beta = 0: the identity)
-            Moebius P = {1.0, 0.0, 0.0, 1.0};
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) {
-                const double ga = fma(al[r], al[r], -(be[r] * be[r]));
-                const double n11 = fma(ga, P.p11, be[r] * P.p21), n12 = fma(ga, P.p12, be[r] * P.p22);
-                P.p21 = fma(-be[r], P.p11, P.p21);
-                P.p22 = fma(-be[r], P.p12, P.p22);
-                P.p11 = n11;
-                P.p12 = n12;
-            }
-            {   // entries near one before the lanes are combined: a stack of thick, nearly conservative scatterers shrinks the
-                // product by 4e-5 per row, and only the ratios matter
-                const double sc = 1.0 / fmax(fmax(fabs(P.p11), fabs(P.p12)), fmax(fabs(P.p21), fabs(P.p22)));
-                P.p11 *= sc; P.p12 *= sc; P.p21 *= sc; P.p22 *= sc;
-            }
-            moebius_scan_up<K>(P, m.j, k);
-            double e11 = K ? below_fixed<K>(P.p11) : from_lane_below<1>(P.p11, k), e12 = K ? below_fixed<K>(P.p12) : from_lane_below<1>(P.p12, k);
-            double e21 = K ? below_fixed<K>(P.p21) : from_lane_below<1>(P.p21, k), e22 = K ? below_fixed<K>(P.p22) : from_lane_below<1>(P.p22, k);
-            const double alb = K ? group_first_lane<K>(albedo, m.lane) : __shfl(albedo, 0, k);
-            double rho = fma(e11, alb, e12) / fma(e21, alb, e22);   // at this lane's lowest node
-            if (m.j == 0) rho = alb;
-            // per row: a = alpha / (1 - beta rho_b) -- the factor of BOTH affine recurrences --, the constant of the sigma
-            // recurrence s_up + a rho_b s_down, what the D recurrence needs: beta / (1 - beta rho_b), s_down / (1 - beta rho_b),
-            // and rho at the row's top node (kept where the sweeps keep their up-flux)
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) {
-                const double inv = HX_MATRIX_RCP(1.0 - be[r] * rho), aa = al[r] * inv;
-                su[r] = fma(aa * rho, sd[r], su[r]);
-                rho = fma(aa * al[r], rho, be[r]);
-                Uo[r] = rho;
-                be[r] *= inv;
-                sd[r] *= inv;
-                al[r] = aa;
-            }
-            // ---------------- sigma: surface -> TOA ----------------
-            double sigma0 = 0.0;
-            if (m.j == 0) sigma0 = albedo * Fdir0 + (1.0 - albedo) * HX_PI * boaK * B_surf;
-            sigma0 = K ? group_first_lane<K>(sigma0, m.lane) : __shfl(sigma0, 0, k);
-            {
-                double A = 1.0, Bc = 0.0;
-#pragma unroll
-                for (int r = 0; r < ROWS; r++) {
-                    Bc = fma(al[r], Bc, su[r]);
-                    A *= al[r];
-                }
-                if (K) {
-                    scan_up_fixed<K>(A, Bc, m.j);
-                } else if (k == 32) {
-                    scan32_up(A, Bc, m.j);
-                } else {
-                    scan_step_up<1>(A, Bc, m.j, k);
-                    scan_step_up<2>(A, Bc, m.j, k);
-                    scan_step_up<4>(A, Bc, m.j, k);
-                    scan_step_up<8>(A, Bc, m.j, k);
-                    scan_step_up<16>(A, Bc, m.j, k);
-                    scan_step_up<32>(A, Bc, m.j, k);
-                }
-                double sg = K ? below_fixed<K>(fma(A, sigma0, Bc)) : from_lane_below<1>(fma(A, sigma0, Bc), k);
-                if (m.j == 0) sg = sigma0;
-#pragma unroll
-                for (int r = 0; r < ROWS; r++) {
-                    sd[r] = fma(be[r], sg, sd[r]);      // constant of the D recurrence: (beta sigma_bottom + s_down) / (1 - beta rho_b)
-                    sg = fma(al[r], sg, su[r]);
-                    su[r] = sg;                         // sigma at the row's top node
-                }
-            }
-            // ---------------- D: TOA -> surface, and U = rho D + sigma ----------------
-            {
-                double A = 1.0, Bc = 0.0;
-#pragma unroll
-                for (int r = ROWS - 1; r >= 0; r--) {
-                    Bc = fma(al[r], Bc, sd[r]);
-                    A *= al[r];
-                }
-                if (K) {
-                    scan_down_fixed<K>(A, Bc, m.j, m.lane);
-                } else if (k == 32) {
-                    scan32_down(A, Bc, m.j, m.lane);
-                } else {
-                    scan_step_down<1>(A, Bc, m.j, k);
-                    scan_step_down<2>(A, Bc, m.j, k);
-                    scan_step_down<4>(A, Bc, m.j, k);
-                    scan_step_down<8>(A, Bc, m.j, k);
-                    scan_step_down<16>(A, Bc, m.j, k);
-                    scan_step_down<32>(A, Bc, m.j, k);
-                }
-                double D = K ? above_fixed<K>(fma(A, D_toa, Bc)) : from_lane_above<1>(fma(A, D_toa, Bc), k);
-                if (m.j == k - 1) D = D_toa;
-#pragma unroll
-                for (int r = ROWS - 1; r >= 0; r--) {
-                    Uo[r] = patch(fma(Uo[r], D, su[r]), (r & 1) ? tiny_u_odd : tiny_u_even);   // U at the top node, D there still in hand
-                    D = patch(fma(al[r], D, sd[r]), tiny_d);
-                    Do[r] = D;
-                }
-            }
-            if (m.j == 0) U0 = patch(fma(albedo, Do[0], sigma0), 0.0);
-        } else
-        for (int sweep = 0; sweep < a.nsweep; sweep++) {
-            // ---------------- down: TOA -> BOA ----------------
-            {
-                double Ubelow = K ? below_fixed<K>(Uo[ROWS - 1]) : from_lane_below<1>(Uo[ROWS - 1], k);  // U at the bottom node of this chunk
-                if (m.j == 0) Ubelow = U0;
-                double A = 1.0, Bc = 0.0;
-#pragma unroll
-                for (int r = ROWS - 1; r >= 0; r--) {
-                    const double Uh = r > 0 ? Uo[r - 1] : Ubelow;
-                    const double t = fma(be[r], Uh, sd[r]);
-                    Bc = fma(al[r], Bc, t);
-                    A *= al[r];
-                }
-                // inclusive suffix composition over the k lanes of this spectral point
-                if (K) {
-                    scan_down_fixed<K>(A, Bc, m.j, m.lane);
-                } else if (k == 32) {
-                    scan32_down(A, Bc, m.j, m.lane);
-                } else {
-                    scan_step_down<1>(A, Bc, m.j, k);
-                    scan_step_down<2>(A, Bc, m.j, k);
-                    scan_step_down<4>(A, Bc, m.j, k);
-                    scan_step_down<8>(A, Bc, m.j, k);
-                    scan_step_down<16>(A, Bc, m.j, k);
-                    scan_step_down<32>(A, Bc, m.j, k);
-                }
-                double Din = K ? above_fixed<K>(fma(A, D_toa, Bc)) : from_lane_above<1>(fma(A, D_toa, Bc), k);
-                if (m.j == k - 1) Din = D_toa;
-                double D = Din;
-#pragma unroll
-                for (int r = ROWS - 1; r >= 0; r--) {
-                    const double Uh = r > 0 ? Uo[r - 1] : Ubelow;
-                    D = tiny_abs(fma(al[r], D, fma(be[r], Uh, sd[r])));
-                    Do[r] = D;
-                }
-            }
-            // ---------------- BOA boundary ----------------
-            if (m.j == 0) U0 = albedo * (Fdir0 + Do[0]) + (1.0 - albedo) * HX_PI * boaK * B_surf;
-            const double Ubc = K ? group_first_lane<K>(U0, m.lane) : __shfl(U0, 0, k);
-            // ---------------- up: BOA -> TOA ----------------
-            {
-                double Dabove = K ? above_fixed<K>(Do[0]) : from_lane_above<1>(Do[0], k);  // D at the top node of this chunk
-                if (m.j == k - 1) Dabove = D_toa;
-                double A = 1.0, Bc = 0.0;
-#pragma unroll
-                for (int r = 0; r < ROWS; r++) {
-                    const double Dh = r < ROWS - 1 ? Do[r + 1] : Dabove;
-                    const double t = fma(be[r], Dh, su[r]);
-                    Bc = fma(al[r], Bc, t);
-                    A *= al[r];
-                }
-                if (K) {
-                    scan_up_fixed<K>(A, Bc, m.j);
-                } else if (k == 32) {
-                    scan32_up(A, Bc, m.j);
-                } else {
-                    scan_step_up<1>(A, Bc, m.j, k);
-                    scan_step_up<2>(A, Bc, m.j, k);
-                    scan_step_up<4>(A, Bc, m.j, k);
-                    scan_step_up<8>(A, Bc, m.j, k);
-                    scan_step_up<16>(A, Bc, m.j, k);
-                    scan_step_up<32>(A, Bc, m.j, k);
-                }
-                double Uin = K ? below_fixed<K>(fma(A, Ubc, Bc)) : from_lane_below<1>(fma(A, Ubc, Bc), k);
-                if (m.j == 0) Uin = Ubc;
-                double U = Uin;
-#pragma unroll
-                for (int r = 0; r < ROWS; r++) {
-                    const double Dh = r < ROWS - 1 ? Do[r + 1] : Dabove;
-                    U = fma(al[r], U, fma(be[r], Dh, su[r]));
-                    // interface nodes only (reference quirk, kernels.cu:1763; isothermal layers: every node, :1509)
-                    if (K) U = tiny_abs_below(U, (r & 1) ? thr_odd : thr_even);
-                    else if (a.iso || ((m.j * ROWS + r) & 1)) U = tiny_abs(U);
-                    Uo[r] = U;
-                }
-            }
-        }
-
-        // Gauss quadrature of the interface fluxes: stage[yl][xl][dir][i], summed over yl in order.
-        // The lane map is derived afresh (e for "epilogue"): carried across the sweeps it lived in scratch
-        const LaneMap e = lane_map(a, bx, part, opaque_tid());
-#ifdef HX_PROFILING  // HELIOS_RT_DEBUG_SKIP: bit 0 no quadrature, bit 1 no state stores -- not in the shipped library
-        const int debug_skip = a.debug_skip;
-#else
-        constexpr int debug_skip = 0;
-#endif
-        auto store_state = [&]() {
-            const size_t eoff = e.tile * (size_t)ROWS * 64 + e.lane;
-            if (!(debug_skip & 2) && (!MATRIX || a.keep_up)) {   // (a direct solve has no state: its spectral fluxes are
-                double* ut = a.Utile + col * a.flux_col + eoff;   //  written where somebody asks for them, hx_rt_get)
-#pragma unroll
-                for (int r = 0; r < ROWS; r++) {
-                    // (write-through store that leaves the line in the Infinity Cache: agent scope = `sc1`; see launch_flux)
-                    if (keep_state_cached) __hip_atomic_store(ut + r * 64, Uo[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    else __builtin_nontemporal_store(Uo[r], ut + r * 64);
-                }
-            }
-            if (a.keep_down) {
-                double* dtile = a.Dtile + col * a.flux_col + eoff;
-#pragma unroll
-                for (int r = 0; r < ROWS; r++) __builtin_nontemporal_store(Do[r], dtile + r * 64);
-            }
-            if (e.valid && e.j == 0) a.U0[col * nc + e.sp] = U0;
-        };
-        if (!(debug_skip & 1)) {
-            if (e.valid) {
-                // Row r of this lane is node h = h0 + r.  Staggered grid: an even node gives D at interface h/2, an odd
-                // one U at interface (h+1)/2 -- with the lane's parity p folded into two base pointers the rows use
-                // compile-time offsets (26 separately computed LDS addresses did not fit the register file: they were
-                // reloaded from scratch, one memory round trip per row and tile)
-                const int h0 = e.j * ROWS, nrow = a.H - h0;
-                double* st = stage + ((size_t)e.yl * a.nxb + e.xl) * 2 * I;
-                if (a.iso) {                                            // every node is an interface
-                    double *pd = st + h0, *pu = st + I + h0 + 1;
-#pragma unroll
-                    for (int r = 0; r < ROWS; r++)
-                        if (r < nrow) {
-                            pd[r] = w * Do[r];
-                            pu[r] = w * Uo[r];
-                        }
-                } else {
-                    const bool p = h0 & 1;
-                    const int q = (h0 + (p ? 1 : 0)) >> 1;
-                    double* pe = st + q + (p ? I : 0);                  // rows 0, 2, ...: D (p = 0) or U (p = 1)
-                    double* po = st + q + (p ? -1 : I);                 // rows 1, 3, ...: U (p = 0) or D (p = 1)
-#pragma unroll
-                    for (int r = 0; r < ROWS; r++)
-                        if (r < nrow) {
-                            if ((r & 1) == 0) pe[r >> 1] = w * (p ? Uo[r] : Do[r]);
-                            else po[(r + 1) >> 1] = w * (p ? Do[r] : Uo[r]);
-                        }
-                }
-                if (e.j == 0) st[I + 0] = w * U0;
-                if (h0 <= a.H - 1 && a.H - 1 < h0 + ROWS) st[a.L] = w * D_toa;
-            }
-            __syncthreads();
-            for (int t = threadIdx.x; t < a.nxb * 2 * I; t += blockDim.x) {
-                const int xl = t / (2 * I), rest = t - xl * 2 * I;
-                double s = acc[t];
-                for (int yl = 0; yl < a.ypb; yl++) s += stage[((size_t)yl * a.nxb + xl) * 2 * I + rest];
-                acc[t] = s;
-            }
-            __syncthreads();
-        }
-        store_state();
-    }
-    // band fluxes of this workgroup's bins, internal layout [x][i]
-    for (int t = threadIdx.x; t < a.nxb * 2 * I; t += blockDim.x) {
-        const int xl = t / (2 * I), rest = t - xl * 2 * I, x = bx * a.nxb + xl;
-        if (x >= a.X) continue;
-        const int dir = rest / I, i = rest - dir * I;
-        (dir == 0 ? a.F_down_band_n : a.F_up_band_n)[((size_t)col * a.X + x) * I + i] = acc[t];
-    }
+__global__ void __launch_bounds__(flux_one_wave(ROWS) ? 64 : 320) k_rt_flux_f32(FluxArgs a, const float* coef32) {
+    rt_flux_f32_body<ROWS, K, MATRIX>(a, coef32);
 }
 
+#ifndef HX_PLANE_KERNELS_ONLY
 // ---- `flux calculation method = matrix`: glue between the node arrays of the loop and the per-stage solver -------------
 // Planck values of the nodes, Bn[x][H+3], in the reference's layouts: planckband_lay[i + x (L+2)] (layers, then the stellar
 // row and the surface) and planckband_int[i + x I].  grid (chunks, C).
@@ -1687,4 +1106,14 @@ __global__ void __launch_bounds__(256) k_rt_tile_rows(const double* __restrict__
     if (x < X) out[x + (size_t)X * i] = src[x];
 }
 
+#endif  // HX_PLANE_KERNELS_ONLY
+
+// ---- fp32 coefficient planes (`precision = single`, hx_rt_flags.coef_fp32): rt_fused_f32.hip -----------------------------
+// The tilings with an fp32 instantiation: every tiling choose_geometry selects without scratch (columns of up to 416
+// layers, isothermal ones up to 512).  Other tilings run on fp64 planes.
+bool coef_fp32_tiling(int rows, int k, bool generic_scans);
+// the launches of launch_coef_tpb / launch_flux on rt->coef32 (ROWS, k and the method are the batch's: rt->g, rt->matrix_scan)
+void launch_coef_f32(hx_rt* rt, const KArgs& a, int tpb, dim3 grid, size_t shmem);
+void launch_flux_f32(hx_rt* rt, const FluxArgs& f, dim3 grid, size_t shmem);
+hipError_t raise_flux_shmem_f32(hx_rt* rt, int shmem);
 }  // namespace hx

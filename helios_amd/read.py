@@ -348,8 +348,10 @@ class Read(object):
         self.synthetic_spec = val["synthetic_spec"]
 
         # ---- derived settings (read.py:884-985) ----
-        if quant.prec != "double":
-            raise IOError("ERROR: this build computes in double precision only (SURVEY.md Q16)")
+        # `single` stores the device-resident loop's coefficient planes in fp32 (hx_rt_flags.coef_fp32); every other
+        # array, all arithmetic and the output files stay fp64 (README, "precision = single")
+        if quant.prec not in ("double", "single"):
+            raise IOError("ERROR: precision must be 'double' or 'single', not %r" % (quant.prec,))
         quant.fl_prec, quant.nr_bytes = np.float64, 8
         if quant.run_type == "iterative":
             quant.singlewalk, quant.iso, quant.energy_correction = i32(0), i32(0), i32(1)

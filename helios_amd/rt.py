@@ -25,7 +25,7 @@ class RtFlags(ctypes.Structure):
                 ("smooth", ctypes.c_int32), ("real_star", ctypes.c_int32),
                 ("planet_type_gas", ctypes.c_int32), ("kcoeff_mixing_ro", ctypes.c_int32),
                 ("debug", ctypes.c_int32), ("iso", ctypes.c_int32), ("singlewalk", ctypes.c_int32),
-                ("matrix", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3),
+                ("matrix", ctypes.c_int32), ("coef_fp32", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2),
                 ("epsi", ctypes.c_double), ("epsi2", ctypes.c_double), ("g_0", ctypes.c_double),
                 ("i2s_transition", ctypes.c_double), ("w_0_limit", ctypes.c_double),
                 ("w_0_scat_limit", ctypes.c_double), ("delta_tau_limit", ctypes.c_double),
@@ -255,25 +255,39 @@ class RTBatch(object):
                  "hx_rt_profile_read")
         return ms.value, n.value
 
+    def coef_plane_bytes(self):
+        """bytes per coefficient-plane element the batch uses: 4 with `precision = single` where its tiling has fp32
+        planes, else 8"""
+        out = np.zeros(1, np.int32)
+        self._ck(self._l.hx_rt_get(self.handle, -1, b"coef_plane_bytes", out.ctypes.data_as(ctypes.c_void_p), out.nbytes),
+                 "hx_rt_get(coef_plane_bytes)")
+        return int(out[0])
+
     def close(self):
         if self.handle:
             self._l.hx_rt_destroy(self.handle)
             self.handle = None
 
 
+def case_flags(c):
+    """hx_rt_flags of a case dict that uses the reference's Store attribute names (batch_from_case)"""
+    return dict(scat=int(c.scat), dir_beam=int(c.dir_beam), clouds=int(c.clouds),
+                scat_corr=int(c.scat_corr), geom_zenith_corr=int(c.geom_zenith_corr),
+                smooth=int(c.smooth), real_star=int(c.real_star),
+                planet_type_gas=0 if c.get("planet_type", "gas") == "rocky" else 1,
+                kcoeff_mixing_ro=0 if c.get("kcoeff_mixing", "RO") == "correlated-k" else 1, iso=int(c.get("iso", 0)),
+                singlewalk=int(c.get("singlewalk", 0)), matrix=1 if c.get("flux_calc_method", "iteration") == "matrix" else 0,
+                coef_fp32=1 if c.get("prec", "double") == "single" else 0,
+                epsi=float(c.epsi), epsi2=float(c.epsi2), g_0=float(c.g_0),
+                i2s_transition=float(c.i2s_transition), w_0_limit=float(c.w_0_limit),
+                w_0_scat_limit=float(c.w_0_scat_limit), delta_tau_limit=float(c.delta_tau_limit))
+
+
 def batch_from_case(ctx, c, ncol=1, nspecies=0, columns=None):
     """build an RTBatch from a dict-like problem description that uses the reference's Store attribute
     names (tests/cases.py, helios_amd.quantities.Store): every column gets the same inputs, except for the
     per-column parameters given in `columns` (a list of ncol dicts overriding g, a, F_intern, ...)."""
-    flags = dict(scat=int(c.scat), dir_beam=int(c.dir_beam), clouds=int(c.clouds),
-                 scat_corr=int(c.scat_corr), geom_zenith_corr=int(c.geom_zenith_corr),
-                 smooth=int(c.smooth), real_star=int(c.real_star),
-                 planet_type_gas=0 if c.get("planet_type", "gas") == "rocky" else 1,
-                 kcoeff_mixing_ro=0 if c.get("kcoeff_mixing", "RO") == "correlated-k" else 1, iso=int(c.get("iso", 0)),
-                 singlewalk=int(c.get("singlewalk", 0)), matrix=1 if c.get("flux_calc_method", "iteration") == "matrix" else 0,
-                 epsi=float(c.epsi), epsi2=float(c.epsi2), g_0=float(c.g_0),
-                 i2s_transition=float(c.i2s_transition), w_0_limit=float(c.w_0_limit),
-                 w_0_scat_limit=float(c.w_0_scat_limit), delta_tau_limit=float(c.delta_tau_limit))
+    flags = case_flags(c)
     col = dict(g=float(c.g), a=float(c.a), R_planet=float(c.R_planet), R_star=float(c.R_star),
                T_star=float(c.T_star), f_factor=float(c.f_factor), mu_star=float(c.mu_star),
                F_intern=float(c.F_intern), rad_convergence_limit=float(c.rad_convergence_limit),

@@ -340,7 +340,12 @@ typedef struct hx_rt_flags {
                                      iteration (fband_matrix_*, computation.py:625-710) instead of the sweeps.  The batch
                                      then holds the reference's per-half-layer arrays (calc_trans_*' outputs, ~20 arrays of
                                      ny*nbin*nlayer doubles per column) in place of the compact coefficient tiles */
-    int32_t reserved[3];
+    int32_t coef_fp32;            /* 1 = `precision = single`: the coefficient planes (alpha, beta, u', v', dd, du) are stored
+                                     in fp32 -- rounded once when written, widened to fp64 when read; all arithmetic and every
+                                     other array stay fp64.  The matrix method and tilings without an fp32 variant (columns of
+                                     more than 416 layers, 512 isothermal) keep fp64 planes; hx_rt_get(rt, -1,
+                                     "coef_plane_bytes", &int32, 4) says which width is in use (4 or 8) */
+    int32_t reserved[2];
     double epsi, epsi2, g_0, i2s_transition, w_0_limit, w_0_scat_limit, delta_tau_limit;
     double reserved_d[9];
 } hx_rt_flags;

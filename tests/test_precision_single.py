@@ -1,0 +1,240 @@
+"""`precision = single` without a GPU: the parameter is read from the file and the command line, reaches hx_rt_flags as
+coef_fp32, leaves the C-ABI structs as they were, and the library's fp32-plane kernels (k_rt_coef_f32, k_rt_flux_f32) are
+held to what the fp64 kernels of the selectable tilings are held to in tests/test_abi.py: no scratch, no spilled VGPRs,
+grouped tile loads -- read from the code objects' own notes."""
+import ctypes
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+
+from helios_amd import _lib
+from helios_amd.read import Read
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+class Q(object):
+    fl_prec = np.float64
+    no_atmo_mode = 0
+
+
+def _read(tmp_path, file_value=None, argv=()):
+    p = tmp_path / "param.dat"
+    text = "name = abc [x]\n"
+    if file_value is not None:
+        text += "precision = %s [double, single] (CL: Y)\n" % file_value
+    p.write_text(text)
+    r, q = Read(), Q()
+    r.read_param_file_and_command_line(q, None, ["-parameter_file", str(p)] + list(argv))
+    return q
+
+
+def _notes_module():
+    spec = importlib.util.spec_from_file_location("code_object_notes", os.path.join(ROOT, "tools", "code_object_notes.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_single_precision_is_read_from_the_file_and_the_command_line(tmp_path):
+    for file_value, argv in (("single", ()), (None, ("-precision", "single")), ("double", ("-precision", "single"))):
+        q = _read(tmp_path, file_value, argv)
+        assert q.prec == "single"
+        assert q.fl_prec is np.float64 and q.nr_bytes == 8        # host arrays and output files stay fp64
+    assert _read(tmp_path).prec == "double"
+    assert _read(tmp_path, "single", ("-precision", "double")).prec == "double"
+
+
+def test_other_precisions_are_refused(tmp_path):
+    for file_value, argv in (("half", ()), (None, ("-precision", "float")), ("single", ("-precision", "quad"))):
+        with pytest.raises(IOError, match="precision"):
+            _read(tmp_path, file_value, argv)
+
+
+def test_rt_flags_carry_coef_fp32(tmp_path):
+    from helios_amd.computation import Compute
+    from helios_amd.rt import RtFlags
+    for value, want in (("single", 1), ("double", 0)):
+        q = _read(tmp_path, value)
+        q.planet_type = "gas"
+        # (set later in a run: the star, the cloud decks, the limits of the flux solver)
+        for name in ("real_star", "clouds", "smooth", "geom_zenith_corr", "w_0_limit", "w_0_scat_limit", "delta_tau_limit"):
+            if not hasattr(q, name):
+                setattr(q, name, 0)
+        f = Compute._rt_flags(q)
+        assert f["coef_fp32"] == want
+        flags = RtFlags()
+        for k, v in f.items():
+            setattr(flags, k, v)
+        assert flags.coef_fp32 == want
+
+
+def test_batch_from_case_takes_the_store_attribute():
+    """tests and tools build batches from case dicts with the Store's attribute names: `prec` as well"""
+    import cases
+    from helios_amd.rt import case_flags
+    c = cases.make_case()
+    assert case_flags(c)["coef_fp32"] == 0                  # (no `prec`: double)
+    c.prec = "single"
+    assert case_flags(c)["coef_fp32"] == 1
+    c.prec = "double"
+    assert case_flags(c)["coef_fp32"] == 0
+
+
+def test_the_driver_names_the_reason_for_fp64_planes(monkeypatch):
+    from helios_amd.computation import Compute
+
+    class Q(object):
+        flux_calc_method, nlayer, iso = "iteration", 500, 0
+    assert "500 layers" in Compute._why_fp64_planes(Q())
+    Q.nlayer, Q.flux_calc_method = 100, "matrix"
+    why = Compute._why_fp64_planes(Q())
+    assert "matrix method" in why and "layers" not in why
+    Q.iso, Q.nlayer, Q.flux_calc_method = 1, 500, "iteration"
+    assert "layers" not in Compute._why_fp64_planes(Q())     # (isothermal: 512 layers have an fp32 tiling)
+
+
+_DRIVER = r"""
+#include <cstdio>
+#include "plane_code.h"
+int main() {
+    double a, b;
+    while (std::scanf("%lf %lf", &a, &b) == 2) {
+        const float c0 = hx::plane0_code(a, b), c1 = hx::plane1_code(b);
+        double al = c0, be = c1;
+        const double rest = hx::plane_decode(al, be);
+        std::printf("%.17g %.17g %.17g\n", al, be, rest);
+    }
+    return 0;
+}
+"""
+
+
+def _plane_round_trip(tmp_path, pairs):
+    """alpha, beta, rest after plane0_code / plane1_code / plane_decode of csrc/plane_code.h, compiled for the host"""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    src, exe = tmp_path / "planes.cpp", tmp_path / "planes"
+    src.write_text(_DRIVER)
+    subprocess.run([cxx, "-std=c++17", "-O2", "-ffp-contract=off", "-I", os.path.join(ROOT, "helios_amd", "csrc"), str(src),
+                    "-o", str(exe)], check=True, capture_output=True)
+    text = "\n".join("%r %r" % (float(a), float(b)) for a, b in pairs) + "\n"
+    out = subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout
+    return np.array([[float(v) for v in ln.split()] for ln in out.strip().split("\n")])
+
+
+def _slab_plain(w0, dtau, epsi=0.5):
+    """alpha = P / M and beta = -N / M of two_stream.h's slab_coeffs_plain (isotropic, no I2S), in fp64"""
+    trans = np.exp(-2.0 * np.sqrt(1.0 - w0) * dtau / epsi ** 0.5 * epsi ** 0.5 / epsi)
+    zeta_m = (1.0 - np.sqrt(1.0 - w0)) / 2.0
+    zeta_p = (1.0 + np.sqrt(1.0 - w0)) / 2.0
+    M = zeta_m ** 2 * trans ** 2 - zeta_p ** 2
+    N = zeta_p * zeta_m * (1.0 - trans ** 2)
+    P = (zeta_m ** 2 - zeta_p ** 2) * trans
+    return P / M, -N / M
+
+
+def test_plane_coding_keeps_alpha_beta_and_rest(tmp_path):
+    """the fp32 planes' coding (csrc/plane_code.h) on the regimes where its sign tag could be confused: nearly conservative
+    scatterers at the w0 clamp (rest = 1 - alpha - beta computed in fp64 comes out slightly negative, -1e-12 at w0 = 1 - 1e-10,
+    dtau = 7e-8), beta rounded above one, tiny negative alpha or beta, and the identity rows.  Decoded, every value is
+    non-negative, alpha + beta + rest = 1, the smaller of alpha and rest and beta keep fp32's relative precision, and
+    alpha -- the transmission -- is within 6e-8 of the truth (it was read back as |rest| ~ 1e-12 for alpha ~ 1)"""
+    pairs = [(1.0, 0.0), (0.0, 0.0), (0.0, 1.0), (0.0, 1.0 + 2.2e-16), (1.0 + 2.2e-16, 0.0), (-1e-20, 0.5), (0.5, -1e-20),
+             (0.99999993, 1.0 - 0.99999993 + 1.39e-12), (0.3, 0.7 + 1e-13), (0.5, 0.5)]
+    for w0 in (0.0, 0.5, 0.9, 0.99, 1.0 - 1e-6, 1.0 - 1e-10):
+        for dtau in np.logspace(-16, 2, 181):
+            pairs.append(_slab_plain(w0, dtau))
+    pairs = np.array(pairs, dtype=np.float64)
+    got = _plane_round_trip(tmp_path, pairs)
+    assert got.shape == (len(pairs), 3)
+    a, b = pairs[:, 0], pairs[:, 1]
+    a_t, b_t = np.clip(a, 0.0, None), np.clip(b, 0.0, None)
+    r_t = np.clip((1.0 - a) - b, 0.0, None)
+    al, be, rest = got[:, 0], got[:, 1], got[:, 2]
+    assert np.all(al >= 0.0) and np.all(be >= 0.0) and np.all(rest >= 0.0)
+    assert np.all(np.abs(al + be + rest - 1.0) <= 4e-16)
+    u = 6e-8                                                   # (2^-24: one fp32 rounding, relative)
+    tiny = 2e-38                                               # (below fp32's normal range -- transmissions of 1e-40 -- absolute)
+    assert np.all(np.abs(be - b_t) <= u * np.minimum(b_t, 1.0 - b_t) + 2.3e-16 + tiny)
+    small_is_alpha = a_t <= r_t
+    assert np.all(np.abs(al - a_t)[small_is_alpha] <= u * a_t[small_is_alpha] + tiny)
+    assert np.all(np.abs(rest - r_t)[~small_is_alpha] <= u * r_t[~small_is_alpha] + tiny)
+    # the larger of the two, formed as (1 - beta) - the smaller: within the roundings of the other two
+    assert np.all(np.abs(al - a_t) <= u * (a_t + b_t + r_t) + 4e-16 + tiny), np.max(np.abs(al - a_t))
+    assert np.all(np.abs(rest - r_t) <= u * (np.minimum(a_t, r_t) + np.minimum(b_t, 1.0 - b_t)) + 4e-16 + tiny)
+
+
+def test_struct_sizes_are_unchanged():
+    """coef_fp32 took the place of reserved[0]: the structs' sizes are those the C-ABI has always had"""
+    from helios_amd.rt import RtColumn, RtDims, RtFlags
+    a, b, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    assert _lib.lib().hx_rt_struct_sizes(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)) == 0
+    assert (a.value, b.value, c.value) == (64, 192, 128)
+    assert (ctypes.sizeof(RtDims), ctypes.sizeof(RtFlags), ctypes.sizeof(RtColumn)) == (64, 192, 128)
+    assert RtFlags.coef_fp32.offset == 13 * 4 and RtFlags.reserved.offset == 14 * 4 and RtFlags.epsi.offset == 16 * 4
+
+
+def _tilings():
+    """(rows, k) of every tiling the selection chooses for 1-416 layers and isothermal 1-512, with and without the beam"""
+    lib = _lib.lib()
+    k, r = ctypes.c_int(), ctypes.c_int()
+    seen = set()
+    for iso, top in ((0, 416), (1, 512)):
+        for beam in (0, 1):
+            for L in range(1, top + 1):
+                assert lib.hx_rt_flux_geometry(L, iso, beam, 20, 10000, 1, ctypes.byref(k), ctypes.byref(r)) == 0
+                seen.add((r.value, k.value))
+    return seen
+
+
+def test_every_selectable_tiling_has_fp32_kernels_without_scratch():
+    notes = {k["name"]: k for k in _notes_module().kernel_notes()}
+    f32 = {n: k for n, k in notes.items() if "k_rt_flux_f32<" in n or "k_rt_coef_f32<" in n}
+    assert f32
+    bad = sorted(n for n, k in f32.items() if k["vgpr_spill_count"] or k["private_segment_fixed_size"])
+    assert not bad, bad
+    flux = [n for n in f32 if "k_rt_flux_f32<" in n]
+    coef = [n for n in f32 if "k_rt_coef_f32<" in n]
+    for rows, k in sorted(_tilings()):
+        K = k if k >= 16 else 0
+        assert len([n for n in flux if "k_rt_flux_f32<%d, %d, false>" % (rows, K) in n]) == 1, (rows, K)
+        for tpb in (1, 2, 4, 8):
+            assert len([n for n in coef if "k_rt_coef_f32<%d, %d>" % (rows, tpb) in n]) == 1, (rows, tpb)
+    # the matrix method keeps fp64 planes: no fp32 direct solve
+    assert not [n for n in flux if ", true>" in n]
+    # the fp64 kernels keep their names (tests/test_abi.py finds them by these substrings)
+    assert [n for n in notes if "k_rt_flux<13, 16, false>" in n] and [n for n in notes if "k_rt_coef<7, 8>" in n]
+
+
+def test_no_fp32_flux_kernel_serialises_its_tile_loads():
+    """the limit tests/test_abi.py sets for the fp64 flux kernels of the selectable tilings: at most six global loads into
+    one destination register, and every row of the tile loaded (three to six planes and the state)"""
+    dest = _notes_module().load_destinations(name_filter="k_rt_flux_f32<")
+    assert len(dest) >= 13 * 4 + 1                            # (rows 1-13 on four lane counts, 14 rows on 16)
+    worst = {n: max(c.values()) for n, c in dest.items() if c}
+    assert len(worst) == len(dest)
+    assert max(worst.values()) <= 6, sorted(worst.items(), key=lambda kv: -kv[1])[:5]
+    n = [n for n in dest if "k_rt_flux_f32<13, 16, false>" in n][0]
+    assert sum(dest[n].values()) >= 7 * 13
+
+
+def test_the_per_stage_path_says_once_that_it_computes_in_double(capsys):
+    from helios_amd.computation import Compute
+
+    class S(object):
+        prec = "single"
+    comp = Compute.__new__(Compute)           # (no device needed for the message)
+    comp._tell_stagewise_is_double(S())
+    comp._tell_stagewise_is_double(S())
+    out = capsys.readouterr().out
+    assert out.count("no fp32 coefficient planes") == 1 and "double precision" in out
+    S.prec = "double"
+    comp2 = Compute.__new__(Compute)
+    comp2._tell_stagewise_is_double(S())
+    assert capsys.readouterr().out == ""
