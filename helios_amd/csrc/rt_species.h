@@ -17,7 +17,6 @@
 // Columns whose loop has ended (done[c]) are skipped on the device: no host round trip inside a refresh.
 #pragma once
 #include "random_overlap.h"
-#include "random_overlap_lean.h"
 #include "two_stream.h"
 
 namespace hx {
@@ -132,21 +131,9 @@ __global__ void k_rt_mmm_from_vmr(const SpeciesDev* __restrict__ sp, int S, doub
 constexpr int MIX_MAX_ABSORBERS = 48;  // LDS images of the species list: 1 KB next to the mixing images; a longer list takes
                                        // one launch per block of 48 (MixArgs::carry_on)
 
-// HX_MIX_LEAN = 1 (default): rol::mix (random_overlap_lean.h) -- 7.9 KB of LDS and at most 96 VGPRs, five wavefronts per SIMD;
-// 0: ro::mix as until round 5 (10.2 KB, 128 VGPRs, four), kept for the same-box A/B (tools/ab_mix_lean.sh)
-#ifndef HX_MIX_LEAN
-#define HX_MIX_LEAN 1
-#endif
-#if HX_MIX_LEAN
-namespace mixro = rol;
-#define HX_MIX_WAVES_PER_EU 5
-#else
-namespace mixro = ro;
-#define HX_MIX_WAVES_PER_EU 4
-#endif
-
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HX_MIX_WAVES_PER_EU))) k_rt_mix_species(MixArgs a) {
-    __shared__ mixro::Shared sh;
+// ro::mix keeps this kernel within 7.9 KB of LDS and 96 VGPRs: five wavefronts per SIMD (tests/test_abi.py)
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) k_rt_mix_species(MixArgs a) {
+    __shared__ ro::Shared sh;
     // what the species loop needs per absorber, staged once per wavefront: table base, correlated-k flag, and -- per
     // level -- the factor vmr * mass / mu.  (Read straight from the argument block these were chains of dependent
     // global loads inside the loop: the scalar registers are all taken, so the compiler fetched them through the
@@ -159,12 +146,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HX_MIX_
     // 16 bytes per lane and point written and read back (2.1 GB of the 2.5 GB WRITE_SIZE of round 2's launch)
     __shared__ double s_blend[4];
     const int lane = threadIdx.x;
-#if HX_MIX_LEAN
-    const rol::LaneConst ln = rol::init(sh, lane, a.gauss_w, a.gauss_y);
-#else
-    ro::Lane ln;
-    ro::init(sh, ln, lane, a.gauss_w, a.gauss_y);
-#endif
+    const ro::LaneConst ln = ro::init(sh, lane, a.gauss_w, a.gauss_y);
     const int nabs = a.nabs;
     if (lane < nabs) {
         const int s = a.abs_list[lane];
@@ -256,7 +238,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HX_MIX_
                 const double raw = ro::shfl((ro::NY * j + y) << 2, raw_mine);  // lanes 0..19: from group j
                 const double add = s_fac[kb + j] * raw;
                 if ((s_info[kb + j] & 1) == 0) mixv += add;
-                else mixv = mixro::mix(sh, ln, lane, mixv, add, cnt);
+                else mixv = ro::mix(sh, ln, lane, mixv, add, cnt);
             }
         }
         if (lane < a.Y) out_level[off] = mixv;

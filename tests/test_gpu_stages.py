@@ -206,12 +206,10 @@ def _ro_run(impl):
     return res
 
 
-def test_random_overlap_orderings_vs_oracle(hip, port, tmp_path):
-    """the quantised-key network with exact finish (default: the lean kernel of round 6, whose keys carry their cell) against
-    the oracle's adjacent-swap sort, incl. problems full of equal sums, and against the three other device variants -- the
-    kernel of rounds 2-5 (HELIOS_RO_SORT=q32: fill positions as tie-break, sums and weights through LDS images), the fp64
-    bitonic network (HELIOS_RO_SORT=bitonic) and the all-pairs ranking (HELIOS_RO_SORT=rank); the knob is read once per
-    process -> child processes.  All four must agree bit for bit."""
+def test_random_overlap_vs_oracle_and_ranking(hip, port, tmp_path):
+    """the product kernel (quantised keys that carry their cell, bitonic network, exact finish) against the oracle's
+    adjacent-swap sort, incl. problems full of equal sums, and bit for bit against the all-pairs ranking
+    (HELIOS_RO_SORT=rank); the knob is read once per process -> a child process."""
     import os
     import subprocess
     import sys
@@ -225,7 +223,7 @@ def test_random_overlap_orderings_vs_oracle(hip, port, tmp_path):
         # decades apart multiply that by K[w] / K[w-1]
         np.testing.assert_allclose(got[k], want[k], rtol=2e-11 if k == "wide" else 5e-12, err_msg=k)
     here = os.path.dirname(os.path.abspath(__file__))
-    for kind in ("q32", "rank", "bitonic"):
+    for kind in ("rank",):
         out = tmp_path / (kind + ".npz")
         code = ("import sys, numpy as np; sys.path.insert(0, %r); import test_gpu_stages as t; from impls import hip_impl; "
                 "np.savez(%r, **t._ro_run(hip_impl()))" % (here, str(out)))
@@ -234,6 +232,23 @@ def test_random_overlap_orderings_vs_oracle(hip, port, tmp_path):
         z = np.load(out)
         for k in want:
             np.testing.assert_array_equal(got[k], z[k], err_msg="%s vs %s" % (k, kind))
+
+
+def test_random_overlap_refuses_retired_kernels(tmp_path):
+    """HELIOS_RO_SORT names a kernel this library no longer builds (q32): the call fails with the value in the message
+    instead of running the product kernel (child process: the knob is read once per process)"""
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = ("import sys, numpy as np; sys.path.insert(0, %r); import test_gpu_stages as t; from impls import hip_impl; "
+            "from helios_amd._lib import HeliosHipError\n"
+            "try:\n    t._ro_run(hip_impl())\nexcept HeliosHipError as e:\n    print('refused:', e)\n" % here)
+    env = dict(os.environ, HELIOS_RO_SORT="q32")
+    r = subprocess.run([sys.executable, "-c", code], env=env, cwd=os.path.dirname(here), capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, r.stderr
+    assert "refused:" in r.stdout and "q32" in r.stdout, r.stdout
 
 
 def test_random_overlap_every_crossing_index_vs_oracle(hip, port):

@@ -52,7 +52,7 @@ python3 bench.py --workload c2beam --steps 50 --warmup 10 --no-cpu-baseline --se
 python3 bench.py --phase convection --workload c5 --steps 20 --warmup 10 --no-cpu-baseline --secondary none --live-counters off --full-line > $O/c5_bench_convection_loop.json 2>> $O/bench.err
 # eight ranks on the one GPU of this box through the gloo hook: the multi-rank path incl. the config-4 share as `secondary`
 HELIOS_BENCH_BACKEND=gloo python3 bench.py --gpus 8 --workload c2small --steps 20 --warmup 10 --secondary c4small --no-cpu-baseline --detail $O/bench_8ranks_one_gpu_gloo_detail.json > $O/bench_8ranks_one_gpu_gloo.json 2>> $O/bench.err
-for K in generic ktable dominated; do for S in lean q32 bitonic rank; do HELIOS_RO_SORT=$S python3 tools/ro_bench.py --kind $K --reps 3; done; done > $O/ro_bench.txt 2>&1
+for K in generic ktable dominated; do for S in lean rank; do HELIOS_RO_SORT=$S python3 tools/ro_bench.py --kind $K --reps 3; done; done > $O/ro_bench.txt 2>&1
 # shader counters of the mixing kernel: in the species loop of config 3 and on problems that all take the network
 bash tools/pmc_sq.sh $TAG c3 > /dev/null 2>&1
 bash tools/pmc_cmd.sh ${TAG}_ro python3 tools/ro_bench.py --kind ktable > /dev/null 2>&1

@@ -4,7 +4,7 @@
     python tools/ro_bench.py [--nbin 10000] [--nlev 101] [--kind generic|dominated|interleaved] [--reps 5]
 
 Prints the HIP-event time per launch, problems/s and the exact-finish pass count (hx_diag.ro_fixup_passes).
-HELIOS_RO_SORT=q32|bitonic|rank selects the older kernels for A/B runs on the same box."""
+HELIOS_RO_SORT=lean|rank selects the product kernel (default) or the all-pairs ranking for A/B runs on the same box."""
 import argparse
 import ctypes
 import os
