@@ -432,13 +432,18 @@ class Compute(object):
             print("\nhelios_amd: precision = single -- the per-stage kernels have no fp32 coefficient planes; this run "
                   "computes in double precision.")
 
+    # The flux tiling depends on the half-layers alone (layers, or twice the layers), and the selection finds one of at most
+    # 13 rows on 64 lanes -- which all have fp32 planes (rt_fused_f32.hip, coef_fp32_tiling) -- while there are at most
+    # 13 x 64 of them: 416 layers, 832 isothermal
+    FP32_PLANES_MAX_HALF_LAYERS = 13 * 64
+
     @staticmethod
     def _why_fp64_planes(q):
         """why a batch asked for fp32 coefficient planes got fp64 ones (hx_rt_create: the matrix method keeps fp64 planes;
-        fp32 variants exist for the sweeps' tilings without scratch, columns of up to 416 layers, 512 isothermal)"""
+        fp32 variants exist for the sweeps' tilings without scratch, columns of up to 416 layers, 832 isothermal)"""
         if q.flux_calc_method == "matrix":
             return "the matrix method's direct solve keeps fp64 coefficient planes"
-        if _i(q.nlayer) > (512 if q.iso == 1 else 416):
+        if _i(q.nlayer) * (1 if q.iso == 1 else 2) > Compute.FP32_PLANES_MAX_HALF_LAYERS:
             return "%d layers have no fp32 coefficient planes in the device-resident loop" % _i(q.nlayer)
         return "this batch's tiling (set by the HELIOS_RT_K / HELIOS_RT_GENERIC_SCANS tuning knobs) has no fp32 variant"
 

@@ -73,8 +73,9 @@ bool choose_geometry(int H, int Y, int X, int C, int dir_beam, int scat_corr, Ti
     // Instantiations that keep part of their register image in scratch are not chosen while another lane count avoids
     // it: k_rt_flux<15, *> spills 15-22 VGPRs, <16, *> 32-37, <14, K != 16> 2-3 (tools/code_object_notes.py;
     // tests/test_abi.py reads the same notes), and scratch round trips inside the Gauss-group loop cost this kernel a
-    // quarter of its time in round 2.  Every column of up to 416 layers has a spill-free tiling
-    // (k = 64, 13 rows); beyond that only k = 64 with 14-16 rows exists.  Measured: profiles/r03_geometry_ab.txt.
+    // quarter of its time in round 2.  Every column of up to 416 layers (832 isothermal ones: the
+    // choice depends only on H) has a spill-free tiling (k = 64, 13 rows); beyond that only k = 64 with 14-16 rows exists.
+    // Measured: profiles/r03_geometry_ab.txt.
     int best_k = 0, best_rows = 0, best_cost = 1 << 30;
     int force_k = 0;
     if (const char* e = getenv("HELIOS_RT_K")) force_k = atoi(e);  // tuning knob
@@ -494,6 +495,9 @@ static int rt_create_into(hx_rt* rt, hx_context* ctx, const hx_rt_dims* dims, co
     // at k = 16, 8 at k = 32 (config 5, same box: 2 tiles 6.4 ms, 4 tiles 4.5 ms, 8 tiles 3.4 ms per refresh)
     rt->coef_tpb = std::max(1, std::min(8, 16 / std::max(1, rt->g.S)));    // (16 tiles per workgroup at k = 64: measured, no faster)
     if (const char* e = getenv("HELIOS_RT_COEF_TPB")) rt->coef_tpb = atoi(e);   // tuning knobs
+    // launch_coef has kernels of 1, 2, 4 and 8 tiles (8 up to 16 rows) and runs any other value as 4: the LDS limits below
+    // and "flux_tiling" are those of the kernel that runs
+    if (rt->coef_tpb != 1 && rt->coef_tpb != 2 && !(rt->coef_tpb == 8 && rt->g.ROWS <= 16)) rt->coef_tpb = 4;
     while (rt->coef_tpb > 1 && coef_shmem_bytes(rt, rt->coef_tpb) > 150 * 1024) rt->coef_tpb /= 2;   // (deep columns: the staged layers of fewer tiles)
     if (coef_shmem_bytes(rt, rt->coef_tpb) > 160 * 1024)
         return hx_fail(ctx, HX_E_UNSUPPORTED, "k_rt_coef's staging of one tile exceeds the 160 KiB of LDS");
@@ -1679,7 +1683,21 @@ int hx_rt_get(hx_rt* rt, int col, const char* name, void* out, size_t out_bytes)
         memcpy(out, &v, sizeof(v));
         return 0;
     }
+    if (strcmp(name, "flux_tiling") == 0) {   // host-side, any column (-1): the tiling and kernels this batch runs
+        const TileGeom& g = rt->g;
+        const int32_t v[14] = {g.k, g.ROWS, g.threads, g.nparts, g.nxb, g.ypb, g.NW, g.nplane, g.has_vp, g.pl_vp, g.pl_dd,
+                               rt->coef_tpb, rt->coef_bytes, rt->generic_scans ? 1 : 0};
+        HX_REQUIRE(rt->ctx, out_bytes == sizeof(v), HX_E_ARG, "flux_tiling is 14 int32");
+        memcpy(out, v, sizeof(v));
+        return 0;
+    }
     HX_REQUIRE(rt->ctx, col >= 0 && col < rt->C, HX_E_ARG, "column index out of range");
+    if (strcmp(name, "coef_planes") == 0) {   // the column's coefficient planes as k_rt_coef wrote them (after a refresh)
+        const void* planes = rt->coef32 ? (const void*)rt->coef32 : (const void*)rt->coef;
+        HX_REQUIRE(rt->ctx, planes, HX_E_ARG, "this batch has no coefficient planes (per-stage matrix solver)");
+        const size_t bytes = rt->g.coef_elems_per_col * rt->coef_bytes;
+        return get_plain(rt, (const char*)planes + (size_t)col * bytes, bytes, out, out_bytes);
+    }
     if (strncmp(name, "opac_wg_", 8) == 0) {
         int rc = materialize_opac(rt);
         if (rc) return rc;

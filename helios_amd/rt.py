@@ -263,6 +263,28 @@ class RTBatch(object):
                  "hx_rt_get(coef_plane_bytes)")
         return int(out[0])
 
+    _TILING = ("k", "ROWS", "threads", "nparts", "nxb", "ypb", "NW", "nplane", "has_vp", "pl_vp", "pl_dd", "coef_tpb",
+               "coef_bytes", "generic_scans")
+
+    def flux_tiling(self):
+        """the batch's tiling and the coefficient kernel it runs (include/helios_hip.h, hx_rt_flags.coef_fp32)"""
+        out = np.zeros(len(self._TILING), np.int32)
+        self._ck(self._l.hx_rt_get(self.handle, -1, b"flux_tiling", out.ctypes.data_as(ctypes.c_void_p), out.nbytes),
+                 "hx_rt_get(flux_tiling)")
+        return dict(zip(self._TILING, (int(v) for v in out)))
+
+    def coef_planes(self, col=0):
+        """column `col`'s coefficient planes as the coefficient kernel wrote them at the last refresh, shaped
+        (tiles, planes, ROWS, 64 lanes): float64, or float32 in plane_code.h's coding"""
+        t = self.flux_tiling()
+        dt = np.float32 if t["coef_bytes"] == 4 else np.float64
+        per_tile = t["nplane"] * t["ROWS"] * 64
+        ntiles = -(-self.nbin // t["nxb"]) * t["nparts"] * t["NW"]
+        out = np.zeros(ntiles * per_tile, dt)
+        self._ck(self._l.hx_rt_get(self.handle, int(col), b"coef_planes", out.ctypes.data_as(ctypes.c_void_p), out.nbytes),
+                 "hx_rt_get(coef_planes)")
+        return out.reshape(ntiles, t["nplane"], t["ROWS"], 64)
+
     def close(self):
         if self.handle:
             self._l.hx_rt_destroy(self.handle)

@@ -343,8 +343,16 @@ typedef struct hx_rt_flags {
     int32_t coef_fp32;            /* 1 = `precision = single`: the coefficient planes (alpha, beta, u', v', dd, du) are stored
                                      in fp32 -- rounded once when written, widened to fp64 when read; all arithmetic and every
                                      other array stay fp64.  The matrix method and tilings without an fp32 variant (columns of
-                                     more than 416 layers, 512 isothermal) keep fp64 planes; hx_rt_get(rt, -1,
-                                     "coef_plane_bytes", &int32, 4) says which width is in use (4 or 8) */
+                                     more than 416 layers, 832 isothermal) keep fp64 planes; hx_rt_get(rt, -1,
+                                     "coef_plane_bytes", &int32, 4) says which width is in use (4 or 8).
+                                     hx_rt_get(rt, -1, "flux_tiling", int32[14], 56) reads the batch's tiling: {k, ROWS,
+                                     threads, nparts, nxb, ypb, NW, nplane, has_vp, pl_vp, pl_dd, coef_tpb, coef_bytes,
+                                     generic_scans} -- coef_tpb the tiles per workgroup of the coefficient kernel that runs
+                                     (after HELIOS_RT_COEF_TPB and the LDS limits), coef_bytes 4 or 8 as above.
+                                     hx_rt_get(rt, col, "coef_planes", buf, nbytes) copies column col's coefficient planes
+                                     as the coefficient kernel wrote them at the last refresh: coef_bytes-wide elements
+                                     laid out [tile][plane][row][lane] (64 lanes, ROWS rows, nplane planes); fp32 planes
+                                     in their stored coding (csrc/plane_code.h) */
     int32_t reserved[2];
     double epsi, epsi2, g_0, i2s_transition, w_0_limit, w_0_scat_limit, delta_tau_limit;
     double reserved_d[9];

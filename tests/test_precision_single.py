@@ -94,6 +94,40 @@ def test_the_driver_names_the_reason_for_fp64_planes(monkeypatch):
     assert "matrix method" in why and "layers" not in why
     Q.iso, Q.nlayer, Q.flux_calc_method = 1, 500, "iteration"
     assert "layers" not in Compute._why_fp64_planes(Q())     # (isothermal: 512 layers have an fp32 tiling)
+    # isothermal columns are tiled by their layers, the others by their half-layers: fp32 planes up to 832 isothermal layers
+    Q.nlayer = 832
+    assert "layers" not in Compute._why_fp64_planes(Q())
+    Q.nlayer = 833
+    assert "833 layers" in Compute._why_fp64_planes(Q())
+    Q.iso, Q.nlayer = 0, 416
+    assert "layers" not in Compute._why_fp64_planes(Q())
+    Q.nlayer = 417
+    assert "417 layers" in Compute._why_fp64_planes(Q())
+
+
+def _has_fp32_tiling(rows, k, generic_scans=False):
+    """rt_fused_f32.hip's coef_fp32_tiling"""
+    return rows <= 13 or (rows == 14 and k == 16 and not generic_scans)
+
+
+def test_the_driver_limit_is_that_of_the_selected_tilings(monkeypatch):
+    """the driver's limit against the library's own choice of tiling (hx_rt_flux_geometry) at every layer count of the
+    device-resident loop, isothermal or not: a layer count gets the layer reason exactly where its tiling has no fp32
+    kernels"""
+    from helios_amd.computation import Compute
+    for knob in ("HELIOS_RT_K", "HELIOS_RT_GENERIC_SCANS"):
+        monkeypatch.delenv(knob, raising=False)
+    lib = _lib.lib()
+    k, r = ctypes.c_int(), ctypes.c_int()
+
+    class Q(object):
+        flux_calc_method = "iteration"
+    for iso, top in ((0, 1024), (1, 2048)):
+        Q.iso = iso
+        for L in range(1, top + 1):
+            assert lib.hx_rt_flux_geometry(L, iso, 1, 20, 300, 1, ctypes.byref(k), ctypes.byref(r)) == 0
+            Q.nlayer = L
+            assert _has_fp32_tiling(r.value, k.value) == ("layers" not in Compute._why_fp64_planes(Q())), (iso, L)
 
 
 _DRIVER = r"""
@@ -139,18 +173,23 @@ def _slab_plain(w0, dtau, epsi=0.5):
     return P / M, -N / M
 
 
+def _regime_pairs():
+    """(alpha, beta) across the regimes where plane_code.h's sign tag could be confused"""
+    pairs = [(1.0, 0.0), (0.0, 0.0), (0.0, 1.0), (0.0, 1.0 + 2.2e-16), (1.0 + 2.2e-16, 0.0), (-1e-20, 0.5), (0.5, -1e-20),
+             (0.99999993, 1.0 - 0.99999993 + 1.39e-12), (0.3, 0.7 + 1e-13), (0.5, 0.5)]
+    for w0 in (0.0, 0.5, 0.9, 0.99, 1.0 - 1e-6, 1.0 - 1e-10):
+        for dtau in np.logspace(-16, 2, 181):
+            pairs.append(_slab_plain(w0, dtau))
+    return pairs
+
+
 def test_plane_coding_keeps_alpha_beta_and_rest(tmp_path):
     """the fp32 planes' coding (csrc/plane_code.h) on the regimes where its sign tag could be confused: nearly conservative
     scatterers at the w0 clamp (rest = 1 - alpha - beta computed in fp64 comes out slightly negative, -1e-12 at w0 = 1 - 1e-10,
     dtau = 7e-8), beta rounded above one, tiny negative alpha or beta, and the identity rows.  Decoded, every value is
     non-negative, alpha + beta + rest = 1, the smaller of alpha and rest and beta keep fp32's relative precision, and
     alpha -- the transmission -- is within 6e-8 of the truth (it was read back as |rest| ~ 1e-12 for alpha ~ 1)"""
-    pairs = [(1.0, 0.0), (0.0, 0.0), (0.0, 1.0), (0.0, 1.0 + 2.2e-16), (1.0 + 2.2e-16, 0.0), (-1e-20, 0.5), (0.5, -1e-20),
-             (0.99999993, 1.0 - 0.99999993 + 1.39e-12), (0.3, 0.7 + 1e-13), (0.5, 0.5)]
-    for w0 in (0.0, 0.5, 0.9, 0.99, 1.0 - 1e-6, 1.0 - 1e-10):
-        for dtau in np.logspace(-16, 2, 181):
-            pairs.append(_slab_plain(w0, dtau))
-    pairs = np.array(pairs, dtype=np.float64)
+    pairs = np.array(_regime_pairs(), dtype=np.float64)
     got = _plane_round_trip(tmp_path, pairs)
     assert got.shape == (len(pairs), 3)
     a, b = pairs[:, 0], pairs[:, 1]
@@ -170,6 +209,99 @@ def test_plane_coding_keeps_alpha_beta_and_rest(tmp_path):
     assert np.all(np.abs(rest - r_t) <= u * (np.minimum(a_t, r_t) + np.minimum(b_t, 1.0 - b_t)) + 4e-16 + tiny)
 
 
+_BITS_DRIVER = r"""
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include "plane_code.h"
+int main() {
+    unsigned long long ua, ub;
+    while (std::scanf("%llx %llx", &ua, &ub) == 2) {
+        double a, b;
+        std::memcpy(&a, &ua, 8);
+        std::memcpy(&b, &ub, 8);
+        const float c0 = hx::plane0_code(a, b), c1 = hx::plane1_code(b);
+        uint32_t u0, u1;
+        std::memcpy(&u0, &c0, 4);
+        std::memcpy(&u1, &c1, 4);
+        std::printf("%08x %08x\n", u0, u1);
+    }
+    return 0;
+}
+"""
+
+
+def test_the_numpy_twin_codes_the_planes_bit_for_bit_like_the_header(tmp_path):
+    """tests/plane_coding.py -- the coding the GPU tests hold the fp32 coefficient kernel to -- against plane0_code and
+    plane1_code of csrc/plane_code.h compiled for the host, as bit patterns: the sign of zero is the tag (-0.0 is rest = 0,
+    alpha = 1), which a comparison of values does not see.  The regimes of the round-trip test above, and the edges of the
+    coding: ties of alpha and rest, beta at one half, -0.0, NaN, negative values and fp32's subnormal range"""
+    import shutil
+    import subprocess
+    from plane_coding import code_alpha_beta
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    pairs = list(_regime_pairs())
+    pairs += [(0.25, 0.5), (0.5, 0.0), (0.4, 0.2), (1.0, 0.5), (0.5, 0.5 + 2 ** -53), (0.5 - 2 ** -54, 0.5),
+              (-0.0, 0.0), (0.0, -0.0), (1.0, -0.0), (-0.0, 1.0), (float("nan"), 0.25), (0.25, float("nan")),
+              (float("nan"), float("nan")), (-3.0, 0.5), (2.0, 0.25), (0.25, 2.0), (0.25, -2.0), (1e-40, 0.0), (1e-45, 0.5),
+              (1.0 - 1e-40, 0.0), (0.5, 1e-40), (7e-46, 0.25), (1e-320, 0.0), (3.4e38, 0.0), (1e39, -1e39), (0.0, 0.5 + 1e-40)]
+    rng = np.random.default_rng(7)
+    pairs += [tuple(p) for p in rng.uniform(-0.1, 1.1, (2000, 2))]
+    pairs += [(float(a), float(1.0 - a) * f) for a, f in zip(rng.uniform(0, 1, 2000), rng.choice([1.0, 1 - 1e-9, 1 + 1e-9], 2000))]
+    pairs = np.array(pairs, dtype=np.float64)
+    src, exe = tmp_path / "bits.cpp", tmp_path / "bits"
+    src.write_text(_BITS_DRIVER)
+    subprocess.run([cxx, "-std=c++17", "-O2", "-ffp-contract=off", "-I", os.path.join(ROOT, "helios_amd", "csrc"), str(src),
+                    "-o", str(exe)], check=True, capture_output=True)
+    text = "\n".join("%016x %016x" % (a, b) for a, b in pairs.view(np.uint64)) + "\n"
+    out = subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout
+    want = np.array([[int(v, 16) for v in ln.split()] for ln in out.strip().split("\n")], dtype=np.uint32)
+    assert want.shape == (len(pairs), 2)
+    c0, c1 = code_alpha_beta(pairs[:, 0], pairs[:, 1])
+    for i, (got, name) in enumerate(((c0, "plane 0"), (c1, "plane 1"))):
+        bad = np.nonzero(got.view(np.uint32) != want[:, i])[0]
+        assert bad.size == 0, (name, [(pairs[j].tolist(), "%08x" % got.view(np.uint32)[j], "%08x" % want[j, i])
+                                      for j in bad[:5]])
+    # (the tag is really exercised: both signs of zero and of non-zero codes occur)
+    bits0 = c0.view(np.uint32)
+    assert np.any(bits0 == 0x80000000) and np.any(bits0 == 0) and np.any(c0 < 0) and np.any(c0 > 0)
+    assert np.any(c1 < 0) and np.any(c1 > 0)
+
+
+def test_the_twin_codes_whole_plane_images():
+    """encode_planes on an fp64 image of every layout the coefficient kernel writes (3 to 6 planes): planes 0 and 1 as
+    above, u' and the beam rounded, v' replaced by u' + v' formed in fp64 -- and the padding rows (alpha = 1, beta = 0,
+    u' = v' = 0) coded as rest = -0.0, beta = +0.0, zeros"""
+    from plane_coding import code_alpha_beta, encode_planes
+    rng = np.random.default_rng(3)
+    for has_vp in (0, 1):
+        for beam in (0, 1):
+            nplane = 3 + has_vp + 2 * beam
+            t = dict(has_vp=has_vp, pl_vp=3, pl_dd=3 + has_vp, nplane=nplane, ROWS=5)
+            p = rng.uniform(-1.0, 1.0, (2, nplane, 5, 64))
+            p[:, 0] = rng.uniform(0.0, 1.0, (2, 5, 64))
+            p[:, 1] = (1.0 - p[:, 0]) * rng.uniform(0.0, 1.0, (2, 5, 64))
+            if has_vp:
+                p[:, 3] = -p[:, 2] * (1.0 + 1e-9 * rng.uniform(-1.0, 1.0, (2, 5, 64)))   # (cancels: the sum is not f32(u') + f32(v'))
+            p[:, :, 4] = 0.0
+            p[:, 0, 4] = 1.0                                                      # (a padding row)
+            e = encode_planes(p, t)
+            assert e.dtype == np.float32 and e.shape == p.shape
+            c0, c1 = code_alpha_beta(p[:, 0], p[:, 1])
+            np.testing.assert_array_equal(e[:, 0].view(np.uint32), c0.view(np.uint32))
+            np.testing.assert_array_equal(e[:, 1].view(np.uint32), c1.view(np.uint32))
+            np.testing.assert_array_equal(e[:, 2], p[:, 2].astype(np.float32))
+            if has_vp:
+                np.testing.assert_array_equal(e[:, 3], (p[:, 2] + p[:, 3]).astype(np.float32))
+                assert np.any(e[:, 3] != p[:, 2].astype(np.float32) + p[:, 3].astype(np.float32))
+            if beam:
+                np.testing.assert_array_equal(e[:, 3 + has_vp:], p[:, 3 + has_vp:].astype(np.float32))
+            pad = e[:, :, 4].view(np.uint32)
+            assert np.all(pad[:, 0] == 0x80000000) and np.all(pad[:, 1:] == 0)
+
+
 def test_struct_sizes_are_unchanged():
     """coef_fp32 took the place of reserved[0]: the structs' sizes are those the C-ABI has always had"""
     from helios_amd.rt import RtColumn, RtDims, RtFlags
@@ -181,11 +313,11 @@ def test_struct_sizes_are_unchanged():
 
 
 def _tilings():
-    """(rows, k) of every tiling the selection chooses for 1-416 layers and isothermal 1-512, with and without the beam"""
+    """(rows, k) of every tiling the selection chooses for 1-416 layers and isothermal 1-832, with and without the beam"""
     lib = _lib.lib()
     k, r = ctypes.c_int(), ctypes.c_int()
     seen = set()
-    for iso, top in ((0, 416), (1, 512)):
+    for iso, top in ((0, 416), (1, 832)):
         for beam in (0, 1):
             for L in range(1, top + 1):
                 assert lib.hx_rt_flux_geometry(L, iso, beam, 20, 10000, 1, ctypes.byref(k), ctypes.byref(r)) == 0
