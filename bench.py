@@ -3,7 +3,7 @@
 (single column per GPU, 10 000 bins x 100 layers x 20 Gauss points, premixed corr-k table,
 isotropic scattering, fp64), synthetic tables per SURVEY.md section 8(d).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the radiation_loop body (reference source/computation.py:851-984): interface
@@ -16,12 +16,16 @@ scaling, no collective on the iteration path, the emission spectra gathered over
 the N = 1 member of a 1/2/4/8 series IS the single-GPU headline.  `python bench.py --gpus N` without a launcher starts
 the N ranks itself (a child `python -m torch.distributed.run ...`, before this process touches a GPU).
 
-The same run also measures, live, into `secondary`: at N = 1 config 3 (20 species mixed on the fly), config 4 (one GPU's
-share of the 512-column sweep: 64 on-the-fly columns in one batch -- the same shape at every N) and config 5 (30 000 x 200,
-20 species on the fly, two cloud decks, beam, albedo, I2S); at N > 1 config 4 alone (`--secondary all` adds config 5 from
-the convection loop and the default-grid batches).  Synthetic k-tables are formed on the device from their two factors
-(hx_rt_set_*_separable): a rank's set-up (`setup_s`) does not depend on the host's core count.  `steady_state_200` is the
-headline workload over 200 iterations from iteration 0 (20 refreshes), SURVEY.md 8(d)'s definition of the metric.
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes --dump-outputs and
+prints the line (`roofline`, `cpu_baseline`, `steady_state_200` and `secondary` are null).  With --full the same run also
+measures, live, into `secondary`: at N = 1 config 3 (20 species mixed on the fly), config 4 (one GPU's share of the
+512-column sweep: 64 on-the-fly columns in one batch -- the same shape at every N) and config 5 (30 000 x 200, 20 species on
+the fly, two cloud decks, beam, albedo, I2S); at N > 1 config 4 alone (`--secondary all` adds config 5 from the convection
+loop and the default-grid batches).  It also counts the headline's HBM traffic in profiler children (N = 1), prices its
+dominant kernel against the roofline, runs `steady_state_200` -- the headline workload over 200 iterations from iteration 0
+(20 refreshes), SURVEY.md 8(d)'s definition of the metric -- and times the CPU baseline (N = 1).  Synthetic k-tables are
+formed on the device from their two factors (hx_rt_set_*_separable): a rank's set-up (`setup_s`) does not depend on the
+host's core count.
 
 OUTPUT.  Rank 0 prints ONE compact JSON line (compact_line(): < 4 KB at every N -- the contract's fields, `config`,
 `roofline`, `cpu_baseline`, `steady_state_200`, `process_group`, and per secondary workload value / ms_per_step / roofline
@@ -42,8 +46,9 @@ sys.path.insert(0, ROOT)
 # 1-5 probed the CPU baseline's thread count up to that answer: two threads)
 HOST_CPUS = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
 
-def _cpu_baseline_will_run(argv, env):
-    """only the N = 1 process that times the CPU oracle at the end"""
+def _binds_openmp(argv, env):
+    """the N = 1 process, unless --no-cpu-baseline: with --full it times the CPU oracle at the end; a plain run is bound the
+    same way, so that its headline is timed under the conditions a --full run times it under"""
     if int(env.get("WORLD_SIZE", "1")) != 1 or "--no-cpu-baseline" in argv:
         return False
     for i, a in enumerate(argv):
@@ -56,10 +61,10 @@ def _cpu_baseline_will_run(argv, env):
 
 # the CPU baseline's OpenMP threads stay on the cores they start on, packed onto neighbouring cores (one NUMA domain for the
 # thread counts that win): read by the OpenMP runtime when it is loaded, so set before anything loads it -- and ONLY in the
-# process that runs the baseline: with binding on, the runtime pins the initial thread to place 0, i.e. the N ranks of a
+# N = 1 process (_binds_openmp): with binding on, the runtime pins the initial thread to place 0, i.e. the N ranks of a
 # multi-GPU run (and every rocprofv3 child pass) would issue their launches from one and the same core
 _OMP_SET_HERE = []
-if __name__ == "__main__" and _cpu_baseline_will_run(sys.argv[1:], os.environ):     # (never on import: tests import this module)
+if __name__ == "__main__" and _binds_openmp(sys.argv[1:], os.environ):    # (never on import: tests import this module)
     for _k, _v in (("OMP_PROC_BIND", "close"), ("OMP_PLACES", "cores")):
         if _k not in os.environ:
             os.environ[_k] = _v
@@ -840,7 +845,7 @@ def emit(full, detail_path):
     print(text, flush=True)
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None)
@@ -848,25 +853,33 @@ def main():
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
                     help="headline workload (default c2, the configuration the metric is quoted on, at every N)")
     ap.add_argument("--columns-per-gpu", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the default secondary workloads, the live HBM "
+                         "counters, the roofline passes, steady_state_200 and the CPU baseline.  A plain run sets up, warms "
+                         "up, times the steps, writes --dump-outputs and prints the line.  --secondary, --live-counters and "
+                         "--profile-steps given explicitly hold with or without --full")
     ap.add_argument("--secondary", default="default",
-                    help="'default' (N = 1: c3,c4,c5; N > 1: c4), 'all' (N = 1: c3,c4,c5,c5conv,d64,d64s), 'none', or a "
-                         "comma-separated list of workloads measured in the same run into the line's `secondary` block")
+                    help="'default' (none; with --full N = 1: c3,c4,c5, N > 1: c4), 'all' (N = 1: c3,c4,c5,c5conv,d64,d64s), "
+                         "'none', or a comma-separated list of workloads measured in the same run into the line's `secondary` "
+                         "block")
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
                     help="side file with the full record of the run (the line on stdout is its compact form); '' = none")
     ap.add_argument("--full-line", action="store_true",
                     help="print the full record instead of the compact line (the A/B scripts under tools/ read per-kernel "
                          "times from it; never what the driver runs)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=20.0,
-                    help="CPU work the oracle's timed sample is sized for (whole decades of iterations)")
+                    help="--full: CPU work the oracle's timed sample is sized for (whole decades of iterations)")
     ap.add_argument("--init-timeout", type=float, default=180.0,
                     help="N > 1: seconds the process group's set-up, roll call and first collective may take each")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--profile-steps", type=int, default=20)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--profile-steps", type=int, default=None,
+                    help="iterations of the roofline passes behind each timed region (default 0; with --full 20)")
     ap.add_argument("--allow-debug-knobs", action="store_true")
-    ap.add_argument("--live-counters", default="headline", choices=["off", "headline", "all"],
+    ap.add_argument("--live-counters", default=None, choices=["off", "headline", "all"],
                     help="N = 1 only: measure the HBM traffic (and, for mixing workloads, the vector instructions) per launch "
                          "in this run -- child passes of this command under rocprofv3 --pmc -- for the headline workload, or "
-                         "for every workload of the line ('all': about a minute more per species workload)")
+                         "for every workload of the line ('all': about a minute more per species workload).  Default 'off'; "
+                         "with --full 'headline'")
     ap.add_argument("--device-warmup-ms", type=float, default=25.0,
                     help="untimed decades of iterations are added to the warm-up until the device has been busy this long "
                          "(0: exactly --warmup iterations, so that two runs do the same iterations)")
@@ -877,7 +890,35 @@ def main():
                     help="write what the headline workload's last timed step computed to DIR/<name>.npy (float64, at most "
                          "64 MB in all; a fixed sample of larger outputs).  The device warm-up is then a fixed number of "
                          "iterations, so that runs with the same arguments can be compared output for output")
-    args = ap.parse_args()
+    return ap
+
+
+def extras(args, world):
+    """what a run measures besides the headline's set-up, warm-up and timed steps: nothing in a plain run; with --full the
+    default secondary workloads, the live HBM counters, the roofline passes, steady_state_200 and the CPU baseline (N = 1).
+    --secondary, --live-counters and --profile-steps given explicitly hold either way."""
+    wname = args.workload or "c2"
+    if args.secondary == "default" and not args.full:
+        secondary = []
+    elif args.secondary in ("default", "all"):
+        # (config 4 with the SAME shape at every N: one GPU's share of the 512-column sweep, 64 columns in one batch)
+        # ('all' adds the regime HELIOS users run: the reference's default grid as a 64-column batch, premixed and with
+        # species.dat's list, and config 5's steps taken from the convection loop)
+        n1 = ["c3", "c4", "c5"] + (["c5conv", "d64", "d64s"] if args.secondary == "all" else [])
+        secondary = (n1 if world == 1 else ["c4"]) if wname == "c2" and args.phase == "radiative" else []
+    else:
+        secondary = [x for x in args.secondary.split(",") if x and x != "none"]
+    for x in secondary:
+        if x not in WORKLOADS:
+            raise SystemExit("unknown secondary workload %r" % x)
+    return dict(secondary=secondary,
+                live_counters=args.live_counters or ("headline" if args.full else "off"),
+                profile_steps=args.profile_steps if args.profile_steps is not None else (20 if args.full else 0),
+                steady_state=args.full, cpu_baseline=args.full and world == 1 and not args.no_cpu_baseline)
+
+
+def main():
+    args = arg_parser().parse_args()
     knobs = env_knobs(args.allow_debug_knobs)
 
     if args.dump_outputs is not None:
@@ -897,26 +938,17 @@ def main():
     if steps < 1 or warmup < 0:
         raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     ncol = args.columns_per_gpu or w.get("columns_per_gpu", 1)
-    if args.secondary in ("default", "all"):
-        # (config 4 with the SAME shape at every N: one GPU's share of the 512-column sweep, 64 columns in one batch)
-        # ('all' adds the regime HELIOS users run: the reference's default grid as a 64-column batch, premixed and with
-        # species.dat's list, and config 5's steps taken from the convection loop)
-        n1 = ["c3", "c4", "c5"] + (["c5conv", "d64", "d64s"] if args.secondary == "all" else [])
-        secondary = (n1 if world == 1 else ["c4"]) if wname == "c2" and args.phase == "radiative" else []
-    else:
-        secondary = [x for x in args.secondary.split(",") if x and x != "none"]
-    for x in secondary:
-        if x not in WORKLOADS:
-            raise SystemExit("unknown secondary workload %r" % x)
+    ex = extras(args, world)
+    secondary = ex["secondary"]
 
-    if world == 1 and args.live_counters != "off" and under_a_profiler(os.environ):
+    if world == 1 and ex["live_counters"] != "off" and under_a_profiler(os.environ):
         # `rocprofv3 ... -- python3 bench.py`: no profiler children inside a profiled run (they would inherit its preloaded tool
         # library and counter configuration); the committed per-launch figures are quoted instead (`traffic_live`: false)
         sys.stderr.write("bench.py: running under a profiler -- HBM traffic is quoted from profiles/traffic.json, not counted in this run\n")
-        args.live_counters = "off"
-    if world == 1 and args.live_counters != "off":
+        ex["live_counters"] = "off"
+    if world == 1 and ex["live_counters"] != "off":
         # before this process touches the GPU: the profiler's children have the device to themselves
-        for x in [wname] + (secondary if args.live_counters == "all" else []):
+        for x in [wname] + (secondary if ex["live_counters"] == "all" else []):
             species = bool(WORKLOADS[x].get("nspecies"))
             got = live_counters(x, ("FETCH_SIZE", "WRITE_SIZE") + (("SQ_INSTS_VALU",) if species else ()),
                                 ncol if x == wname else WORKLOADS[x].get("columns_per_gpu", 1))
@@ -944,8 +976,8 @@ def main():
     from helios_amd.device import Context
     seed = 20240 + 2
     ctx = Context(device_index)
-    head = measure(ctx, ranks, wname, ncol, steps, warmup, seed, phase=args.phase, profile_steps=args.profile_steps,
-                   steady_state=True, device_warmup_ms=args.device_warmup_ms, dump_dir=args.dump_outputs)
+    head = measure(ctx, ranks, wname, ncol, steps, warmup, seed, phase=args.phase, profile_steps=ex["profile_steps"],
+                   steady_state=ex["steady_state"], device_warmup_ms=args.device_warmup_ms, dump_dir=args.dump_outputs)
     line = {"metric": "rad-conv iterations/sec x (lambda-bins x layers)", "value": head.pop("value"),
             "unit": head.pop("unit"), "n_gpus": world, "steps": head.pop("steps"), "warmup": head.pop("warmup"),
             "device_warmup_iterations": head.pop("device_warmup_iterations"), "ms_per_step": head.pop("ms_per_step"),
@@ -979,13 +1011,13 @@ def main():
         hx_ = bool(wx.get("nspecies")) and wx["nbin"] >= 5000
         try:
             r = measure(ctx, ranks, x, wx.get("columns_per_gpu", 1), 20 if hx_ else 100, 10, seed,
-                        phase=wx.get("phase", "radiative"), profile_steps=args.profile_steps,
+                        phase=wx.get("phase", "radiative"), profile_steps=ex["profile_steps"],
                         device_warmup_ms=args.device_warmup_ms)
         except Exception as e:   # the headline above is measured and stands; a secondary that could not run says why
             r = {"error": "%s: %s" % (type(e).__name__, e)}   # (measure() lets the ranks agree on a failed set-up first)
         sec[x] = r
     line["secondary"] = sec or None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and ex["cpu_baseline"]:
         line["cpu_baseline"] = cpu_baseline(w, seed, args.cpu_baseline_seconds)
     elif rank == 0:
         line["cpu_baseline"] = None

@@ -87,6 +87,27 @@ def test_default_secondaries_are_the_three_baseline_configs():
     assert 'n1 = ["c3", "c4", "c5"] + (["c5conv", "d64", "d64s"] if args.secondary == "all" else [])' in src
 
 
+def test_a_plain_run_measures_the_headline_alone():
+    """`bench.py --gpus 1 --steps K --warmup W` times the headline and nothing else; --full adds the secondaries, the live
+    HBM counters, the roofline passes, steady_state_200 and the CPU baseline; options given explicitly hold either way"""
+    import bench
+
+    def ex(argv, world=1):
+        return bench.extras(bench.arg_parser().parse_args(argv), world)
+    plain = ["--gpus", "1", "--steps", "20", "--warmup", "5"]
+    assert ex(plain) == dict(secondary=[], live_counters="off", profile_steps=0, steady_state=False, cpu_baseline=False)
+    assert ex(plain + ["--full"]) == dict(secondary=["c3", "c4", "c5"], live_counters="headline", profile_steps=20,
+                                          steady_state=True, cpu_baseline=True)
+    assert ex(plain + ["--full", "--no-cpu-baseline"])["cpu_baseline"] is False
+    assert ex(["--gpus", "8", "--full"], 8) == dict(secondary=["c4"], live_counters="headline", profile_steps=20,
+                                                    steady_state=True, cpu_baseline=False)
+    assert ex(["--gpus", "8"], 8)["secondary"] == [] and ex(["--workload", "c1", "--full"])["secondary"] == []
+    assert ex(plain + ["--secondary", "c4small", "--profile-steps", "3", "--live-counters", "all"]) == dict(
+        secondary=["c4small"], live_counters="all", profile_steps=3, steady_state=False, cpu_baseline=False)
+    assert ex(plain + ["--full", "--secondary", "none", "--profile-steps", "0", "--live-counters", "off"]) == dict(
+        secondary=[], live_counters="off", profile_steps=0, steady_state=True, cpu_baseline=True)
+
+
 def test_bench_knows_when_it_runs_under_a_profiler():
     """`rocprofv3 ... -- python3 bench.py` must not start profiler children of its own (the live HBM counters): the preloaded
     tool library and the ROCPROF_* variables of the outer run give it away"""

@@ -5,6 +5,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -33,11 +34,36 @@ def _last_json(out, detail=True):
     return full
 
 
-def test_the_drivers_command_prints_one_short_line_last(tmp_path):
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` as the driver runs it (default secondaries, live counters, CPU
-    baseline): what a reader of the last 2 000 characters of stdout sees ends in one line that parses and holds the
-    contract's fields with `roofline` and `cpu_baseline`"""
+def test_the_plain_run_times_the_headline_alone(tmp_path):
+    """`python bench.py --gpus 1 --steps 20 --warmup 5` as the driver runs it: set-up, warm-up, the timed steps and ONE line
+    last, with the contract's fields and nothing the headline does not need (no secondaries, roofline passes, profiler
+    children, steady_state_200 or CPU baseline) -- well within 30 s of wall time outside its steps"""
+    t0 = time.time()
     p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--detail",
+                        str(tmp_path / "detail.json")], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    wall = time.time() - t0
+    assert p.returncode == 0, p.stderr[-2000:]
+    last = p.stdout[-4000:].rstrip().splitlines()[-1]
+    line = json.loads(last)
+    for f in FIELDS:
+        assert f in line, f
+    assert line["metric"] == "rad-conv iterations/sec x (lambda-bins x layers)" and line["unit"] == "bin*layer*iterations/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["n_gpus"] == 1 and line["steps"] == 20 and line["warmup"] == 5 and line["config"]["nbin"] == 10000
+    assert abs(line["value"] - 10000 * 100 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    for f in ("roofline", "cpu_baseline", "steady_state_200", "secondary"):
+        assert line[f] is None, f
+    with open(str(tmp_path / "detail.json")) as f:
+        full = json.load(f)
+    assert full["value"] == line["value"] and full["roofline"] is None and "steady_state_200" not in full
+    assert wall - 25 * line["ms_per_step"] * 1e-3 < 30.0, wall
+
+
+def test_the_drivers_command_prints_one_short_line_last(tmp_path):
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full`, the driver's command with everything else the benchmark
+    measures (default secondaries, live counters, CPU baseline): what a reader of the last 2 000 characters of stdout sees
+    ends in one line that parses and holds the contract's fields with `roofline` and `cpu_baseline`"""
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--detail",
                         str(tmp_path / "detail.json")], cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-2000:]
     last = p.stdout[-4000:].rstrip().splitlines()[-1]
@@ -59,8 +85,8 @@ def test_the_drivers_command_prints_one_short_line_last(tmp_path):
 
 
 def test_bench_single_rank_contract():
-    p = subprocess.run([sys.executable, "bench.py", "--workload", "c1", "--steps", "40", "--warmup", "10"], cwd=ROOT,
-                       capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, "bench.py", "--workload", "c1", "--steps", "40", "--warmup", "10", "--full"],
+                       cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     line = _last_json(p.stdout)
     assert line["n_gpus"] == 1 and line["steps"] == 40 and line["warmup"] == 10 and line["value"] > 0
@@ -102,10 +128,10 @@ def test_bench_gpus_2_without_a_launcher_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["HELIOS_BENCH_BACKEND"] = "gloo"
     p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "10", "--workload", "c1",
-                        "--secondary", "c4small"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--secondary", "c4small", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     line = _last_json(p.stdout)
-    one = subprocess.run([sys.executable, "bench.py", "--workload", "c1", "--steps", "20", "--warmup", "10",
+    one = subprocess.run([sys.executable, "bench.py", "--workload", "c1", "--steps", "20", "--warmup", "10", "--full",
                           "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert one.returncode == 0, one.stderr[-2000:]
     one = _last_json(one.stdout)
@@ -175,7 +201,7 @@ def test_bench_two_ranks_share_the_columns():
 def test_bench_species_workload_carries_roofline_and_cpu_baseline():
     """on-the-fly mixing (config 3 shape, reduced): the line names the mixing kernel, prices it against HBM and has a
     CPU baseline too"""
-    p = subprocess.run([sys.executable, "bench.py", "--workload", "c3small", "--steps", "20", "--warmup", "10"],
+    p = subprocess.run([sys.executable, "bench.py", "--workload", "c3small", "--steps", "20", "--warmup", "10", "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     line = _last_json(p.stdout)
