@@ -35,24 +35,6 @@ struct Species {
     bool absorbing = false, scattering = false;
 };
 
-// `flux calculation method = matrix` (hx_rt_flags.matrix): the reference's per-half-layer arrays in the reference's
-// layouts, filled by the per-stage kernels of calc_trans_* (every refresh) and read by the per-stage matrix solver
-// (every iteration), both launched from the device-resident loop.  Per column unless noted; with isothermal layers the
-// `_u` members are the reference's single arrays.
-struct MatrixArrays {
-    double *trans_u = nullptr, *trans_l = nullptr, *M_u = nullptr, *M_l = nullptr, *N_u = nullptr, *N_l = nullptr,
-           *P_u = nullptr, *P_l = nullptr, *Gp_u = nullptr, *Gp_l = nullptr, *Gm_u = nullptr, *Gm_l = nullptr,
-           *w0_u = nullptr, *w0_l = nullptr;                                         // ny*nbin*nlayer
-    double *dtc_u = nullptr, *dtc_l = nullptr;                                       // nbin*nlayer (cloud optical depths)
-    double* dcol_iso = nullptr;                                                      // nlayer (delta_colmass, isothermal layers)
-    int* trigger = nullptr;                                                          // ny*nbin
-    double *F_down = nullptr, *F_up = nullptr, *Fc_down = nullptr, *Fc_up = nullptr;  // ny*nbin*ninterface
-    double *pb_lay = nullptr, *pb_int = nullptr;                                     // nbin*(nlayer+2), nbin*ninterface
-    // work arrays of the elimination, shared by the columns (solved one after the other on one stream)
-    // (alpha, beta and the source terms, which nothing reads after the elimination, are not materialised here)
-    double *c_prime = nullptr, *d_prime = nullptr;
-};
-
 struct ProfileEntry {
     std::string name;
     hipEvent_t e0, e1;
@@ -137,11 +119,10 @@ struct hx_rt {
     double* add_heat_dens = nullptr;   // L: additional heating density [erg cm^-3 s^-1]; flux = density * layer height
     bool has_heating = false;
 
-    bool matrix = false;           // hx_rt_flags.matrix
-    // the matrix method as three scans on the coefficient tiles (k_rt_flux<.., true>): the default.
-    // HELIOS_RT_MATRIX=stage: the reference-shaped per-stage kernels (calc_trans_*, one Thomas elimination per thread with its
-    // work arrays in HBM) inside the loop instead, as until round 4
-    bool matrix_scan = false;
+    // hx_rt_flags.matrix: `flux calculation method = matrix`, the direct solve as three scans on the coefficient tiles
+    // (k_rt_flux<.., true>)
+    bool matrix = false;
+    int* trigger = nullptr;           // [C][Y X] scat_trigger per spectral point, written by k_rt_coef (matrix method only)
     bool matrix_keep_state = false;   // the direct solve stores its up-fluxes too (debug = 1: the negative-flux counts read them)
     int* zero_flags = nullptr;        // [C] zeros: the `done` flags of a launch that must cover every column
     // The iteration index lives on the device (iter_dev[0]: index of the next iteration; k_rt_nodes, the first kernel of an
@@ -162,7 +143,6 @@ struct hx_rt {
     long long solve_serial = 1, matrix_tiles_serial = 0;
     int use_graph = -1;            // -1: decide from the grid size (HELIOS_RT_GRAPH=0|1 overrides), 0 / 1
     std::vector<char> have_albedo; // per column: a surface albedo has been handed over (the matrix method divides by it)
-    hx::MatrixArrays mx;
 
     // profiling
     bool profiling = false;

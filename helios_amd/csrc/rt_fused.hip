@@ -154,7 +154,7 @@ KArgs make_args(hx_rt* rt) {
     a.nparts = g.nparts; a.G = g.G; a.NW = g.NW; a.nblk_x = g.nblk_x; a.nblk = g.nblk;
     a.nplane = g.nplane; a.nchunk = rt->nchunk;
     a.has_vp = g.has_vp; a.pl_vp = g.pl_vp; a.pl_dd = g.pl_dd;
-    a.matrix = rt->matrix_scan ? 1 : 0; a.trigger = rt->mx.trigger;
+    a.matrix = rt->matrix ? 1 : 0; a.trigger = rt->trigger;
     a.Kconst = 2.0 * HX_PI * rt->f.epsi;
     a.scat = rt->f.scat; a.dir_beam = rt->f.dir_beam; a.clouds = rt->f.clouds;
     a.scat_corr = rt->f.scat_corr; a.nsweep = rt->nsweep; a.keep_down = rt->keep_down ? 1 : 0;
@@ -234,10 +234,67 @@ size_t flux_shmem_bytes(hx_rt* rt) {
            sizeof(double);
 }
 
+#define DISPATCH_ROWS(fn, rt, a)                  \
+    switch ((rt)->g.ROWS) {                       \
+        case 1: fn<1>(rt, a); break;              \
+        case 2: fn<2>(rt, a); break;              \
+        case 3: fn<3>(rt, a); break;              \
+        case 4: fn<4>(rt, a); break;              \
+        case 5: fn<5>(rt, a); break;              \
+        case 6: fn<6>(rt, a); break;              \
+        case 7: fn<7>(rt, a); break;              \
+        case 8: fn<8>(rt, a); break;              \
+        case 9: fn<9>(rt, a); break;              \
+        case 10: fn<10>(rt, a); break;            \
+        case 11: fn<11>(rt, a); break;            \
+        case 12: fn<12>(rt, a); break;            \
+        case 13: fn<13>(rt, a); break;            \
+        case 14: fn<14>(rt, a); break;            \
+        case 15: fn<15>(rt, a); break;            \
+        case 20: fn<20>(rt, a); break;            \
+        case 24: fn<24>(rt, a); break;            \
+        case 28: fn<28>(rt, a); break;            \
+        case 32: fn<32>(rt, a); break;            \
+        default: fn<16>(rt, a); break;            \
+    }
+
+// The k_rt_flux instantiation this batch runs (rt_fused_f32.hip's flux_kernel / flux_method on fp64 planes): launched with
+// `f`, or -- f == nullptr -- its dynamic-LDS limit raised to the batch's demand, the outcome in rt->shmem_rc
+template <int ROWS, int K, bool MATRIX>
+void flux_kernel(hx_rt* rt, const FluxArgs* f) {
+    const size_t shmem = flux_shmem_bytes(rt);
+    if (!f) {
+        rt->shmem_rc = hipFuncSetAttribute((const void*)k_rt_flux<ROWS, K, MATRIX>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)shmem);
+        return;
+    }
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rt_flux<ROWS, K, MATRIX>), dim3(rt->g.nblk_x, rt->C), dim3(rt->g.threads), shmem,
+                       rt->ctx->stream, *f);
+}
+
+template <int ROWS, bool MATRIX>
+void flux_method(hx_rt* rt, const FluxArgs* f) {
+    const int k = rt->g.k;
+    const bool generic = rt->generic_scans;
+    if constexpr (ROWS > 16) {   // (only on 64 lanes: choose_geometry)
+        (void)k; (void)generic;
+        flux_kernel<ROWS, 64, MATRIX>(rt, f);
+    } else {
+        if (k == 16 && !generic) flux_kernel<ROWS, 16, MATRIX>(rt, f);
+        else if (k == 32 && !generic) flux_kernel<ROWS, 32, MATRIX>(rt, f);
+        else if (k == 64 && !generic) flux_kernel<ROWS, 64, MATRIX>(rt, f);
+        else flux_kernel<ROWS, 0, MATRIX>(rt, f);
+    }
+}
+
 template <int ROWS>
+void flux_rows(hx_rt* rt, const FluxArgs* f) {
+    if (rt->matrix) flux_method<ROWS, true>(rt, f);
+    else flux_method<ROWS, false>(rt, f);
+}
+
 void launch_flux(hx_rt* rt, const KArgs& a) {
     const TileGeom& g = rt->g;
-    const size_t shmem = flux_shmem_bytes(rt);
     FluxArgs f;
     memset(&f, 0, sizeof(f));
     f.X = a.X; f.Y = a.Y; f.L = a.L; f.I = a.I; f.H = a.H;
@@ -264,63 +321,22 @@ void launch_flux(hx_rt* rt, const KArgs& a) {
     f.reverse = rt->serpentine ? (rt->flux_launches++ & 1) : 0;
     f.cache_state_from = INT_MAX;
     if (rt->serpentine && rt->state_cache_mb > 0) {
-        const double per_wg = (double)g.nparts * g.NW * ROWS * 64 * sizeof(double);
+        const double per_wg = (double)g.nparts * g.NW * g.ROWS * 64 * sizeof(double);
         const long long total = (long long)g.nblk_x * rt->C;
         const long long keep = (long long)(rt->state_cache_mb * 1048576.0 / per_wg);
         f.cache_state_from = (int)std::max(0LL, total - keep);
     }
-    if (rt->coef32) {   // `precision = single`: the same kernel on fp32 planes (rt_fused_f32.hip)
-        if (rt->matrix_scan) {
-            f.reverse = 0;
-            f.cache_state_from = INT_MAX;
-        }
-        launch_flux_f32(rt, f, dim3(g.nblk_x, rt->C), shmem);
-        return;
-    }
-    const bool generic = rt->generic_scans;
-    if constexpr (ROWS > 16) {   // (only on 64 lanes: choose_geometry)
-        if (rt->matrix_scan) {
-            f.reverse = 0;
-            f.cache_state_from = INT_MAX;
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rt_flux<ROWS, 64, true>), dim3(g.nblk_x, rt->C), dim3(g.threads), shmem,
-                               rt->ctx->stream, f);
-        } else {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rt_flux<ROWS, 64>), dim3(g.nblk_x, rt->C), dim3(g.threads), shmem,
-                               rt->ctx->stream, f);
-        }
-        return;
-    } else {
-    if (rt->matrix_scan) {   // the direct solve: no state to leave in the cache for a next launch, no launch order to alternate
+    if (rt->matrix) {   // the direct solve: no state to leave in the cache for a next launch, no launch order to alternate
         f.reverse = 0;
         f.cache_state_from = INT_MAX;
-        if (g.k == 16 && !generic)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rt_flux<ROWS, 16, true>), dim3(g.nblk_x, rt->C), dim3(g.threads), shmem,
-                               rt->ctx->stream, f);
-        else if (g.k == 32 && !generic)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rt_flux<ROWS, 32, true>), dim3(g.nblk_x, rt->C), dim3(g.threads), shmem,
-                               rt->ctx->stream, f);
-        else if (g.k == 64 && !generic)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rt_flux<ROWS, 64, true>), dim3(g.nblk_x, rt->C), dim3(g.threads), shmem,
-                               rt->ctx->stream, f);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rt_flux<ROWS, 0, true>), dim3(g.nblk_x, rt->C), dim3(g.threads), shmem,
-                               rt->ctx->stream, f);
+    }
+    if (rt->coef32) {   // `precision = single`: the same kernel on fp32 planes (rt_fused_f32.hip)
+        launch_flux_f32(rt, f, dim3(g.nblk_x, rt->C), flux_shmem_bytes(rt));
         return;
     }
-    if (g.k == 16 && !generic)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rt_flux<ROWS, 16>), dim3(g.nblk_x, rt->C), dim3(g.threads), shmem,
-                           rt->ctx->stream, f);
-    else if (g.k == 32 && !generic)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rt_flux<ROWS, 32>), dim3(g.nblk_x, rt->C), dim3(g.threads), shmem,
-                           rt->ctx->stream, f);
-    else if (g.k == 64 && !generic)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rt_flux<ROWS, 64>), dim3(g.nblk_x, rt->C), dim3(g.threads), shmem,
-                           rt->ctx->stream, f);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rt_flux<ROWS>), dim3(g.nblk_x, rt->C), dim3(g.threads), shmem,
-                           rt->ctx->stream, f);
-    }
+    DISPATCH_ROWS(flux_rows, rt, &f);
 }
+
 template <int ROWS, int TPB>
 void launch_coef_tpb(hx_rt* rt, KArgs a) {
     const TileGeom& g = rt->g;
@@ -364,64 +380,16 @@ size_t coef_shmem_bytes(const hx_rt* rt, int tpb) {
     return ((size_t)(rt->L + rt->I) * TS + (size_t)rt->H * (NBX + 2)) * sizeof(double) + 2 * TS * sizeof(int);
 }
 
-#define DISPATCH_ROWS(fn, rt, a)                  \
-    switch ((rt)->g.ROWS) {                       \
-        case 1: fn<1>(rt, a); break;              \
-        case 2: fn<2>(rt, a); break;              \
-        case 3: fn<3>(rt, a); break;              \
-        case 4: fn<4>(rt, a); break;              \
-        case 5: fn<5>(rt, a); break;              \
-        case 6: fn<6>(rt, a); break;              \
-        case 7: fn<7>(rt, a); break;              \
-        case 8: fn<8>(rt, a); break;              \
-        case 9: fn<9>(rt, a); break;              \
-        case 10: fn<10>(rt, a); break;            \
-        case 11: fn<11>(rt, a); break;            \
-        case 12: fn<12>(rt, a); break;            \
-        case 13: fn<13>(rt, a); break;            \
-        case 14: fn<14>(rt, a); break;            \
-        case 15: fn<15>(rt, a); break;            \
-        case 20: fn<20>(rt, a); break;            \
-        case 24: fn<24>(rt, a); break;            \
-        case 28: fn<28>(rt, a); break;            \
-        case 32: fn<32>(rt, a); break;            \
-        default: fn<16>(rt, a); break;            \
-    }
-
-template <int ROWS>
-void raise_flux_shmem(hx_rt* rt, int shmem) {
-    hipError_t e = hipSuccess;
-    if constexpr (ROWS <= 16) {
-        e = hipFuncSetAttribute((const void*)k_rt_flux<ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, shmem);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)k_rt_flux<ROWS, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, shmem);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)k_rt_flux<ROWS, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, shmem);
-    }
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)k_rt_flux<ROWS, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, shmem);
-    if (rt->matrix_scan) {
-        if constexpr (ROWS <= 16) {
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute((const void*)k_rt_flux<ROWS, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, shmem);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute((const void*)k_rt_flux<ROWS, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, shmem);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute((const void*)k_rt_flux<ROWS, 32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, shmem);
-        }
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)k_rt_flux<ROWS, 64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, shmem);
-    }
-    rt->shmem_rc = e;
-}
-
 int set_flux_shmem_limits(hx_rt* rt) {
     const size_t shmem = flux_shmem_bytes(rt);
     if (shmem > 160 * 1024) return rt_fail(rt, HX_E_UNSUPPORTED, "workgroup LDS demand exceeds 160 KiB");
     if (shmem <= 64 * 1024) return 0;
-    DISPATCH_ROWS(raise_flux_shmem, rt, (int)shmem);
+    if (rt->coef_bytes == 4) {   // (the batch's fp32 kernel: rt_create_into chose the width before this call)
+        HX_HIP(rt->ctx, raise_flux_shmem_f32(rt, (int)shmem));
+        return 0;
+    }
+    DISPATCH_ROWS(flux_rows, rt, nullptr);
     HX_HIP(rt->ctx, rt->shmem_rc);
-    if (rt->coef_bytes == 4) HX_HIP(rt->ctx, raise_flux_shmem_f32(rt, (int)shmem));
     return 0;
 }
 
@@ -475,11 +443,13 @@ static int rt_create_into(hx_rt* rt, hx_context* ctx, const hx_rt_dims* dims, co
 #ifdef HX_PROFILING
     if (const char* e = getenv("HELIOS_RT_DEBUG_NSWEEP")) rt->nsweep = atoi(e);  // profiling experiments only
 #endif
+    // HELIOS_RT_MATRIX=stage selected the per-stage matrix solver inside the loop until that path was retired: refused for every
+    // batch, so that an old A/B recipe cannot silently time the direct solve
+    if (const char* e = getenv("HELIOS_RT_MATRIX"))
+        return hx_fail(ctx, HX_E_ARG, "HELIOS_RT_MATRIX=%s: the knob is retired (the matrix method has one solver); unset it", e);
     rt->matrix = flags->matrix != 0;
-    rt->matrix_scan = rt->matrix;
-    if (const char* e = getenv("HELIOS_RT_MATRIX")) rt->matrix_scan = rt->matrix && std::string(e) != "stage";
-    rt->matrix_keep_state = rt->matrix_scan && flags->debug == 1;   // count_negative_fluxes reads the up-flux tiles
-    if (!choose_geometry(rt->H, rt->Y, rt->X, rt->C, flags->dir_beam, flags->scat_corr, rt->g, rt->matrix_scan ? 1 : 0))
+    rt->matrix_keep_state = rt->matrix && flags->debug == 1;   // count_negative_fluxes reads the up-flux tiles
+    if (!choose_geometry(rt->H, rt->Y, rt->X, rt->C, flags->dir_beam, flags->scat_corr, rt->g, rt->matrix ? 1 : 0))
         return hx_fail(ctx, HX_E_UNSUPPORTED, "fused path supports nlayer <= 1024 (2048 isothermal layers); use the per-stage API");
     // bin chunks of the totals reduction: k_rt_totals_a wants many, _b few.  nbin/48 measured best at 10 000 bins;
     // a small grid keeps at least 32 chunks (of >= 8 bins) so that the first level still spreads over the chip
@@ -488,7 +458,7 @@ static int rt_create_into(hx_rt* rt, hx_context* ctx, const hx_rt_dims* dims, co
     // `precision = single`: fp32 coefficient planes for the sweeps where the tiling has an fp32 instantiation
     // (rt_fused_f32.hip).  The matrix method keeps fp64 planes: its direct solve of a nearly conservative column (w0 at
     // w_0_limit, thin layers) took the planes' fp32 rounding to 2e-3 on spectral up-fluxes, the sweeps stayed within 1e-5
-    // (DESIGN.md); the per-stage matrix solver has no planes at all.  The caller reads the width through "coef_plane_bytes"
+    // (DESIGN.md).  The caller reads the width through "coef_plane_bytes"
     rt->coef_bytes = flags->coef_fp32 && !rt->matrix && coef_fp32_tiling(rt->g.ROWS, rt->g.k, rt->generic_scans) ? 4 : 8;
     if (const char* e = getenv("HELIOS_RT_CLOUD_LDS")) rt->cloud_lds = atoi(e) != 0;  // 0: k_rt_coef's fallback path (tests)
     // tiles per workgroup of k_rt_coef: 16 spectral points staged side by side (128-byte runs of the k-table) -- 4 tiles
@@ -550,33 +520,16 @@ static int rt_create_into(hx_rt* rt, hx_context* ctx, const hx_rt_dims* dims, co
         RT_ALLOC(rt->sc_spec_lay, X * I); RT_ALLOC(rt->sc_spec_int, X * I);
     }
     RT_ALLOC(rt->delta_z, C * L); RT_ALLOC(rt->z_lay, C * L);
-    const bool stage_matrix = rt->matrix && !rt->matrix_scan;
-    if (flags->dir_beam || stage_matrix) {   // (the per-stage matrix solver reads the beam arrays unconditionally: zeros without a beam)
+    if (flags->dir_beam) {
         RT_ALLOC(rt->dtau_u, C * nc * L); RT_ALLOC(rt->dtau_l, C * nc * L);
         RT_ALLOC(rt->F_dir_wg, C * nc * I); RT_ALLOC(rt->Fc_dir_wg, C * nc * I);
     }
     RT_ALLOC(rt->F_dir_band_n, C * X * I);
     RT_ALLOC(rt->Bn, C * X * (rt->H + 3));
-    if (rt->matrix_scan) RT_ALLOC(rt->mx.trigger, C * nc);
-    if (stage_matrix) {
-        // `flux calculation method = matrix` through the per-stage kernels: the reference's per-half-layer arrays instead of the coefficient tiles
-        // and the persistent up-flux state (a direct solve has none)
-        MatrixArrays& m = rt->mx;
-        const size_t wgL = C * nc * L, halves = flags->iso ? 1 : 2;
-        for (double** q : {&m.trans_u, &m.M_u, &m.N_u, &m.P_u, &m.Gp_u, &m.Gm_u, &m.w0_u}) RT_ALLOC(*q, wgL);
-        if (!flags->iso)
-            for (double** q : {&m.trans_l, &m.M_l, &m.N_l, &m.P_l, &m.Gp_l, &m.Gm_l, &m.w0_l}) RT_ALLOC(*q, wgL);
-        RT_ALLOC(m.dtc_u, C * X * L); RT_ALLOC(m.dtc_l, C * X * L); RT_ALLOC(m.dcol_iso, C * L);
-        if (!m.trigger) RT_ALLOC(m.trigger, C * nc);
-        RT_ALLOC(m.F_down, C * nc * I); RT_ALLOC(m.F_up, C * nc * I);
-        RT_ALLOC(m.Fc_down, C * nc * I); RT_ALLOC(m.Fc_up, C * nc * I);
-        RT_ALLOC(m.pb_lay, C * X * (L + 2)); RT_ALLOC(m.pb_int, C * X * I);
-        RT_ALLOC(m.c_prime, nc * (halves * 2 * I)); RT_ALLOC(m.d_prime, nc * (halves * 2 * I));
-    } else {
-        if (rt->coef_bytes == 4) RT_ALLOC(rt->coef32, C * rt->g.coef_elems_per_col);
-        else RT_ALLOC(rt->coef, C * rt->g.coef_elems_per_col);
-        RT_ALLOC(rt->Utile, C * rt->g.flux_elems_per_col);
-    }
+    if (rt->matrix) RT_ALLOC(rt->trigger, C * nc);
+    if (rt->coef_bytes == 4) RT_ALLOC(rt->coef32, C * rt->g.coef_elems_per_col);
+    else RT_ALLOC(rt->coef, C * rt->g.coef_elems_per_col);
+    RT_ALLOC(rt->Utile, C * rt->g.flux_elems_per_col);
     RT_ALLOC(rt->U0, C * nc); RT_ALLOC(rt->boaK, C * nc); RT_ALLOC(rt->Fdir0, C * nc);
     RT_ALLOC(rt->F_down_band_n, C * X * I); RT_ALLOC(rt->F_up_band_n, C * X * I);
     RT_ALLOC(rt->tot_part, C * rt->nchunk * 2 * I);
@@ -808,10 +761,6 @@ int hx_rt_set_column_profile(hx_rt* rt, int col, const double* p_lay, const doub
         rc |= h2d(rt, rt->p_int + c * I, p_int, I * 8);
         rc |= h2d(rt, rt->dcol_u + c * L, du.data(), L * 8);
         rc |= h2d(rt, rt->dcol_l + c * L, dl.data(), L * 8);
-        if (rt->matrix && rt->mx.dcol_iso) {  // whole layers (host_functions.py:733), calc_trans_iso's delta_colmass
-            for (size_t i = 0; i < L; i++) du[i] = (p_int[i] - p_int[i + 1]) / g;
-            rc |= h2d(rt, rt->mx.dcol_iso + c * L, du.data(), L * 8);
-        }
         rc |= h2d(rt, rt->T_lay + c * (L + 1), T_lay, (L + 1) * 8);
         if (surf_albedo) {
             rc |= h2d(rt, rt->surf_albedo + c * X, surf_albedo, X * 8);
@@ -1010,86 +959,6 @@ static int refresh_species(hx_rt* rt) {
     return 0;
 }
 
-// ---- `flux calculation method = matrix` ------------------------------------------------------------------------------
-// The per-stage kernels of calc_trans_* and fband_matrix_* (the ones the goldens pin), launched column by column from the
-// device-resident loop on the arrays of rt->mx.  A column whose loop has ended recomputes its coefficients from unchanged
-// inputs (same values) and skips the solve (`done`), so its fluxes stay those of its last iteration.
-static int matrix_calc_trans(hx_rt* rt) {
-    ProfScope ps(rt, "matrix_calc_trans");
-    hx_context* ctx = rt->ctx;
-    const hx_rt_flags& f = rt->f;
-    const MatrixArrays& m = rt->mx;
-    const size_t X = rt->X, L = rt->L, I = rt->I, nc = X * rt->Y, wgL = nc * L, wgI = nc * I, bI = X * I, bL = X * L;
-    HX_HIP(ctx, hipMemsetAsync(m.trigger, 0, (size_t)rt->C * nc * sizeof(int), ctx->stream));  // computation.py:368
-    for (size_t c = 0; c < (size_t)rt->C; c++) {
-        const double mu_star = rt->cols[c].mu_star;
-        int rc;
-        if (f.iso)
-            rc = hx_calc_trans_iso(ctx, m.trans_u + c * wgL, rt->dtau_u + c * wgL, m.M_u + c * wgL, m.N_u + c * wgL,
-                                   m.P_u + c * wgL, m.Gp_u + c * wgL, m.Gm_u + c * wgL, m.dcol_iso + c * L,
-                                   rt->opac_wg_lay + c * wgI, rt->mmm_lay + c * I, rt->scat_cross_lay + c * bI,
-                                   rt->cl_abs_lay + c * bI, rt->cl_sc_lay + c * bI, m.dtc_u + c * bL, m.w0_u + c * wgL,
-                                   rt->g0_tot_lay + c * bI, m.trigger + c * nc, f.g_0, f.epsi, f.epsi2, mu_star,
-                                   f.w_0_limit, f.w_0_scat_limit, f.scat, rt->X, rt->Y, rt->L, f.clouds, f.scat_corr, 0,
-                                   f.i2s_transition);
-        else
-            rc = hx_calc_trans_noniso(
-                ctx, m.trans_u + c * wgL, m.trans_l + c * wgL, rt->dtau_u + c * wgL, rt->dtau_l + c * wgL, m.M_u + c * wgL,
-                m.M_l + c * wgL, m.N_u + c * wgL, m.N_l + c * wgL, m.P_u + c * wgL, m.P_l + c * wgL, m.Gp_u + c * wgL,
-                m.Gp_l + c * wgL, m.Gm_u + c * wgL, m.Gm_l + c * wgL, rt->dcol_u + c * L, rt->dcol_l + c * L,
-                rt->opac_wg_lay + c * wgI, rt->opac_wg_int + c * wgI, rt->mmm_lay + c * I, rt->mmm_int + c * I,
-                rt->scat_cross_lay + c * bI, rt->scat_cross_int + c * bI, rt->cl_abs_lay + c * bI, rt->cl_abs_int + c * bI,
-                rt->cl_sc_lay + c * bI, rt->cl_sc_int + c * bI, m.dtc_u + c * bL, m.dtc_l + c * bL, m.w0_u + c * wgL,
-                m.w0_l + c * wgL, rt->g0_tot_lay + c * bI, rt->g0_tot_int + c * bI, m.trigger + c * nc, f.g_0, f.epsi,
-                f.epsi2, mu_star, f.w_0_limit, f.w_0_scat_limit, f.scat, rt->X, rt->Y, rt->L, f.clouds, f.scat_corr, 0,
-                f.i2s_transition);
-        if (rc) return rc;
-    }
-    return 0;
-}
-
-static int matrix_solve(hx_rt* rt) {
-    ProfScope ps(rt, "matrix_solve");
-    hx_context* ctx = rt->ctx;
-    const hx_rt_flags& f = rt->f;
-    const MatrixArrays& m = rt->mx;
-    const size_t X = rt->X, L = rt->L, I = rt->I, nc = X * rt->Y, wgL = nc * L, wgI = nc * I, bI = X * I, bL = X * L;
-    {   // the node values in the reference's layouts
-        const long long n = (long long)X * (L + 2 + I);
-        k_rt_matrix_planck<<<dim3(hx_cdiv(n, 256), rt->C), 256, 0, ctx->stream>>>(rt->Bn, m.pb_lay, m.pb_int, rt->X, rt->L,
-                                                                               rt->H, f.iso, rt->done);
-        HX_LAUNCH_CHECK(ctx);
-    }
-    for (size_t c = 0; c < (size_t)rt->C; c++) {
-        const hx_rt_column& cp = rt->cols[c];
-        const double* pbl = m.pb_lay + c * X * (L + 2);
-        int rc;
-        if (f.iso)
-            rc = hx_internal_fband_matrix_iso(
-                ctx, rt->done + c, m.F_down + c * wgI, m.F_up + c * wgI, rt->F_dir_wg + c * wgI, pbl, m.w0_u + c * wgL,
-                m.M_u + c * wgL, m.N_u + c * wgL, m.P_u + c * wgL, m.Gp_u + c * wgL, m.Gm_u + c * wgL,
-                rt->g0_tot_lay + c * bI, nullptr, nullptr, nullptr, nullptr, m.c_prime, m.d_prime, m.trigger + c * nc,
-                m.trans_u + c * wgL, rt->surf_albedo + c * X, f.g_0, f.singlewalk, cp.R_star, cp.a, rt->I, rt->X,
-                cp.f_factor, cp.mu_star, rt->Y, f.epsi, f.dir_beam, f.clouds, f.scat_corr, f.debug, f.i2s_transition);
-        else
-            rc = hx_internal_fband_matrix_noniso(
-                ctx, rt->done + c, m.F_down + c * wgI, m.F_up + c * wgI, m.Fc_down + c * wgI, m.Fc_up + c * wgI,
-                rt->F_dir_wg + c * wgI, rt->Fc_dir_wg + c * wgI, pbl, m.pb_int + c * bI, m.w0_u + c * wgL, m.w0_l + c * wgL,
-                rt->dtau_u + c * wgL, rt->dtau_l + c * wgL, m.dtc_u + c * bL, m.dtc_l + c * bL, m.M_u + c * wgL,
-                m.M_l + c * wgL, m.N_u + c * wgL, m.N_l + c * wgL, m.P_u + c * wgL, m.P_l + c * wgL, m.Gp_u + c * wgL,
-                m.Gp_l + c * wgL, m.Gm_u + c * wgL, m.Gm_l + c * wgL, rt->g0_tot_lay + c * bI, rt->g0_tot_int + c * bI,
-                nullptr, nullptr, nullptr, nullptr, m.c_prime, m.d_prime, m.trigger + c * nc, m.trans_u + c * wgL,
-                m.trans_l + c * wgL, rt->surf_albedo + c * X, f.g_0, f.singlewalk, cp.R_star, cp.a, rt->I, rt->X,
-                cp.f_factor, cp.mu_star, rt->Y, f.epsi, f.delta_tau_limit, f.dir_beam, f.clouds, f.scat_corr, f.debug,
-                f.i2s_transition);
-        if (rc) return rc;
-    }
-    k_rt_matrix_bands<<<dim3(hx_cdiv(rt->X, QUAD_BINS), rt->I, rt->C), 256, 2 * QUAD_BINS * (rt->Y + 1) * sizeof(double), ctx->stream>>>(
-        m.F_down, m.F_up, rt->F_down_band_n, rt->F_up_band_n, rt->gauss_w, rt->X, rt->Y, rt->I, rt->done);
-    HX_LAUNCH_CHECK(ctx);
-    return 0;
-}
-
 int hx_rt_refresh(hx_rt* rt) {
     if (!rt) return HX_E_ARG;  // e.g. a call after hx_rt_destroy
     hx_context* ctx = rt->ctx;
@@ -1124,8 +993,7 @@ int hx_rt_refresh(hx_rt* rt) {
     // inside the kernels and keeps the state of its last real refresh.  No host round trip.
     // premixed table without the beam: the k-table look-up is fused into k_rt_coef (the beam needs the
     // materialised opacities for its optical depths); HELIOS_RT_FUSED_LOOKUP=0 switches it off
-    const bool stage_matrix = rt->matrix && !rt->matrix_scan;
-    bool fused_lookup = rt->d.nspecies == 0 && !rt->f.dir_beam && !stage_matrix;
+    bool fused_lookup = rt->d.nspecies == 0 && !rt->f.dir_beam;
     if (const char* e = getenv("HELIOS_RT_FUSED_LOOKUP")) fused_lookup = fused_lookup && atoi(e) != 0;
     rt->opac_stale = fused_lookup;
     if (rt->d.nspecies == 0) {
@@ -1160,16 +1028,10 @@ int hx_rt_refresh(hx_rt* rt) {
                                                 rt->F_add_heat_sum, L, rt->done);
         HX_LAUNCH_CHECK(ctx);
     }
-    if (stage_matrix) {
-        rc = matrix_calc_trans(rt);
-        if (rc) return rc;
-    }
     if (rt->f.dir_beam) {
         ProfScope ps(rt, "direct_beam");
-        if (!stage_matrix) {  // (calc_trans_* has just written the same optical depths)
-            k_rt_dtau_halves<<<dim3(hx_cdiv((long long)nc, 256), L, C), 256, 0, ctx->stream>>>(a);
-            HX_LAUNCH_CHECK(ctx);
-        }
+        k_rt_dtau_halves<<<dim3(hx_cdiv((long long)nc, 256), L, C), 256, 0, ctx->stream>>>(a);
+        HX_LAUNCH_CHECK(ctx);
         rc = hx_internal_fdir_noniso_batch(ctx, rt->F_dir_wg, rt->f.iso ? nullptr : rt->Fc_dir_wg, rt->Bstar, rt->dtau_u, rt->dtau_l,
                                            rt->z_lay, rt->colpar, rt->done, C, rt->f.dir_beam,
                                            rt->f.geom_zenith_corr, I, X, Y);
@@ -1178,7 +1040,7 @@ int hx_rt_refresh(hx_rt* rt) {
                                                                            rt->gauss_w, X, Y, I, rt->done);
         HX_LAUNCH_CHECK(ctx);
     }
-    if (!stage_matrix) {
+    {
         ProfScope ps(rt, "rt_coef");
         k_rt_half_bands<<<dim3(hx_cdiv(X, 32), hx_cdiv(rt->H, 32), C), 256, 0, ctx->stream>>>(a);
         HX_LAUNCH_CHECK(ctx);
@@ -1203,10 +1065,9 @@ static int count_negative_fluxes(hx_rt* rt) {
 
 // the spectral fluxes of one iteration: the register-resident sweeps, or one tridiagonal solve per spectral point
 static int spectral_fluxes(hx_rt* rt, const KArgs& a) {
-    if (rt->matrix && !rt->matrix_scan) return matrix_solve(rt);
     {
-        ProfScope ps(rt, rt->matrix_scan ? "matrix_solve" : "rt_flux");
-        DISPATCH_ROWS(launch_flux, rt, a);
+        ProfScope ps(rt, rt->matrix ? "matrix_solve" : "rt_flux");
+        launch_flux(rt, a);
         HX_LAUNCH_CHECK(rt->ctx);
     }
     return rt->f.debug == 1 ? count_negative_fluxes(rt) : 0;   // (debug = 1 keeps the solve's stores on: rt_create_into)
@@ -1505,9 +1366,8 @@ static bool graph_wanted(hx_rt* rt) {
     // kappa refresh (computation.py:921-923)
     bool time_stepped = false;   // any column of the batch
     for (const auto& c : rt->cols) time_stepped = time_stepped || c.physical_tstep != 0;
-    // (the matrix method's direct solve replays like the sweeps; its per-stage form -- HELIOS_RT_MATRIX=stage -- launches
-    // column by column and stays outside)
-    return rt->use_graph == 1 && !rt->profiling && !(rt->matrix && !rt->matrix_scan) && !(rt->entr_kappa && time_stepped);
+    // (the matrix method's direct solve replays like the sweeps)
+    return rt->use_graph == 1 && !rt->profiling && !(rt->entr_kappa && time_stepped);
 }
 
 // `with_refresh`: the whole decade -- the opacity refresh with the iteration that carries it, then the nine refresh-free
@@ -1694,7 +1554,6 @@ int hx_rt_get(hx_rt* rt, int col, const char* name, void* out, size_t out_bytes)
     HX_REQUIRE(rt->ctx, col >= 0 && col < rt->C, HX_E_ARG, "column index out of range");
     if (strcmp(name, "coef_planes") == 0) {   // the column's coefficient planes as k_rt_coef wrote them (after a refresh)
         const void* planes = rt->coef32 ? (const void*)rt->coef32 : (const void*)rt->coef;
-        HX_REQUIRE(rt->ctx, planes, HX_E_ARG, "this batch has no coefficient planes (per-stage matrix solver)");
         const size_t bytes = rt->g.coef_elems_per_col * rt->coef_bytes;
         return get_plain(rt, (const char*)planes + (size_t)col * bytes, bytes, out, out_bytes);
     }
@@ -1782,17 +1641,7 @@ int hx_rt_get(hx_rt* rt, int col, const char* name, void* out, size_t out_bytes)
         }
         return 0;
     }
-    if (rt->matrix && !rt->matrix_scan && (n == "F_up_wg" || n == "F_down_wg" || n == "Fc_up_wg" || n == "Fc_down_wg")) {
-        // the solver's own arrays, already in the reference's layout (centre fluxes: nlayer slabs, the rest stays zero)
-        const MatrixArrays& m = rt->mx;
-        if (out_bytes != nc * I * 8) return hx_fail(rt->ctx, HX_E_ARG, "hx_rt_get: wrong buffer size");
-        const bool centre = n[1] == 'c';
-        const double* src = n == "F_up_wg" ? m.F_up : n == "F_down_wg" ? m.F_down : n == "Fc_up_wg" ? m.Fc_up : m.Fc_down;
-        memset(out, 0, out_bytes);
-        if (centre && rt->f.iso) return 0;
-        return hx_d2h(rt->ctx, out, src + c * nc * I, nc * (centre ? L : I) * 8);
-    }
-    if (rt->matrix_scan && (n == "F_up_wg" || n == "F_down_wg" || n == "Fc_up_wg" || n == "Fc_down_wg")) {
+    if (rt->matrix && (n == "F_up_wg" || n == "F_down_wg" || n == "Fc_up_wg" || n == "Fc_down_wg")) {
         // The direct solve keeps no spectral fluxes between iterations (nothing reads them: the band fluxes are summed inside
         // the kernel).  Asked for, they are the last solve's: the coefficient tiles and node Planck values it read are still in
         // place, so the same launch -- this time with its stores, and for every column, also those whose loop has ended --
@@ -1808,7 +1657,7 @@ int hx_rt_get(hx_rt* rt, int col, const char* name, void* out, size_t out_bytes)
             rt->matrix_keep_state = true;
             KArgs a = make_args(rt);
             a.done = rt->zero_flags;
-            DISPATCH_ROWS(launch_flux, rt, a);
+            launch_flux(rt, a);
             rt->keep_down = kd;
             rt->matrix_keep_state = ks;
             HX_LAUNCH_CHECK(rt->ctx);
@@ -1819,7 +1668,7 @@ int hx_rt_get(hx_rt* rt, int col, const char* name, void* out, size_t out_bytes)
     if (n == "F_up_wg") return get_flux_wg(rt, col, rt->Utile, rt->U0, true, true, out, out_bytes);
     if (n == "Fc_up_wg") return get_flux_wg(rt, col, rt->Utile, nullptr, true, false, out, out_bytes);
     if (n == "F_down_wg" || n == "Fc_down_wg") {
-        HX_REQUIRE(rt->ctx, (rt->keep_down || rt->matrix_scan) && rt->Dtile, HX_E_STATE,
+        HX_REQUIRE(rt->ctx, (rt->keep_down || rt->matrix) && rt->Dtile, HX_E_STATE,
                    "down-flux tiles are only kept after hx_rt_set_state(rt, col, \"keep_down\", ...)");
         int rc = get_flux_wg(rt, col, rt->Dtile, nullptr, false, n == "F_down_wg", out, out_bytes);
         if (rc || n != "F_down_wg") return rc;
@@ -1987,7 +1836,7 @@ int hx_rt_traffic_model(hx_rt* rt, double* step_alg, double* step_act, double* r
     const double tiles = (double)g.nblk * g.NW * 64.0 * g.ROWS * 8.0;  // one fp64 plane (the state)
     const double planes = tiles / 8.0 * rt->coef_bytes * g.nplane;     // the coefficient planes, fp64 or fp32
     // (the matrix method's direct solve reads the same planes and keeps no flux state)
-    const double state_planes = rt->matrix_scan ? (rt->matrix_keep_state ? 1.0 : 0.0) : 2.0;
+    const double state_planes = rt->matrix ? (rt->matrix_keep_state ? 1.0 : 0.0) : 2.0;
     const double flux_k = planes + tiles * (state_planes + (rt->keep_down ? 1.0 : 0.0))     // coef + U read/write
                           + 8.0 * X * (rt->H + 3) * 2.0                            // node Planck write+read
                           + 8.0 * X * 2.0 * (L + 1) * 2.0                          // band arrays w + r

@@ -591,64 +591,6 @@ __global__ void __launch_bounds__(flux_one_wave(ROWS) ? 64 : 320) k_rt_flux_f32(
 }
 
 #ifndef HX_PLANE_KERNELS_ONLY
-// ---- `flux calculation method = matrix`: glue between the node arrays of the loop and the per-stage solver -------------
-// Planck values of the nodes, Bn[x][H+3], in the reference's layouts: planckband_lay[i + x (L+2)] (layers, then the stellar
-// row and the surface) and planckband_int[i + x I].  grid (chunks, C).
-__global__ void __launch_bounds__(256) k_rt_matrix_planck(const double* __restrict__ Bn, double* __restrict__ pb_lay,
-                                                          double* __restrict__ pb_int, int X, int L, int H, int iso,
-                                                          const int* __restrict__ done) {
-    const int col = blockIdx.y;
-    if (done[col]) return;
-    const int NN = H + 3, I = L + 1, per = L + 2 + I;
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long long)X * per) return;
-    const int x = (int)(t / per), s = (int)(t - (long long)x * per);
-    const double* B = Bn + ((size_t)col * X + x) * NN;
-    if (s < L + 2) {
-        const int n = s < L ? (iso ? s : 2 * s + 1) : H + 1 + (s - L);
-        pb_lay[((size_t)col * X + x) * (L + 2) + s] = B[n];
-    } else {  // isothermal layers: the reference computes no interface values (computation.py:315-329)
-        const int i = s - (L + 2);
-        pb_int[((size_t)col * X + x) * I + i] = iso ? 0.0 : B[2 * i];
-    }
-}
-
-// Gauss quadrature of the solver's interface fluxes (kernels.cu:2474-2476) into the band arrays of the loop, [x][i].
-// grid (ceil(X / QUAD_BINS), I, C), 256 threads: the workgroup reads its bins' ny*QUAD_BINS spectral points of one
-// interface as one contiguous run, weights them into LDS, and one thread per bin adds its Gauss points in order (a thread
-// per bin reading its own ny values took 0.65 ms at 10 000 x 101 x 20: one 64-byte sector per double)
-constexpr int QUAD_BINS = 32;
-__global__ void __launch_bounds__(256) k_rt_matrix_bands(const double* __restrict__ F_down_wg, const double* __restrict__ F_up_wg,
-                                                         double* __restrict__ F_down_band_n, double* __restrict__ F_up_band_n,
-                                                         const double* __restrict__ gauss_w, int X, int Y, int I,
-                                                         const int* __restrict__ done) {
-    extern __shared__ __align__(16) double smem[];
-    const int col = blockIdx.z, i = blockIdx.y, x0 = blockIdx.x * QUAD_BINS;
-    if (done[col]) return;
-    const int nb = min(QUAD_BINS, X - x0), pitch = Y + 1;
-    double* su = smem;
-    double* sd = smem + QUAD_BINS * pitch;
-    const size_t nc = (size_t)X * Y, base = (size_t)col * nc * I + nc * i + (size_t)Y * x0;
-    for (int t = threadIdx.x; t < nb * Y; t += blockDim.x) {
-        const int xl = t / Y, y = t - xl * Y;
-        const double w = 0.5 * gauss_w[y];
-        su[xl * pitch + y] = w * F_up_wg[base + t];
-        sd[xl * pitch + y] = w * F_down_wg[base + t];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < nb) {
-        const int xl = threadIdx.x;
-        double d = 0.0, u = 0.0;
-        for (int y = 0; y < Y; y++) {
-            u += su[xl * pitch + y];
-            d += sd[xl * pitch + y];
-        }
-        const size_t b = ((size_t)col * X + x0 + xl) * I + i;
-        F_up_band_n[b] = u;
-        F_down_band_n[b] = d;
-    }
-}
-
 // ---- per iteration: wavelength totals, level 1 ---------------------------------------------------
 // grid (nchunk, C), 256 threads.  Thread t owns the (dir, i) slots t, t+256, ... (< 2I) and walks the
 // bins of its chunk; consecutive threads read consecutive addresses of the [x][i] band arrays.
@@ -1112,7 +1054,7 @@ __global__ void __launch_bounds__(256) k_rt_tile_rows(const double* __restrict__
 // The tilings with an fp32 instantiation: every tiling choose_geometry selects without scratch (columns of up to 416
 // layers, isothermal ones up to 512).  Other tilings run on fp64 planes.
 bool coef_fp32_tiling(int rows, int k, bool generic_scans);
-// the launches of launch_coef_tpb / launch_flux on rt->coef32 (ROWS, k and the method are the batch's: rt->g, rt->matrix_scan)
+// the launches of launch_coef_tpb / launch_flux on rt->coef32 (ROWS, k and the method are the batch's: rt->g, rt->matrix)
 void launch_coef_f32(hx_rt* rt, const KArgs& a, int tpb, dim3 grid, size_t shmem);
 void launch_flux_f32(hx_rt* rt, const FluxArgs& f, dim3 grid, size_t shmem);
 hipError_t raise_flux_shmem_f32(hx_rt* rt, int shmem);

@@ -73,9 +73,6 @@ __device__ __forceinline__ void back_substitute(const double* __restrict__ c_pri
     }
 }
 
-// LEAN: the call of the device-resident loop -- the work arrays alpha ... s_up, which nothing reads, are not written, and
-// without a direct beam its (zero) arrays and G+- are not read: traffic, the kernel runs at the memory system's rate
-template <bool LEAN>
 __global__ void __launch_bounds__(256)
 k_fband_matrix_iso(double* __restrict__ F_down, double* __restrict__ F_up,
                    const double* __restrict__ F_dir, const double* __restrict__ planckband_lay,
@@ -88,10 +85,10 @@ k_fband_matrix_iso(double* __restrict__ F_down, double* __restrict__ F_up,
                    const int* __restrict__ scat_trigger, const double* __restrict__ trans,
                    const double* __restrict__ surf_albedo, double g_0, double Rstar, double a, int ni,
                    int nbin, double f_factor, double mu_star, int ny, double epsi, int dir_beam,
-                   int clouds, int scat_corr, double i2s, const int* __restrict__ skip) {
+                   int clouds, int scat_corr, double i2s) {
     const size_t nc = (size_t)ny * nbin;
     const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= nc || (skip && *skip)) return;
+    if (c >= nc) return;
     const int x = (int)(c / ny), nl = ni - 1;
     const double* B = planckband_lay + (size_t)x * (ni + 1);
     const double A = surf_albedo[x];
@@ -110,22 +107,17 @@ k_fband_matrix_iso(double* __restrict__ F_down, double* __restrict__ F_up,
             const double M = M_term[k], N = N_term[k], P = P_term[k], w0 = w_0[k];
             const double g0 = clouds == 1 ? g_0_tot_lay[x + (size_t)nbin * j] : g_0;
             const double E = E_factor(w0, g0, scat_corr, i2s);
-            const double Fdir_top = (!LEAN || dir_beam == 1) ? F_dir[k + nc] : 0.0;
+            const double Fdir_top = F_dir[k + nc];
             const double al = P / M, be = -N / M;
             const double planck = 2.0 * HX_PI * epsi * (1.0 - w0) / (E - w0) * (N + M - P) * B[j];
-            double dd = 0.0, du = 0.0;
-            if (!LEAN || dir_beam == 1) {
-                const double Gm = G_minus[k], Gp = G_plus[k];
-                dd = dmin(0.0, Fdir_bot / (-mu_star) * (Gm * M + Gp * N) - Fdir_top / (-mu_star) * P * Gm);
-                du = dmin(0.0, Fdir_top / (-mu_star) * (Gm * N + Gp * M) - Fdir_bot / (-mu_star) * P * Gp);
-            }
+            const double Gm = G_minus[k], Gp = G_plus[k];
+            const double dd = dmin(0.0, Fdir_bot / (-mu_star) * (Gm * M + Gp * N) - Fdir_top / (-mu_star) * P * Gm);
+            const double du = dmin(0.0, Fdir_top / (-mu_star) * (Gm * N + Gp * M) - Fdir_bot / (-mu_star) * P * Gp);
             const double sd = 1.0 / M * (planck + dd), su = 1.0 / M * (planck + du);
-            if (!LEAN) {
-                alpha[k] = al;
-                beta[k] = be;
-                s_down[k] = sd;
-                s_up[k] = su;
-            }
+            alpha[k] = al;
+            beta[k] = be;
+            s_down[k] = sd;
+            s_up[k] = su;
             th.push(-be, -al, sd);  // down equation of slab j
             th.push(-be, 1.0, su);  // up equation of slab j
             Fdir_bot = Fdir_top;
@@ -162,7 +154,6 @@ struct MatrixNoniso {
     double *alpha, *beta, *s_down, *s_up, *c_prime, *d_prime;
 };
 
-template <bool LEAN>
 __global__ void __launch_bounds__(256)
 k_fband_matrix_noniso(double* __restrict__ F_down, double* __restrict__ F_up,
                       double* __restrict__ Fc_down, double* __restrict__ Fc_up,
@@ -172,10 +163,10 @@ k_fband_matrix_noniso(double* __restrict__ F_down, double* __restrict__ F_up,
                       const int* __restrict__ scat_trigger, const double* __restrict__ surf_albedo,
                       double g_0, double Rstar, double a, int ni, int nbin, double f_factor,
                       double mu_star, int ny, double epsi, double dtau_limit, int dir_beam, int clouds,
-                      int scat_corr, double i2s, const int* __restrict__ skip) {
+                      int scat_corr, double i2s) {
     const size_t nc = (size_t)ny * nbin;
     const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= nc || (skip && *skip)) return;
+    if (c >= nc) return;
     const int x = (int)(c / ny), nl = ni - 1;
     const double* Bl = planckband_lay + (size_t)x * (ni + 1);
     const double* Bi = planckband_int + (size_t)x * ni;
@@ -209,24 +200,19 @@ k_fband_matrix_noniso(double* __restrict__ F_down, double* __restrict__ F_up,
                 pd = (M + N) * B_bot - P * B_top + epsi / (E * (1.0 - w0 * g0)) * (P - M + N) * pgrad;
                 pu = (M + N) * B_top - P * B_bot + epsi / (E * (1.0 - w0 * g0)) * (M - N - P) * pgrad;
             }
-            double dd = 0.0, du = 0.0;
-            if (!LEAN || dir_beam == 1) {
-                const double Gm = lower ? q.Gml[k] : q.Gmu[k], Gp = lower ? q.Gpl[k] : q.Gpu[k];
-                const double F_bot = lower ? F_dir[k] : Fc_dir[k];
-                const double F_top = lower ? Fc_dir[k] : F_dir[k + nc];
-                dd = dmin(0.0, F_bot / (-mu_star) * (Gm * M + Gp * N) - F_top / (-mu_star) * P * Gm);
-                du = dmin(0.0, F_top / (-mu_star) * (Gm * N + Gp * M) - F_bot / (-mu_star) * P * Gp);
-            }
+            const double Gm = lower ? q.Gml[k] : q.Gmu[k], Gp = lower ? q.Gpl[k] : q.Gpu[k];
+            const double F_bot = lower ? F_dir[k] : Fc_dir[k];
+            const double F_top = lower ? Fc_dir[k] : F_dir[k + nc];
+            const double dd = dmin(0.0, F_bot / (-mu_star) * (Gm * M + Gp * N) - F_top / (-mu_star) * P * Gm);
+            const double du = dmin(0.0, F_top / (-mu_star) * (Gm * N + Gp * M) - F_bot / (-mu_star) * P * Gp);
             const double al = P / M, be = -N / M;
             const double sd = 1.0 / M * (2.0 * HX_PI * epsi * (1.0 - w0) / (E - w0) * pd + dd);
             const double su = 1.0 / M * (2.0 * HX_PI * epsi * (1.0 - w0) / (E - w0) * pu + du);
             const size_t kj = c + nc * j;
-            if (!LEAN) {
-                q.alpha[kj] = al;
-                q.beta[kj] = be;
-                q.s_down[kj] = sd;
-                q.s_up[kj] = su;
-            }
+            q.alpha[kj] = al;
+            q.beta[kj] = be;
+            q.s_down[kj] = sd;
+            q.s_up[kj] = su;
             th.push(-be, -al, sd);
             th.push(-be, 1.0, su);
         }
@@ -284,8 +270,7 @@ k_fband_matrix_noniso(double* __restrict__ F_down, double* __restrict__ F_up,
 
 extern "C" {
 
-// `skip`: device flag of the fused loop (a column whose loop has ended keeps its fluxes), or null
-int hx_internal_fband_matrix_iso(hx_context* ctx, const int* skip, double* F_down_wg, double* F_up_wg, const double* F_dir_wg,
+int hx_fband_matrix_iso(hx_context* ctx, double* F_down_wg, double* F_up_wg, const double* F_dir_wg,
                         const double* planckband_lay, const double* w_0, const double* M_term,
                         const double* N_term, const double* P_term, const double* G_plus,
                         const double* G_minus, const double* g_0_tot_lay, double* alpha, double* beta,
@@ -296,11 +281,11 @@ int hx_internal_fband_matrix_iso(hx_context* ctx, const int* skip, double* F_dow
                         double epsi, int dir_beam, int clouds, int scat_corr, int debug,
                         double i2s_transition) {
     (void)singlewalk;
-    (skip ? k_fband_matrix_iso<true> : k_fband_matrix_iso<false>)<<<hx_cdiv((long long)ny * nbin, 256), 256, 0, ctx->stream>>>(
+    k_fband_matrix_iso<<<hx_cdiv((long long)ny * nbin, 256), 256, 0, ctx->stream>>>(
         F_down_wg, F_up_wg, F_dir_wg, planckband_lay, w_0, M_term, N_term, P_term, G_plus, G_minus,
         g_0_tot_lay, alpha, beta, source_term_down, source_term_up, c_prime, d_prime, scat_trigger,
         trans_wg, surf_albedo, g_0, Rstar, a, numinterfaces, nbin, f_factor, mu_star, ny, epsi,
-        dir_beam, clouds, scat_corr, i2s_transition, skip);
+        dir_beam, clouds, scat_corr, i2s_transition);
     HX_LAUNCH_CHECK(ctx);
     if (debug == 1) {  // kernels.cu:1990, :2018 (the solution vector of :2268 lands in these arrays)
         const size_t n = (size_t)ny * nbin * numinterfaces;
@@ -311,8 +296,8 @@ int hx_internal_fband_matrix_iso(hx_context* ctx, const int* skip, double* F_dow
     return 0;
 }
 
-int hx_internal_fband_matrix_noniso(
-    hx_context* ctx, const int* skip, double* F_down_wg, double* F_up_wg, double* Fc_down_wg, double* Fc_up_wg,
+int hx_fband_matrix_noniso(
+    hx_context* ctx, double* F_down_wg, double* F_up_wg, double* Fc_down_wg, double* Fc_up_wg,
     const double* F_dir_wg, const double* Fc_dir_wg, const double* planckband_lay,
     const double* planckband_int, const double* w_0_upper, const double* w_0_lower,
     const double* delta_tau_wg_upper, const double* delta_tau_wg_lower,
@@ -332,10 +317,10 @@ int hx_internal_fband_matrix_noniso(
                       N_upper, N_lower, P_upper, P_lower, G_plus_upper, G_plus_lower, G_minus_upper,
                       G_minus_lower, g_0_tot_lay, g_0_tot_int, trans_wg_upper, trans_wg_lower,
                       alpha, beta, source_term_down, source_term_up, c_prime, d_prime};
-    (skip ? k_fband_matrix_noniso<true> : k_fband_matrix_noniso<false>)<<<hx_cdiv((long long)ny * nbin, 256), 256, 0, ctx->stream>>>(
+    k_fband_matrix_noniso<<<hx_cdiv((long long)ny * nbin, 256), 256, 0, ctx->stream>>>(
         F_down_wg, F_up_wg, Fc_down_wg, Fc_up_wg, F_dir_wg, Fc_dir_wg, planckband_lay, planckband_int,
         q, scat_trigger, surf_albedo, g_0, Rstar, a, numinterfaces, nbin, f_factor, mu_star, ny, epsi,
-        delta_tau_limit, dir_beam, clouds, scat_corr, i2s_transition, skip);
+        delta_tau_limit, dir_beam, clouds, scat_corr, i2s_transition);
     HX_LAUNCH_CHECK(ctx);
     if (debug == 1) {  // kernels.cu:2268, :2329, :2351, :2397, :2418
         const size_t nc = (size_t)ny * nbin;
@@ -346,47 +331,6 @@ int hx_internal_fband_matrix_noniso(
         if (rc) return rc;
     }
     return 0;
-}
-
-int hx_fband_matrix_iso(hx_context* ctx, double* F_down_wg, double* F_up_wg, const double* F_dir_wg,
-                        const double* planckband_lay, const double* w_0, const double* M_term,
-                        const double* N_term, const double* P_term, const double* G_plus,
-                        const double* G_minus, const double* g_0_tot_lay, double* alpha, double* beta,
-                        double* source_term_down, double* source_term_up, double* c_prime,
-                        double* d_prime, const int* scat_trigger, const double* trans_wg,
-                        const double* surf_albedo, double g_0, int singlewalk, double Rstar, double a,
-                        int numinterfaces, int nbin, double f_factor, double mu_star, int ny,
-                        double epsi, int dir_beam, int clouds, int scat_corr, int debug,
-                        double i2s_transition) {
-    return hx_internal_fband_matrix_iso(ctx, nullptr, F_down_wg, F_up_wg, F_dir_wg, planckband_lay, w_0, M_term, N_term,
-                                        P_term, G_plus, G_minus, g_0_tot_lay, alpha, beta, source_term_down,
-                                        source_term_up, c_prime, d_prime, scat_trigger, trans_wg, surf_albedo, g_0,
-                                        singlewalk, Rstar, a, numinterfaces, nbin, f_factor, mu_star, ny, epsi,
-                                        dir_beam, clouds, scat_corr, debug, i2s_transition);
-}
-
-int hx_fband_matrix_noniso(
-    hx_context* ctx, double* F_down_wg, double* F_up_wg, double* Fc_down_wg, double* Fc_up_wg,
-    const double* F_dir_wg, const double* Fc_dir_wg, const double* planckband_lay,
-    const double* planckband_int, const double* w_0_upper, const double* w_0_lower,
-    const double* delta_tau_wg_upper, const double* delta_tau_wg_lower,
-    const double* delta_tau_all_clouds_upper, const double* delta_tau_all_clouds_lower,
-    const double* M_upper, const double* M_lower, const double* N_upper, const double* N_lower,
-    const double* P_upper, const double* P_lower, const double* G_plus_upper,
-    const double* G_plus_lower, const double* G_minus_upper, const double* G_minus_lower,
-    const double* g_0_tot_lay, const double* g_0_tot_int, double* alpha, double* beta,
-    double* source_term_down, double* source_term_up, double* c_prime, double* d_prime,
-    const int* scat_trigger, const double* trans_wg_upper, const double* trans_wg_lower,
-    const double* surf_albedo, double g_0, int singlewalk, double Rstar, double a, int numinterfaces,
-    int nbin, double f_factor, double mu_star, int ny, double epsi, double delta_tau_limit,
-    int dir_beam, int clouds, int scat_corr, int debug, double i2s_transition) {
-    return hx_internal_fband_matrix_noniso(
-        ctx, nullptr, F_down_wg, F_up_wg, Fc_down_wg, Fc_up_wg, F_dir_wg, Fc_dir_wg, planckband_lay, planckband_int,
-        w_0_upper, w_0_lower, delta_tau_wg_upper, delta_tau_wg_lower, delta_tau_all_clouds_upper,
-        delta_tau_all_clouds_lower, M_upper, M_lower, N_upper, N_lower, P_upper, P_lower, G_plus_upper, G_plus_lower,
-        G_minus_upper, G_minus_lower, g_0_tot_lay, g_0_tot_int, alpha, beta, source_term_down, source_term_up, c_prime,
-        d_prime, scat_trigger, trans_wg_upper, trans_wg_lower, surf_albedo, g_0, singlewalk, Rstar, a, numinterfaces,
-        nbin, f_factor, mu_star, ny, epsi, delta_tau_limit, dir_beam, clouds, scat_corr, debug, i2s_transition);
 }
 
 }  // extern "C"

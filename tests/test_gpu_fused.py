@@ -375,6 +375,20 @@ def test_fused_matrix_method_refuses_a_black_surface(ctx):
         batch_from_case(ctx, c0)
 
 
+@pytest.mark.parametrize("method", ["matrix", "iteration"])
+def test_fused_refuses_the_retired_matrix_knob(ctx, monkeypatch, method):
+    """HELIOS_RT_MATRIX=stage chose the per-stage matrix solver inside the loop; that path is retired, and the knob is refused
+    for every batch (read per batch), so that an old A/B recipe cannot silently time the direct solve"""
+    from helios_amd import _lib
+    from helios_amd.rt import batch_from_case
+    c0 = cases.make_case(nbin=5, nlayer=6)
+    c0.flux_calc_method = method
+    monkeypatch.setenv("HELIOS_RT_MATRIX", "stage")
+    with pytest.raises(_lib.HeliosHipError) as e:
+        batch_from_case(ctx, c0)
+    assert "HELIOS_RT_MATRIX" in str(e.value) and "stage" in str(e.value)
+
+
 def test_fused_stops_at_convergence(ctx, port):
     """a column whose every layer satisfies the criterion is frozen on the device exactly where the
     reference's loop would exit (computation.py:938), however late the host looks"""

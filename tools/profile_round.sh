@@ -39,8 +39,7 @@ stats c5 --steps 20 --warmup 10
 python3 bench.py --workload c2matrix --steps 100 --warmup 20 --full --no-cpu-baseline --secondary none --full-line > $O/c2matrix_bench.json 2>> $O/bench.err
 stats c2matrix --steps 50 --warmup 10
 { for pass in 1 2; do
-  echo "# three scans inside k_rt_flux<.., true> (default)"; python3 tools/time_matrix_method.py 10000 100 2>/dev/null | grep MATRIX_METHOD
-  echo "# per-stage kernels (HELIOS_RT_MATRIX=stage)"; HELIOS_RT_MATRIX=stage python3 tools/time_matrix_method.py 10000 100 2>/dev/null | grep MATRIX_METHOD
+  echo "# three scans inside k_rt_flux<.., true>"; python3 tools/time_matrix_method.py 10000 100 2>/dev/null | grep MATRIX_METHOD
 done; } > $O/matrix_method_timing.txt 2>&1
 python3 tools/whole_run_timeline.py --out $O/whole_run_timeline.json > $O/timeline.log 2>&1
 python3 bench.py --workload c1 --steps 500 --full --no-cpu-baseline --full-line > $O/c1_bench.json 2>> $O/bench.err
