@@ -407,19 +407,26 @@ class Compute(object):
             quant.dev_F_add_heat_lay.set(np.asarray(quant.F_add_heat_lay, np.float64))
             quant.dev_F_add_heat_sum.set(np.asarray(quant.F_add_heat_sum, np.float64))
 
-    def _fused_supported(self, quant):
+    def _why_not_fused(self, quant):
+        """why this configuration lies outside the device-resident loop, or None: a pure predicate (a sweep quotes the
+        reason when it refuses the configuration; a single run prints it when it takes the per-stage kernels)"""
         # isothermal layers halve the segments per layer: 2048 of them fit the sweeps' tiles (32 rows x 64 lanes)
         # (`flux calculation method = matrix` runs in the same device-resident loop: hx_rt_flags.matrix; any number of
         # absorbers: the species loop on chip takes them in blocks of 48, csrc/rt_fused.hip refresh_species)
-        why = None
         if quant.flux_calc_method not in ("iteration", "matrix"):
-            why = "flux calculation method %r" % (quant.flux_calc_method,)
-        elif _i(quant.nlayer) > (2048 if quant.iso == 1 else 1024):
-            why = "%d layers (the sweeps' tiles hold 1024, 2048 isothermal ones)" % _i(quant.nlayer)
-        if why is not None and self.use_fused and not getattr(self, "_told_stagewise", False):
+            return "flux calculation method %r" % (quant.flux_calc_method,)
+        if _i(quant.nlayer) > (2048 if quant.iso == 1 else 1024):
+            return "%d layers (the sweeps' tiles hold 1024, 2048 isothermal ones)" % _i(quant.nlayer)
+        return None
+
+    def _fused_supported(self, quant):
+        """the single run's question: device-resident loop or per-stage kernels?  Says once per reason that it falls back"""
+        why = self._why_not_fused(quant)
+        told = self.__dict__.setdefault("_told_stagewise", set())
+        if why is not None and self.use_fused and why not in told:
             # not silent: the same kernels' per-stage entry points, every array through HBM at every stage -- measured
             # 5-10 times the device-resident loop's time per iteration (DESIGN.md section 6)
-            self._told_stagewise = True
+            told.add(why)
             print("\nhelios_amd: " + why + " -- outside the device-resident loop's limits; this run uses the per-stage "
                   "kernels (still on the GPU, same results, about 5-10 times slower per iteration).")
         return self.use_fused and why is None
@@ -489,6 +496,14 @@ class Compute(object):
                         raise ValueError("make_rt_batch: species %r is FastChem-tabulated in column 0 but not in column %d; "
                                          "columns of one batch share the species list and the kind of their mixing ratios"
                                          % (getattr(sp, "name", s), c))
+        else:
+            # likewise before any device call: the premixed tables of one batch share their grid (the sweep's batch signature
+            # keeps tables sampled differently apart; a caller with Stores of its own is told here)
+            for c, qc in enumerate(quants):
+                for n in ("opac_k", "opac_scat_cross", "opac_meanmass"):
+                    if np.size(getattr(qc, n)) != np.size(getattr(q, n)):
+                        raise ValueError("make_rt_batch: %s of column %d has %d entries, column 0's has %d; the tables of one "
+                                         "batch share their grid" % (n, c, np.size(getattr(qc, n)), np.size(getattr(q, n))))
         rt = RTBatch(self._ctx_of(q), _i(q.nbin), _i(q.ny), _i(q.nlayer), len(quants), _i(q.ntemp), _i(q.npress),
                      _i(q.plancktable_dim), _i(q.plancktable_step), self._rt_flags(q),
                      [self._rt_column(c) for c in quants], nspecies=nspecies)
@@ -524,7 +539,16 @@ class Compute(object):
                     for c, qc in enumerate(quants):
                         rt.set_column_vmr_table(c, s, np.asarray(qc.species_list[s].vmr_pretab, np.float64).reshape(-1))
         else:
+            # every distinct premixed table of the batch goes to the device once (the Stores of a sweep that name the same
+            # file hold the same array objects, sweep._prepare_column), and every column reads its own set; a batch with one
+            # table makes the calls it always made
             rt.set_premixed_tables(q.opac_k, q.opac_scat_cross, q.opac_meanmass)
+            index = {id(q.opac_k): 0}
+            for c, qc in enumerate(quants):
+                if id(qc.opac_k) not in index:
+                    index[id(qc.opac_k)] = rt.add_premixed_tables(qc.opac_k, qc.opac_scat_cross, qc.opac_meanmass)
+                if index[id(qc.opac_k)] != 0:
+                    rt.set_column_table(c, index[id(qc.opac_k)])
         if self._kappa_from_table(q):
             rt.set_kappa_table(q.entr_temp, q.entr_press, q.entr_kappa, q.entr_c_p)
         for c, qc in enumerate(quants):

@@ -86,6 +86,7 @@ __global__ void __launch_bounds__(64 * COEF_TPB) HX_COEF_KERNEL(KArgs a HX_PLANE
             // premixed k-table look-up done while staging (kernels.cu:561-608): the opacity arrays of
             // the reference are not materialised on this path (hx_rt_get rebuilds them on demand)
             const size_t sp = nc, st = nc * a.npress;
+            const double* ktable = a.coltab[col].k;   // the k-table of this column's set: col is uniform, one scalar load
             for (int pass = 0; pass < (a.iso ? 1 : 2); pass++) {
                 const int nlev = pass == 0 ? a.L : a.I;
                 const TPIndex* tp = (pass == 0 ? a.tp_lay : a.tp_int) + (size_t)col * a.I;
@@ -103,8 +104,8 @@ __global__ void __launch_bounds__(64 * COEF_TPB) HX_COEF_KERNEL(KArgs a HX_PLANE
                     knext = tp[min(lev + 1, nlev - 1)];
                     if (cq >= 0) {
                         if (k.tdown != ktd || k.tup != ktu || k.pdown != kpd || k.pup != kpu) {
-                            const double* t0 = a.ktable + (size_t)cq + st * k.tdown;
-                            const double* t1 = a.ktable + (size_t)cq + st * k.tup;
+                            const double* t0 = ktable + (size_t)cq + st * k.tdown;
+                            const double* t1 = ktable + (size_t)cq + st * k.tup;
                             c00 = t0[sp * k.pdown];
                             c01 = t0[sp * k.pup];
                             c10 = t1[sp * k.pdown];

@@ -35,6 +35,13 @@ struct Species {
     bool absorbing = false, scattering = false;
 };
 
+// One premixed table set on the device: k-table [ntemp*npress*nbin*ny], weighted Rayleigh cross-sections [ntemp*npress*nbin],
+// mean molecular mass [ntemp*npress].  Also the record the kernels read: hx_rt::coltab holds one per COLUMN, the bases of that
+// column's set (col is uniform per workgroup, so the record arrives by one scalar load).
+struct TableSet {
+    const double *k, *scat_cross, *meanmass;
+};
+
 struct ProfileEntry {
     std::string name;
     hipEvent_t e0, e1;
@@ -69,7 +76,12 @@ struct hx_rt {
     // shared device arrays
     double *interwave = nullptr, *deltawave = nullptr, *wave = nullptr, *gauss_y = nullptr,
            *gauss_w = nullptr, *ktemp = nullptr, *kpress = nullptr;
-    double *opac_k = nullptr, *opac_scat_cross = nullptr, *opac_meanmass = nullptr;
+    // premixed table sets (hx_rt_set_premixed_tables fills set 0, hx_rt_add_premixed_tables appends): all on the batch's grid
+    std::vector<hx::TableSet> tables;
+    std::vector<int> col_table;      // [C] index of every column's set (hx_rt_set_column_table), default 0
+    hx::TableSet* coltab = nullptr;  // device [C]: the column-to-table map as the bases of each column's set -- the kernels
+                                     // read it, so assigning a set changes no kernel argument and no captured graph
+    hx::TableSet* coltab_ref = nullptr;  // device [C]: the set each column's last (fused) refresh read, kept with T_lay_ref
     double* planck_grid = nullptr;  // [(dim+1) * X]; row dim = stellar row of column 0
     std::vector<hx::Species> species;
     void* species_dev = nullptr;   // SpeciesDev [nspecies]: what the batched mixing kernels read (rt_species.h)

@@ -184,7 +184,7 @@ KArgs make_args(hx_rt* rt) {
     a.F_up_tot = rt->F_up_tot; a.F_down_tot = rt->F_down_tot; a.F_net = rt->F_net;
     a.coef_col = g.coef_elems_per_col; a.flux_col = g.flux_elems_per_col;
     a.done = rt->done;
-    a.ktable = rt->opac_k; a.crosstable = rt->opac_scat_cross; a.ktemp = rt->ktemp; a.kpress = rt->kpress;
+    a.coltab = rt->coltab; a.ktemp = rt->ktemp; a.kpress = rt->kpress;
     a.tp_lay = (const TPIndex*)rt->tp_lay; a.tp_int = (const TPIndex*)rt->tp_int;
     a.ntemp = rt->d.ntemp; a.npress = rt->d.npress; a.from_table = 0;
     a.iter_dev = rt->iter_dev;
@@ -437,6 +437,7 @@ static int rt_create_into(hx_rt* rt, hx_context* ctx, const hx_rt_dims* dims, co
     rt->H = flags->iso ? rt->L : 2 * rt->L;
     rt->C = dims->ncol;
     rt->have_albedo.assign(dims->ncol, 0);
+    rt->col_table.assign(dims->ncol, 0);
     RT_ALLOC(rt->iter_dev, 2);
     // computation.py:531-537: 3*scat+1 sweeps per iteration, 1000*scat+1 in the post-processing run type
     rt->nsweep = (flags->singlewalk ? 1000 : 3) * (flags->scat ? 1 : 0) + 1;
@@ -498,6 +499,8 @@ static int rt_create_into(hx_rt* rt, hx_context* ctx, const hx_rt_dims* dims, co
     RT_ALLOC(rt->ktemp, dims->ntemp); RT_ALLOC(rt->kpress, dims->npress);
     RT_ALLOC(rt->planck_grid, (size_t)(dims->plancktable_dim + 1) * X);
     RT_ALLOC(rt->colpar, C);
+    RT_ALLOC(rt->coltab, C);
+    RT_ALLOC(rt->coltab_ref, C);
     RT_ALLOC(rt->p_lay, C * L); RT_ALLOC(rt->p_int, C * I); RT_ALLOC(rt->dcol_u, C * L);
     RT_ALLOC(rt->dcol_l, C * L); RT_ALLOC(rt->T_lay, C * (L + 1)); RT_ALLOC(rt->T_int, C * I);
     RT_ALLOC(rt->surf_albedo, C * X); RT_ALLOC(rt->starflux, C * X); RT_ALLOC(rt->Bstar, C * X);
@@ -593,23 +596,92 @@ int hx_rt_set_grid(hx_rt* rt, const double* opac_interwave, const double* opac_d
     return rc;
 }
 
+static int for_cols(hx_rt* rt, int col, int* c0, int* c1);
+
+// the device's column-to-table map: the bases of the sets of columns [c0, c1)
+static int upload_coltab(hx_rt* rt, int c0, int c1) {
+    std::vector<TableSet> m(c1 - c0);
+    for (int c = c0; c < c1; c++) m[c - c0] = rt->tables[rt->col_table[c]];
+    return h2d(rt, rt->coltab + c0, m.data(), m.size() * sizeof(TableSet));
+}
+
+// one more premixed table set on the batch's grid, zero-filled
+static int new_table_set(hx_rt* rt) {
+    const size_t ntp = (size_t)rt->d.ntemp * rt->d.npress;
+    const size_t n[3] = {ntp * rt->X * rt->Y, ntp * rt->X, ntp};
+    double* p[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < 3; i++)
+        if (const int rc = dev_alloc(rt, &p[i], n[i])) {   // (what was allocated stays in rt->allocs: hx_rt_destroy frees it)
+            const std::string why = rt->ctx->err;
+            return hx_fail(rt->ctx, rc, "premixed table set %d: %zu sets of %zu bytes each were asked for on this "
+                           "device, the last one did not fit (%s)", (int)rt->tables.size(), rt->tables.size() + 1,
+                           (n[0] + n[1] + n[2]) * 8, why.c_str());
+        }
+    rt->tables.push_back({p[0], p[1], p[2]});
+    // (a further set changes no column's assignment: the map is written when the first set arrives and per assignment)
+    return rt->tables.size() == 1 ? upload_coltab(rt, 0, rt->C) : 0;
+}
+
 int hx_rt_set_premixed_tables(hx_rt* rt, const double* opac_k, const double* opac_scat_cross,
                               const double* opac_meanmass) {
     if (!rt) return HX_E_ARG;  // e.g. a call after hx_rt_destroy
     rt_touch(rt);            // a captured iteration graph holds the arguments of before this call
     HX_REQUIRE(rt->ctx, rt->d.nspecies == 0, HX_E_STATE, "object was created for on-the-fly mixing");
     const size_t ntp = (size_t)rt->d.ntemp * rt->d.npress;
-    if (!rt->opac_k) {
-        RT_ALLOC(rt->opac_k, ntp * rt->X * rt->Y);
-        RT_ALLOC(rt->opac_scat_cross, ntp * rt->X);
-        RT_ALLOC(rt->opac_meanmass, ntp);
+    if (rt->tables.empty()) {
+        int rc0 = new_table_set(rt);
+        if (rc0) return rc0;
     }
+    const TableSet& t = rt->tables[0];
     int rc = 0;
-    rc |= h2d(rt, rt->opac_k, opac_k, ntp * rt->X * rt->Y * 8);
-    rc |= h2d(rt, rt->opac_scat_cross, opac_scat_cross, ntp * rt->X * 8);
-    rc |= h2d(rt, rt->opac_meanmass, opac_meanmass, ntp * 8);
+    rc |= h2d(rt, (void*)t.k, opac_k, ntp * rt->X * rt->Y * 8);
+    rc |= h2d(rt, (void*)t.scat_cross, opac_scat_cross, ntp * rt->X * 8);
+    rc |= h2d(rt, (void*)t.meanmass, opac_meanmass, ntp * 8);
     rt->have_tables = rc == 0;
     return rc;
+}
+
+int hx_rt_add_premixed_tables(hx_rt* rt, const double* opac_k, const double* opac_scat_cross, const double* opac_meanmass,
+                              int* out_index) {
+    if (!rt) return HX_E_ARG;  // e.g. a call after hx_rt_destroy
+    const int ntab = (int)rt->tables.size();
+    if (rt->d.nspecies != 0)
+        return hx_fail(rt->ctx, HX_E_STATE, "hx_rt_add_premixed_tables: object was created for on-the-fly mixing (%d species): "
+                       "it holds 0 premixed table sets and takes none", rt->d.nspecies);
+    if (rt->refreshed)   // (the sets of a batch are complete before its first refresh: what a refresh read stays what it reads)
+        return hx_fail(rt->ctx, HX_E_STATE, "hx_rt_add_premixed_tables: table set %d comes after the first refresh; the batch "
+                       "keeps its %d set(s)", ntab, ntab);
+    HX_REQUIRE(rt->ctx, opac_k && opac_scat_cross && opac_meanmass && out_index, HX_E_ARG, "null table");
+    rt_touch(rt);
+    int rc = new_table_set(rt);
+    if (rc) return rc;
+    const size_t ntp = (size_t)rt->d.ntemp * rt->d.npress;
+    const TableSet& t = rt->tables[ntab];
+    rc |= h2d(rt, (void*)t.k, opac_k, ntp * rt->X * rt->Y * 8);
+    rc |= h2d(rt, (void*)t.scat_cross, opac_scat_cross, ntp * rt->X * 8);
+    rc |= h2d(rt, (void*)t.meanmass, opac_meanmass, ntp * 8);
+    if (ntab == 0) rt->have_tables = rc == 0;
+    *out_index = ntab;
+    return rc;
+}
+
+// The column reads set `index` from its next refresh on (col < 0: every column).  The map is device data the kernels read: no
+// kernel argument changes, so the captured graphs stay (no rt_touch of the graph generation).  Until that refresh the
+// column's coefficients, and the opacities hx_rt_get rebuilds on demand (coltab_ref), stay the previous set's.
+int hx_rt_set_column_table(hx_rt* rt, int col, int index) {
+    if (!rt) return HX_E_ARG;  // e.g. a call after hx_rt_destroy
+    const int ntab = (int)rt->tables.size();
+    if (rt->d.nspecies != 0)
+        return hx_fail(rt->ctx, HX_E_STATE, "hx_rt_set_column_table: object was created for on-the-fly mixing (%d species): "
+                       "table index %d, but it holds 0 premixed table sets", rt->d.nspecies, index);
+    if (index < 0 || index >= ntab)
+        return hx_fail(rt->ctx, HX_E_ARG, "hx_rt_set_column_table: table index %d out of range, the batch holds %d premixed "
+                       "table set(s)", index, ntab);
+    int c0, c1, rc = for_cols(rt, col, &c0, &c1);
+    if (rc) return rc;
+    rt->solve_serial++;
+    for (int c = c0; c < c1; c++) rt->col_table[c] = index;
+    return upload_coltab(rt, c0, c1);
 }
 
 int hx_rt_set_species(hx_rt* rt, int s, const double* opacity_pretab, const double* scat_cross,
@@ -686,19 +758,17 @@ int hx_rt_set_premixed_separable(hx_rt* rt, const double* kxy, const double* ftp
     HX_REQUIRE(rt->ctx, rt->d.nspecies == 0, HX_E_STATE, "object was created for on-the-fly mixing");
     HX_REQUIRE(rt->ctx, kxy && ftp && opac_scat_cross && opac_meanmass, HX_E_ARG, "null table");
     const size_t ntp = (size_t)rt->d.ntemp * rt->d.npress;
-    if (!rt->opac_k) {
-        RT_ALLOC(rt->opac_k, ntp * rt->X * rt->Y);
-        RT_ALLOC(rt->opac_scat_cross, ntp * rt->X);
-        RT_ALLOC(rt->opac_meanmass, ntp);
+    if (rt->tables.empty()) {
+        int rc0 = new_table_set(rt);
+        if (rc0) return rc0;
     }
-    int rc = fill_outer(rt, rt->opac_k, kxy, ftp);
-    if (!rc) rc = h2d(rt, rt->opac_scat_cross, opac_scat_cross, ntp * rt->X * 8);
-    if (!rc) rc = h2d(rt, rt->opac_meanmass, opac_meanmass, ntp * 8);
+    const TableSet& t = rt->tables[0];
+    int rc = fill_outer(rt, (double*)t.k, kxy, ftp);
+    if (!rc) rc = h2d(rt, (void*)t.scat_cross, opac_scat_cross, ntp * rt->X * 8);
+    if (!rc) rc = h2d(rt, (void*)t.meanmass, opac_meanmass, ntp * 8);
     rt->have_tables = rc == 0;
     return rc;
 }
-
-static int for_cols(hx_rt* rt, int col, int* c0, int* c1);
 
 // calculate_vmr_for_all_species on the device (host_functions.py:874-910): a species whose mixing ratio is tabulated on the
 // opacity tables' (T, P) grid -- vmr_pretab[p + npress * t], what read.py keeps per FastChem species -- follows the
@@ -999,12 +1069,12 @@ int hx_rt_refresh(hx_rt* rt) {
     if (rt->d.nspecies == 0) {
         k_rt_tp_index<<<dim3(hx_cdiv(I, 64), C), 64, 0, ctx->stream>>>(a, (TPIndex*)rt->tp_lay, (TPIndex*)rt->tp_int);
         k_rt_scat_interp<<<dim3(hx_cdiv(X, 256), I, C), 256, 0, ctx->stream>>>(a, rt->scat_cross_lay, rt->scat_cross_int);
-        k_rt_mmm_table<<<dim3(hx_cdiv(I, 64), C), 64, 0, ctx->stream>>>(a, rt->opac_meanmass, rt->mmm_lay, rt->mmm_int);
+        k_rt_mmm_table<<<dim3(hx_cdiv(I, 64), C), 64, 0, ctx->stream>>>(a, rt->mmm_lay, rt->mmm_int);
         HX_LAUNCH_CHECK(ctx);
         if (fused_lookup) {
             // opacities are interpolated inside k_rt_coef; remember the temperatures this refresh used, so that
             // the arrays can be rebuilt on demand
-            k_rt_keep_ref_T<<<dim3(hx_cdiv(I + 1, 64), C), 64, 0, ctx->stream>>>(a, rt->T_lay_ref, rt->T_int_ref);
+            k_rt_keep_ref_T<<<dim3(hx_cdiv(I + 1, 64), C), 64, 0, ctx->stream>>>(a, rt->T_lay_ref, rt->T_int_ref, rt->coltab_ref);
         } else {
             ProfScope ps(rt, "opac_interpol");
             const int chunks = (int)std::min<long long>(hx_cdiv((long long)nc, 256), 1024);
@@ -1246,7 +1316,7 @@ int hx_rt_conv_adjust(hx_rt* rt, int itervalue) {
         if (rt->d.nspecies == 0) {
             for (int c = 0; c < rt->C; c++) {
                 int rc = hx_meanmolmass_interpol(ctx, rt->T_lay + (size_t)c * (rt->L + 1), rt->ktemp,
-                                                 rt->mmm_lay + (size_t)c * rt->I, rt->opac_meanmass,
+                                                 rt->mmm_lay + (size_t)c * rt->I, rt->tables[rt->col_table[c]].meanmass,
                                                  rt->p_lay + (size_t)c * rt->L, rt->kpress, rt->d.npress,
                                                  rt->d.ntemp, rt->L);
                 if (rc) return rc;
@@ -1521,13 +1591,18 @@ static int materialize_opac(hx_rt* rt) {
     if (!rt->opac_stale) return 0;
     hx_context* ctx = rt->ctx;
     const size_t nc = (size_t)rt->X * rt->Y, wgI = nc * rt->I, bandI = (size_t)rt->X * rt->I;
+    // the set each column's last refresh read (a set assigned since then is in effect from the NEXT refresh)
+    std::vector<TableSet> used(rt->C);
+    int rc0 = hx_d2h(ctx, used.data(), rt->coltab_ref, used.size() * sizeof(TableSet));
+    if (rc0) return rc0;
     for (int c = 0; c < rt->C; c++) {
+        const TableSet& t = used[c];
         int rc = hx_opac_interpol(ctx, rt->T_lay_ref + (size_t)c * (rt->L + 1), rt->ktemp, rt->p_lay + (size_t)c * rt->L,
-                                  rt->kpress, rt->opac_k, rt->opac_wg_lay + c * wgI, rt->opac_scat_cross,
+                                  rt->kpress, t.k, rt->opac_wg_lay + c * wgI, t.scat_cross,
                                   rt->scat_cross_lay + c * bandI, rt->d.npress, rt->d.ntemp, rt->Y, rt->X, rt->L);
         if (rc) return rc;
         rc = hx_opac_interpol(ctx, rt->T_int_ref + (size_t)c * rt->I, rt->ktemp, rt->p_int + (size_t)c * rt->I,
-                              rt->kpress, rt->opac_k, rt->opac_wg_int + c * wgI, rt->opac_scat_cross,
+                              rt->kpress, t.k, rt->opac_wg_int + c * wgI, t.scat_cross,
                               rt->scat_cross_int + c * bandI, rt->d.npress, rt->d.ntemp, rt->Y, rt->X, rt->I);
         if (rc) return rc;
     }
@@ -1551,7 +1626,19 @@ int hx_rt_get(hx_rt* rt, int col, const char* name, void* out, size_t out_bytes)
         memcpy(out, v, sizeof(v));
         return 0;
     }
+    if (strcmp(name, "premixed_table_count") == 0) {   // host-side, any column (-1): int32, the table sets the batch holds
+        HX_REQUIRE(rt->ctx, out_bytes == sizeof(int32_t), HX_E_ARG, "premixed_table_count is one int32");
+        const int32_t v = (int32_t)rt->tables.size();
+        memcpy(out, &v, sizeof(v));
+        return 0;
+    }
     HX_REQUIRE(rt->ctx, col >= 0 && col < rt->C, HX_E_ARG, "column index out of range");
+    if (strcmp(name, "premixed_table") == 0) {   // host-side: int32, the index of the column's table set
+        HX_REQUIRE(rt->ctx, out_bytes == sizeof(int32_t), HX_E_ARG, "premixed_table is one int32");
+        const int32_t v = rt->col_table[col];
+        memcpy(out, &v, sizeof(v));
+        return 0;
+    }
     if (strcmp(name, "coef_planes") == 0) {   // the column's coefficient planes as k_rt_coef wrote them (after a refresh)
         const void* planes = rt->coef32 ? (const void*)rt->coef32 : (const void*)rt->coef;
         const size_t bytes = rt->g.coef_elems_per_col * rt->coef_bytes;

@@ -47,7 +47,8 @@ struct KArgs {
     size_t coef_col, flux_col;  // per-column strides (elements) of coef / Utile / Dtile
     const int* done;
     // premixed table look-up fused into the coefficient kernel
-    const double *ktable, *crosstable, *ktemp, *kpress;
+    const TableSet* coltab;    // [C] bases of every column's premixed table set (k_rt_coef reads its k-table through it)
+    const double *ktemp, *kpress;
     const TPIndex *tp_lay, *tp_int;  // [C][I] fractional table indices of the levels
     int ntemp, npress, from_table;
     unsigned long long* diag;  // hx_context::diag when the batch runs with debug = 1, else nullptr
@@ -968,11 +969,12 @@ __global__ void __launch_bounds__(256) k_rt_scat_interp(KArgs a, double* scat_la
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= a.X || a.done[col]) return;
     const size_t cp = a.X, ct = (size_t)a.X * a.npress, bandI = (size_t)a.X * a.I;
+    const double* crosstable = a.coltab[col].scat_cross;   // this column's table set
     for (int pass = 0; pass < 2; pass++) {
         if (pass == 0 && lev >= a.L) continue;
         const TPIndex k = (pass == 0 ? a.tp_lay : a.tp_int)[(size_t)col * a.I + lev];
-        const double* t0 = a.crosstable + x + ct * k.tdown;
-        const double* t1 = a.crosstable + x + ct * k.tup;
+        const double* t0 = crosstable + x + ct * k.tdown;
+        const double* t1 = crosstable + x + ct * k.tup;
         (pass == 0 ? scat_lay : scat_int)[col * bandI + x + (size_t)a.X * lev] =
             blend_tp(t0[cp * k.pdown], t0[cp * k.pup], t1[cp * k.pdown], t1[cp * k.pup], k, false);
     }
@@ -980,10 +982,11 @@ __global__ void __launch_bounds__(256) k_rt_scat_interp(KArgs a, double* scat_la
 
 // ---- per refresh, all columns at once (a column whose loop has ended is skipped on the device) -------------------
 // mean molecular mass of a premixed table at every level (meanmolmass_interpol, kernels.cu:649-699) from the table
-// indices k_rt_tp_index left behind
-__global__ void k_rt_mmm_table(KArgs a, const double* __restrict__ table, double* mmm_lay, double* mmm_int) {
+// indices k_rt_tp_index left behind, in the table of the column's own set
+__global__ void k_rt_mmm_table(KArgs a, double* mmm_lay, double* mmm_int) {
     const int col = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.I || a.done[col]) return;
+    const double* __restrict__ table = a.coltab[col].meanmass;
     for (int pass = 0; pass < 2; pass++) {
         if (pass == 0 && i >= a.L) continue;
         const TPIndex k = (pass == 0 ? a.tp_lay : a.tp_int)[(size_t)col * a.I + i];
@@ -998,13 +1001,14 @@ __global__ void __launch_bounds__(256) k_rt_opac_table(KArgs a, double* opac_lay
     const int col = blockIdx.z, lev = blockIdx.y;
     if (a.done[col]) return;
     const size_t nc = (size_t)a.Y * a.X, sp = nc, st = nc * a.npress, wgI = nc * a.I;
+    const double* ktable = a.coltab[col].k;   // this column's table set
     for (int pass = 0; pass < 2; pass++) {
         if (pass == 0 && lev >= a.L) continue;
         const TPIndex k = (pass == 0 ? a.tp_lay : a.tp_int)[(size_t)col * a.I + lev];
         double* out = (pass == 0 ? opac_lay : opac_int) + col * wgI + nc * lev;
         for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < nc; c += (size_t)gridDim.x * blockDim.x)
-            out[c] = blend_tp(a.ktable[c + sp * k.pdown + st * k.tdown], a.ktable[c + sp * k.pup + st * k.tdown],
-                              a.ktable[c + sp * k.pdown + st * k.tup], a.ktable[c + sp * k.pup + st * k.tup], k, false);
+            out[c] = blend_tp(ktable[c + sp * k.pdown + st * k.tdown], ktable[c + sp * k.pup + st * k.tdown],
+                              ktable[c + sp * k.pdown + st * k.tup], ktable[c + sp * k.pup + st * k.tup], k, false);
     }
 }
 
@@ -1033,10 +1037,11 @@ __global__ void __launch_bounds__(256) k_rt_total_g0(KArgs a, const double* __re
     g_tot_int[k] = num / (a.scat_cross_int[k] + a.cl_sc_int[k]);
 }
 
-// remember the temperatures a refresh used (opacities are rebuilt from them on demand)
-__global__ void k_rt_keep_ref_T(KArgs a, double* T_lay_ref, double* T_int_ref) {
+// remember the temperatures and the table set a refresh used (opacities are rebuilt from them on demand)
+__global__ void k_rt_keep_ref_T(KArgs a, double* T_lay_ref, double* T_int_ref, TableSet* coltab_ref) {
     const int col = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
     if (a.done[col]) return;  // a finished column keeps the state of its last real refresh
+    if (i == 0) coltab_ref[col] = a.coltab[col];
     if (i <= a.L) T_lay_ref[(size_t)col * (a.L + 1) + i] = a.T_lay[(size_t)col * (a.L + 1) + i];
     if (i < a.I) T_int_ref[(size_t)col * a.I + i] = a.T_int[(size_t)col * a.I + i];
 }

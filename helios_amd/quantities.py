@@ -77,13 +77,16 @@ class Store(object):
             self._ctx = Context(0)   # raises when libhelios_hip.so / a GPU is missing: no CPU fallback
         return self._ctx
 
-    def convert_input_list_to_array(self):
-        """source/quantities.py:366-398"""
+    def as_input_array(self, v):
+        """the form every input array takes (source/quantities.py:366-398): flat, contiguous, in the run's precision"""
+        return np.ascontiguousarray(np.array([] if v is None else v, self.fl_prec).reshape(-1))
+
+    def convert_input_list_to_array(self, skip=()):
+        """source/quantities.py:366-398; `skip`: names that hold arrays of that form already and are shared between Stores
+        (the opacity tables of a sweep), which must not be copied per Store"""
         for n in _INPUT_ARRAYS + _INPUT_ARRAYS_NONISO:
-            v = getattr(self, n)
-            if v is None:
-                v = []
-            setattr(self, n, np.ascontiguousarray(np.array(v, self.fl_prec).reshape(-1)))
+            if n not in skip:
+                setattr(self, n, self.as_input_array(getattr(self, n)))
 
     def dimensions(self):
         """source/quantities.py:400-409"""

@@ -99,6 +99,25 @@ class RTBatch(object):
         self._ck(self._l.hx_rt_set_premixed_tables(self.handle, *[_dp(a) for a in arrs]),
                  "hx_rt_set_premixed_tables")
 
+    def add_premixed_tables(self, opac_k, opac_scat_cross, opac_meanmass):
+        """one more premixed table set on the batch's grid (before the first refresh); returns its index"""
+        arrs = [_f64(a) for a in (opac_k, opac_scat_cross, opac_meanmass)]
+        idx = ctypes.c_int32(-1)
+        self._ck(self._l.hx_rt_add_premixed_tables(self.handle, *[_dp(a) for a in arrs], ctypes.byref(idx)),
+                 "hx_rt_add_premixed_tables")
+        return int(idx.value)
+
+    def set_column_table(self, col, index):
+        """column `col` (< 0: all) reads premixed table set `index` from its next refresh on"""
+        self._ck(self._l.hx_rt_set_column_table(self.handle, int(col), int(index)), "hx_rt_set_column_table")
+
+    def column_table(self, col):
+        """index of the premixed table set column `col` reads"""
+        return int(self.get("premixed_table", col)[0])
+
+    def premixed_table_count(self):
+        return int(self.get("premixed_table_count", -1)[0])
+
     def set_species(self, s, opacity_pretab, scat_cross, weight, is_h2o=0, is_cia=0, in_mu=1):
         p, q = _f64(opacity_pretab), _f64(scat_cross)
         self._ck(self._l.hx_rt_set_species(self.handle, s, _dp(p), _dp(q), float(weight), int(is_h2o),
@@ -218,7 +237,7 @@ class RTBatch(object):
             "delta_z_lay": (L, np.float64), "z_lay": (L, np.float64),
             "F_up_wg": (wg, np.float64), "F_down_wg": (wg, np.float64), "Fc_up_wg": (wg, np.float64),
             "Fc_down_wg": (wg, np.float64), "F_dir_wg": (wg, np.float64), "Fc_dir_wg": (wg, np.float64),
-            "iters_done": (1, np.int32), "done": (1, np.int32), "flux_launch_policy": (2, np.float64), "graph_replays": (3, np.float64), "graph_builds": (2, np.float64),
+            "iters_done": (1, np.int32), "done": (1, np.int32), "premixed_table": (1, np.int32), "premixed_table_count": (1, np.int32), "flux_launch_policy": (2, np.float64), "graph_replays": (3, np.float64), "graph_builds": (2, np.float64),
             "conv_layer": (L + 1, np.int32), "conv_unstable": (L + 1, np.int32), "marked_red": (L + 1, np.int32),
             "kappa_lay": (L, np.float64), "kappa_int": (L + 1, np.float64), "c_p_lay": (L, np.float64),
             "F_smooth_sum": (L, np.float64), "F_add_heat_lay": (L, np.float64), "F_add_heat_sum": (L, np.float64),

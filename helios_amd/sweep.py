@@ -10,7 +10,9 @@ exactly what `RTBatch` keeps per column -- so a sweep is one batch whose kernels
 
 Every column gets the full set of output files under `<output>/<name>_<k>/`, exactly as a single run would write them.
 """
+import hashlib
 import itertools
+import os
 
 import numpy as np
 
@@ -23,10 +25,15 @@ from . import write as write_mod
 
 # options that may vary between the columns of one batch (everything else defines the batch itself)
 # (directory_with_fastchem_files: every column reads its own chemistry -- a sweep over metallicity or C/O -- and keeps its own
-# (T, P) mixing-ratio tables on the device, hx_rt_set_column_vmr_table)
+# (T, P) mixing-ratio tables on the device, hx_rt_set_column_vmr_table; path_to_opacity_file: the same sweep on the premixed
+# path, one premixed k-table file per chemistry -- every distinct table is resident once per GPU and every column reads its
+# own, hx_rt_add_premixed_tables / hx_rt_set_column_table)
 PER_COLUMN_OPTIONS = ("internal_temperature", "f_factor", "stellar_zenith_angle", "surface_albedo", "surface_gravity",
                       "orbital_distance", "radius_planet", "radius_star", "temperature_star",
-                      "radiative_equilibrium_criterion", "directory_with_fastchem_files", "name")
+                      "radiative_equilibrium_criterion", "directory_with_fastchem_files", "path_to_opacity_file", "name")
+
+_TABLE_NAMES = ("opacity_mixing", "opac_k", "opac_scat_cross", "opac_meanmass", "opac_wave", "opac_interwave",
+                "opac_deltawave", "gauss_y", "ktemp", "kpress", "nbin", "ny", "ntemp", "npress")
 
 
 def expand_sweep(spec):
@@ -41,8 +48,21 @@ def expand_sweep(spec):
     return [dict(combo) for combo in itertools.product(*axes)] if axes else [{}]
 
 
+def _table_entry(keeper):
+    """what a table file leaves on the Store that read it, as the entry the Stores of a sweep share: the arrays in the form
+    Store.convert_input_list_to_array gives input arrays, made here ONCE, so that host memory holds each table once and
+    `make_rt_batch` can tell the distinct tables of a batch by the identity of their arrays"""
+    entry = {}
+    for n in _TABLE_NAMES:
+        if hasattr(keeper, n):
+            v = getattr(keeper, n)
+            entry[n] = keeper.as_input_array(v) if isinstance(v, (np.ndarray, list, tuple)) else v
+    return entry
+
+
 def _prepare_column(base_argv, overrides, shared):
-    """the read -> grid -> start-profile part of helios.py:35-83 for one column; tables are read once and shared"""
+    """the read -> grid -> start-profile part of helios.py:35-83 for one column; every distinct table file is read once per
+    process (`shared`, which lives as long as its run_sweep) and its arrays are shared by the Stores that name it"""
     reader = read_mod.Read()
     keeper = quant_mod.Store()
     argv = list(base_argv)
@@ -50,20 +70,29 @@ def _prepare_column(base_argv, overrides, shared):
         argv += ["-" + k, str(v)]
     reader.read_param_file_and_command_line(keeper, reader.cloud, argv)
     reader.check_run_configuration(keeper)
-    if "tables" not in shared:
-        if keeper.opacity_mixing in ("premixed", "synthetic"):
-            reader.load_premixed_opacity_table(keeper)
+    tables = shared.setdefault("tables", {})
+    if keeper.opacity_mixing in ("premixed", "synthetic"):
+        # one entry per table FILE (and what is made of it: "no atmosphere" discards the opacities, read.py:445)
+        if keeper.opacity_mixing == "synthetic" or str(reader.ktable_path) == "synthetic":
+            key = ("synthetic", str(reader.synthetic_spec))
         else:
+            key = (os.path.realpath(str(reader.ktable_path)), int(getattr(keeper, "no_atmo_mode", 0)))
+        if key not in tables:
+            reader.load_premixed_opacity_table(keeper)
+            tables[key] = _table_entry(keeper)
+    else:
+        if "path_to_opacity_file" in overrides:
+            raise ValueError("a sweep over path_to_opacity_file varies the PREMIXED table; with opacity mixing = on-the-fly the "
+                             "option has no meaning (sweep over directory_with_fastchem_files there)")
+        key = "species"
+        if key not in tables:
             reader.read_species_file(keeper)
             reader.read_species_opacities(keeper)
             reader.read_species_scat_cross_sections(keeper)
-        names = ("opacity_mixing", "opac_k", "opac_scat_cross", "opac_meanmass", "opac_wave", "opac_interwave",
-                 "opac_deltawave", "gauss_y", "ktemp", "kpress", "nbin", "ny", "ntemp", "npress")
-        shared["tables"] = {n: getattr(keeper, n) for n in names if hasattr(keeper, n)}
-        shared["species_template"] = keeper.species_list
-    else:
-        for n, v in shared["tables"].items():
-            setattr(keeper, n, v)
+            tables[key] = _table_entry(keeper)
+            shared["species_template"] = keeper.species_list
+    for n, v in tables[key].items():      # (the Store that read the file too: it takes the entry's arrays)
+        setattr(keeper, n, v)
     if keeper.opacity_mixing == "on-the-fly":
         import copy
         keeper.species_list = [copy.copy(sp) for sp in shared["species_template"]]   # tables shared, VMR profiles own
@@ -82,8 +111,20 @@ def _prepare_column(base_argv, overrides, shared):
     add_heat.load_heating_terms_or_not(keeper)
     reader.cloud.cloud_pre_processing(keeper)
     keeper.create_zero_arrays()
-    keeper.convert_input_list_to_array()
+    # the table's arrays are in their final form already and stay ONE per process (_table_entry)
+    keeper.convert_input_list_to_array(skip=[n for n, v in tables[key].items() if isinstance(v, np.ndarray)])
     return keeper, reader
+
+
+def _table_grid_digest(q):
+    """the sampling of the column's opacity table: wavelength bins, Gauss points and the (T, P) nodes.  A batch has ONE grid
+    (hx_rt_set_grid); tables on the same grid may differ from column to column"""
+    h = hashlib.sha1()
+    for n in ("opac_interwave", "gauss_y", "ktemp", "kpress"):
+        v = getattr(q, n, None)
+        h.update(b"-" if v is None else np.ascontiguousarray(np.asarray(v, np.float64)).tobytes())
+        h.update(b"|")
+    return h.hexdigest()
 
 
 def _batch_signature(q):
@@ -93,7 +134,7 @@ def _batch_signature(q):
                  for sp in (getattr(q, "species_list", None) or [])) if str(q.opacity_mixing) == "on-the-fly" else ()
     return (int(q.nbin), int(q.ny), int(q.nlayer), int(q.scat), int(q.dir_beam), int(q.clouds), int(q.scat_corr),
             int(q.smooth), int(q.convection), str(q.opacity_mixing), float(q.g_0), float(q.epsi), str(q.planet_type),
-            int(q.iso), int(q.singlewalk), str(q.flux_calc_method), chem)
+            int(q.iso), int(q.singlewalk), str(q.flux_calc_method), chem, _table_grid_digest(q))
 
 
 def _radiation_loop(computer, quants, rt):
@@ -278,9 +319,11 @@ def _run_columns(base_argv, overrides_list, cols, computer, writer, shared, colu
         fresh.append((q, reader))
     groups = {}
     for q, reader in fresh:
-        if not computer._fused_supported(q):
+        why = computer._why_not_fused(q)
+        if why is not None:
             raise IOError("sweeps run on the fused device path: flux calculation method 'iteration' or 'matrix' and at most 1024 "
-                          "layers (2048 isothermal ones); run this configuration column by column with helios.py")
+                          "layers (2048 isothermal ones); this one has " + why + " -- run this configuration column by column "
+                          "with helios.py")
         groups.setdefault(_batch_signature(q), []).append((q, reader))
     for members in groups.values():
         quants = [q for q, _ in members]

@@ -390,6 +390,21 @@ int hx_rt_set_species_separable(hx_rt* rt, int s, const double* kxy, const doubl
                                 double weight, int is_h2o, int is_cia, int in_mu);
 int hx_rt_set_premixed_separable(hx_rt* rt, const double* kxy, const double* ftp, const double* opac_scat_cross,
                                  const double* opac_meanmass);
+/* Further premixed table sets (a sweep over metallicity or C/O on the premixed path: one k-table file per chemistry).  A batch
+ * holds ntab >= 1 sets -- k-table, weighted Rayleigh cross-sections, mean molecular mass, laid out as for
+ * hx_rt_set_premixed_tables, which fills set 0 -- all on the grid of hx_rt_set_grid; each is resident once, whatever the number
+ * of columns that read it.  hx_rt_add_premixed_tables appends a set and returns its index (the first set of a batch without one
+ * gets index 0); sets are added before the first refresh.  hx_rt_set_column_table assigns a set to a column (col < 0: all
+ * columns; default: set 0), in effect from the column's next refresh; the map is device data, so captured graphs stay valid.
+ * Until that refresh the column's coefficients and what hx_rt_get returns for its opacities and Rayleigh cross-sections stay the
+ * previous set's (a column whose loop has ended is not refreshed again); hx_rt_conv_adjust, which re-evaluates the mean
+ * molecular mass of the current profile itself, reads the set assigned at its call.
+ * hx_rt_get(rt, col, "premixed_table") reads a column's index back, hx_rt_get(rt, -1, "premixed_table_count") the number of
+ * sets (one int32 each).  Errors (index out of range, an on-the-fly object, a set added after the first refresh, no device
+ * memory for a further set) name the index and the count; the batch stays usable and destroyable. */
+int hx_rt_add_premixed_tables(hx_rt* rt, const double* opac_k, const double* opac_scat_cross,
+                              const double* opac_meanmass, int* out_index);
+int hx_rt_set_column_table(hx_rt* rt, int col, int index);
 /* A6 on the device: calculate_vmr_for_all_species + interpolate_grid_to_lay_or_int (source/host_functions.py:874-910).
  * vmr_pretab[p + npress * t] on the opacity tables' (T, P) grid, as source/read.py keeps it per FastChem species
  * (Species.vmr_pretab); the species' profile is then interpolated at every refresh from the device's temperatures,
