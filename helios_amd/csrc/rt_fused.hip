@@ -978,6 +978,29 @@ static int upload_species_table(hx_rt* rt) {
     return rc;
 }
 
+// the species loop of a batch, a refresh or a premix (csrc/premix.hip): one launch per block of MIX_MAX_ABSORBERS absorbers
+extern "C++" int hx::launch_mix_species(hx_context* ctx, MixArgs m, const int* abs_list, int nabs_all) {
+    const long long npair = (long long)m.C * (m.L + m.I) * m.X;
+    if (npair <= 0) return 0;
+    // short runs (about ten points, each folding in every absorber): a wavefront lives for a fraction of a
+    // millisecond, so the last round of workgroups does not leave the chip half empty
+    static const int waves = [] { const char* e = getenv("HELIOS_RT_MIX_WAVES"); return e ? atoi(e) : 256 * 16 * 48; }();
+    const int grid = (int)std::min(npair, (long long)waves);
+    // occupancy experiment (profiles/r05_mix_occupancy.txt): bytes of unused dynamic LDS per wavefront on top of the
+    // kernel's 9.95 KB -- 16 wavefronts share a CU's 160 KB as built, +3.4 KB leaves 12, +10 KB 8.  Results unchanged.
+    static const int extra_lds = [] { const char* e = getenv("HELIOS_RT_MIX_EXTRA_LDS"); return e ? atoi(e) : 0; }();
+    // the species list on chip holds MIX_MAX_ABSORBERS entries: a longer list is folded in block by block, every launch but
+    // the first starting from the mix the one before it wrote (the absorbers' order, and so every sum, is the reference's)
+    for (int first = 0; first == 0 || first < nabs_all; first += MIX_MAX_ABSORBERS) {
+        m.abs_list = abs_list + first;
+        m.nabs = std::min(MIX_MAX_ABSORBERS, nabs_all - first);
+        m.carry_on = first > 0 ? 1 : 0;
+        k_rt_mix_species<<<grid, 64, extra_lds, ctx->stream>>>(m);
+        HX_LAUNCH_CHECK(ctx);
+    }
+    return 0;
+}
+
 // on-the-fly mixing of every column, level and bin of the batch (computation.py:865-869, :1454-1501)
 static int refresh_species(hx_rt* rt) {
     hx_context* ctx = rt->ctx;
@@ -1000,26 +1023,8 @@ static int refresh_species(hx_rt* rt) {
     HX_LAUNCH_CHECK(ctx);
     {
         ProfScope ps(rt, "add_to_mixed_opac");
-        const long long npair = (long long)rt->C * (rt->L + rt->I) * rt->X;
-        // short runs (about ten points, each folding in every absorber): a wavefront lives for a fraction of a
-        // millisecond, so the last round of workgroups does not leave the chip half empty
-        static const int waves = [] { const char* e = getenv("HELIOS_RT_MIX_WAVES"); return e ? atoi(e) : 256 * 16 * 48; }();
-        const int grid = (int)std::min(npair, (long long)waves);
-        // occupancy experiment (profiles/r05_mix_occupancy.txt): bytes of unused dynamic LDS per wavefront on top of the
-        // kernel's 9.95 KB -- 16 wavefronts share a CU's 160 KB as built, +3.4 KB leaves 12, +10 KB 8.  Results unchanged.
-        static const int extra_lds = [] { const char* e = getenv("HELIOS_RT_MIX_EXTRA_LDS"); return e ? atoi(e) : 0; }();
-        // the species list on chip holds MIX_MAX_ABSORBERS entries: a longer list is folded in block by block, every launch but
-        // the first starting from the mix the one before it wrote (the absorbers' order, and so every sum, is the reference's)
-        const int nabs_all = rt->nabs;
-        for (int first = 0; first == 0 || first < nabs_all; first += MIX_MAX_ABSORBERS) {
-            m.abs_list = rt->abs_list + first;
-            m.nabs = std::min(MIX_MAX_ABSORBERS, nabs_all - first);
-            m.carry_on = first > 0 ? 1 : 0;
-            k_rt_mix_species<<<grid, 64, extra_lds, ctx->stream>>>(m);
-            HX_LAUNCH_CHECK(ctx);
-        }
-        m.abs_list = rt->abs_list;
-        m.nabs = nabs_all;
+        rc = launch_mix_species(ctx, m, rt->abs_list, rt->nabs);
+        if (rc) return rc;
     }
     {
         ProfScope ps(rt, "mixed_scat");

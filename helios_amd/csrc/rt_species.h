@@ -74,6 +74,14 @@ struct MixArgs {
     unsigned long long* diag;
 };
 
+constexpr int MIX_MAX_ABSORBERS = 48;  // LDS images of the species list: 1 KB next to the mixing images; a longer list takes
+                                       // one launch per block of 48 (MixArgs::carry_on)
+
+// The launches of k_rt_mix_species over the absorbers `abs_list[0 .. nabs_all)` of `m`, block by block (rt_fused.hip, where
+// the kernel lives).  csrc/premix.hip hands it node records of its own: a pseudo-column of L = 0 layers and I = nodes interfaces.
+int launch_mix_species(hx_context* ctx, MixArgs m, const int* abs_list, int nabs_all);
+
+#ifndef HX_SPECIES_DECLARATIONS_ONLY  // (premix.hip: the structures and vmr_from_table, not a second copy of the kernels)
 __global__ void k_rt_species_prep(MixArgs a) {
     const int col = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.I || a.done[col]) return;
@@ -127,9 +135,6 @@ __global__ void k_rt_mmm_from_vmr(const SpeciesDev* __restrict__ sp, int S, doub
         }
     mmm_lay[(size_t)col * I + i] = num / tot * HX_AMU;
 }
-
-constexpr int MIX_MAX_ABSORBERS = 48;  // LDS images of the species list: 1 KB next to the mixing images; a longer list takes
-                                       // one launch per block of 48 (MixArgs::carry_on)
 
 // ro::mix keeps this kernel within 7.9 KB of LDS and 96 VGPRs: five wavefronts per SIMD (tests/test_abi.py)
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) k_rt_mix_species(MixArgs a) {
@@ -265,5 +270,7 @@ __global__ void __launch_bounds__(256) k_rt_scat_species(MixArgs a) {
     }
     (lay ? a.scat_lay : a.scat_int)[(size_t)col * a.X * a.I + x + (size_t)a.X * i] = sum;
 }
+
+#endif  // HX_SPECIES_DECLARATIONS_ONLY
 
 }  // namespace hx

@@ -481,6 +481,43 @@ int hx_rt_traffic_model(hx_rt* rt, double* step_bytes_algorithmic, double* step_
 int hx_rt_profile(hx_rt* rt, int enable);
 int hx_rt_profile_read(hx_rt* rt, const char* kernel, double* out_avg_ms, int* out_count);
 
+/* ---- (5) premixed k-tables from the on-the-fly species set (csrc/premix.hip) -------------------------------------------------
+ * Where every species' mixing ratio is a constant or a (T, P) table, the on-the-fly mix of a level is a function of (T, P)
+ * alone; hx_premix_* evaluates it on the nodes of the species tables -- each cell of that grid divided into refine_t x
+ * refine_p cells, uniform in T and log10 P -- with the refresh's own species loop (k_rt_mix_species: correlated-k for the
+ * first absorber and CIA pairs, random overlap otherwise, or correlated-k throughout), and writes the tables a premixed run
+ * reads: kpoints[t][p][x][y], the weighted Rayleigh cross-sections [t][p][x] and the mean molecular mass [t][p] in amu.
+ * Works on the context: no batch, Planck table or columns.
+ *
+ *   hx_premix_create       dimensions; the species tables have ntemp x npress nodes, the output (ntemp-1)*refine_t+1 by
+ *                          (npress-1)*refine_p+1.  correlated_k = 1: `kcoeff_mixing = correlated-k`
+ *   hx_premix_set_grid     wave[nbin], Gauss points and weights [ny], the species tables' nodes (uniform in T and log10 P)
+ *   hx_premix_set_species  as hx_rt_set_species (pretab NULL: no absorber; scat_cross NULL: no fixed Rayleigh cross-section),
+ *                          with the mixing ratio as vmr_table[p + npress * t] on the species' nodes, or NULL and vmr_const.
+ *                          Tables stay on the device between runs: a second chemistry needs hx_premix_set_species_vmr only
+ *   hx_premix_run          builds the tables slab by slab (rows of temperature nodes; hx_premix_set_slab_rows: 0 = as many as
+ *                          fit) into host memory; cell_error = 1 also evaluates the mix at every output cell's centre and
+ *                          compares it with the premixed look-up's bilinear value there: max and mean over (x, y) of
+ *                          |k_table - k_otf| / k_otf per cell (deterministic: tree reductions in a fixed order)
+ *   hx_premix_get          "temperatures" [nT], "pressures" [nP], "kpoints", "scat_cross", "meanmolmass" (amu),
+ *                          "cell_error_max", "cell_error_mean" [(nT-1)(nP-1), p fastest], "timing_ms" (double[4]: node
+ *                          records, mixing launches, Rayleigh table, cell error incl. its mixing launches), "dims" (int32[2])
+ */
+typedef struct hx_premix hx_premix;
+int hx_premix_create(hx_context* ctx, int nbin, int ny, int ntemp, int npress, int nspecies, int refine_t, int refine_p,
+                     int correlated_k, hx_premix** out_pm);
+int hx_premix_destroy(hx_premix* pm);
+int hx_premix_set_grid(hx_premix* pm, const double* wave, const double* gauss_y, const double* gauss_w, const double* ktemp,
+                       const double* kpress);
+int hx_premix_set_species(hx_premix* pm, int s, const double* pretab, const double* scat_cross, const double* vmr_table,
+                          double vmr_const, double weight, int absorbing, int scattering, int is_h2o, int is_cia, int in_mu);
+/* synthetic species table kappa[t][p][x][y] = kxy[y + ny*x] * ftp[p + npress*t], formed on the device (hx_rt_set_species_separable) */
+int hx_premix_set_species_separable(hx_premix* pm, int s, const double* kxy, const double* ftp);
+int hx_premix_set_species_vmr(hx_premix* pm, int s, const double* vmr_table, double vmr_const);
+int hx_premix_set_slab_rows(hx_premix* pm, int rows);
+int hx_premix_run(hx_premix* pm, int cell_error);
+int hx_premix_get(hx_premix* pm, const char* name, void* out, size_t out_bytes);
+
 #ifdef __cplusplus
 }
 #endif
