@@ -518,6 +518,39 @@ int hx_premix_set_slab_rows(hx_premix* pm, int rows);
 int hx_premix_run(hx_premix* pm, int cell_error);
 int hx_premix_get(hx_premix* pm, const char* name, void* out, size_t out_bytes);
 
+/* ---- (6) per-species k-tables from HELIOS-K opacities (csrc/ktable.hip; host logic in helios_amd/ktable.py) -------------------
+ * Stage 1 of the reference's k-table tool: per wavelength bin and (T, P) point the opacities are floored at 1e-15, sorted by
+ * (log10 k, weight w), the mid-points of w accumulated to y and log10 k interpolated linearly in y at the Gauss abscissae
+ * (clamped to the end values).  The host decides once per species which points a bin holds and refuses an interior bin
+ * without points; a bin with none is filled with the floor here, one with a single point takes its value.
+ *
+ *   hx_ktable_create    n_points of the spectral axis, bins, Gauss points, (T, P) points of the table, slabs per launch, and
+ *                       the number of points up to which a bin is sorted in LDS (a power of two <= 16384; longer bins go
+ *                       through a device scratch of 8 B per point)
+ *   hx_ktable_set_grid  lamda[n_points] ascending (cm), per bin the range [bin_start, bin_end) of its points in lamda,
+ *                       interfaces[n_bins + 1], gauss_y[n_gauss] on (0, 1)
+ *   hx_ktable_run       n_tp slabs of fp32 opacities [n_tp][n_points] in ascending WAVENUMBER (as HELIOS-K writes them: point
+ *                       j of lamda is entry n_points - 1 - j) into the nodes first_tp ... of the table.  Returns when the
+ *                       slabs are on the device; the kernel may still run
+ *   hx_ktable_put       a table kpoints[n_tp][n_bins][n_gauss] made elsewhere, in place of hx_ktable_run's
+ *   hx_ktable_regrid    bilinear in T and log10 P onto nt_new x np_new nodes (table node = p + np_old * t); per target node
+ *                       the left source node and whether the axis is clamped there, as the reference's routine finds them
+ *   hx_ktable_get       "kpoints" [y + ny*x + ny*nx*node], "kpoints_ip" (the same on the target nodes), "timing_ms"
+ *                       (double[4]: ms in k_ktable_bins, its launches, ms in the re-gridding, (T, P) points done)
+ */
+typedef struct hx_ktable hx_ktable;
+int hx_ktable_create(hx_context* ctx, int n_points, int n_bins, int n_gauss, int n_tp, int max_tp_per_launch, int lds_points,
+                     hx_ktable** out_kt);
+int hx_ktable_destroy(hx_ktable* kt);
+int hx_ktable_set_grid(hx_ktable* kt, const double* lamda, const int* bin_start, const int* bin_end, const double* interfaces,
+                       const double* gauss_y);
+int hx_ktable_run(hx_ktable* kt, const void* opac_f32, int n_tp, int first_tp);
+int hx_ktable_put(hx_ktable* kt, const double* kpoints);
+int hx_ktable_regrid(hx_ktable* kt, int nt_old, int np_old, int nt_new, int np_new, const int* t_left, const int* t_reduced,
+                     const int* p_left, const int* p_reduced, const double* temp_old, const double* logp_old,
+                     const double* temp_new, const double* logp_new);
+int hx_ktable_get(hx_ktable* kt, const char* name, void* out, size_t out_bytes);
+
 #ifdef __cplusplus
 }
 #endif
