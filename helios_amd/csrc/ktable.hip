@@ -381,6 +381,8 @@ int hx_ktable_set_grid(hx_ktable* kt, const double* lamda, const int* bin_start,
     for (int x = 0; x < kt->nbin; x++) {
         HX_REQUIRE(ctx, 0 <= bin_start[x] && bin_start[x] <= bin_end[x] && bin_end[x] <= kt->N, HX_E_ARG,
                    "a bin's range lies outside the spectral axis");
+        // two workgroups would sort the same stretch of the scratch at once
+        HX_REQUIRE(ctx, x == 0 || bin_start[x] >= bin_end[x - 1], HX_E_ARG, "the bins' ranges overlap or do not ascend");
         HX_REQUIRE(ctx, interfaces[x] < interfaces[x + 1], HX_E_ARG, "interfaces are not ascending");
         longest = std::max(longest, bin_end[x] - bin_start[x]);
     }

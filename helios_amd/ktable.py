@@ -176,8 +176,20 @@ def _interp_clamped(y, logk, yg):
     return out
 
 
-def numpy_bin(lam, inter, x, s, e, opac_rev, yg):
-    """one bin of one (T, P) point; `opac_rev` in ascending wavelength"""
+def _compensated_cumsum(a):
+    """the reference's sequential running sum in fp64, and with it what every one of its additions rounded away (two-sum,
+    exact in fp64), summed up alongside: over 7e4 points the plain sum drifts by tens of ulps of y, which the steep steps
+    between tie groups turn into 1e-9 in log10 k; this one stays within an ulp or two"""
+    s = np.cumsum(a)
+    prev = np.concatenate(([0.0], s[:-1]))
+    b = s - prev
+    lost = (prev - (s - b)) + (a - b)
+    return s + np.cumsum(lost)
+
+
+def numpy_bin(lam, inter, x, s, e, opac_rev, yg, plain_sum=False):
+    """one bin of one (T, P) point; `opac_rev` in ascending wavelength.  `plain_sum`: y by the reference's plain running sum,
+    the fp64 noise of which is what the tests measure the device's bound from"""
     n = e - s
     if n == 0:
         return np.full(len(yg), K_FLOOR)
@@ -191,7 +203,7 @@ def numpy_bin(lam, inter, x, s, e, opac_rev, yg):
     mid = np.empty(n, np.float64)
     mid[0] = 0.5 * w[0]
     mid[1:] = 0.5 * (w[:-1] + w[1:])
-    y = np.cumsum(mid)                       # sequential, as the reference's loop
+    y = np.cumsum(mid) if plain_sum else _compensated_cumsum(mid)
     return 10 ** _interp_clamped(y, logk, yg)
 
 

@@ -528,7 +528,8 @@ int hx_premix_get(hx_premix* pm, const char* name, void* out, size_t out_bytes);
  *                       the number of points up to which a bin is sorted in LDS (a power of two <= 16384; longer bins go
  *                       through a device scratch of 8 B per point)
  *   hx_ktable_set_grid  lamda[n_points] ascending (cm), per bin the range [bin_start, bin_end) of its points in lamda,
- *                       interfaces[n_bins + 1], gauss_y[n_gauss] on (0, 1)
+ *                       interfaces[n_bins + 1], gauss_y[n_gauss] on (0, 1).  The ranges ascend and are disjoint
+ *                       (bin_start[x] >= bin_end[x - 1]); anything else is refused with HX_E_ARG
  *   hx_ktable_run       n_tp slabs of fp32 opacities [n_tp][n_points] in ascending WAVENUMBER (as HELIOS-K writes them: point
  *                       j of lamda is entry n_points - 1 - j) into the nodes first_tp ... of the table.  Returns when the
  *                       slabs are on the device; the kernel may still run
