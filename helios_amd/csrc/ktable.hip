@@ -510,3 +510,151 @@ int hx_ktable_get(hx_ktable* kt, const char* name, void* out, size_t out_bytes) 
 }
 
 }  // extern "C"
+
+// ---- the analytic containers (include/helios_hip.h section 7; the contract is stated in helios_amd/continuum.py) -------------------
+//
+// k_ktable_continuum: a workgroup takes 256 consecutive bins of one (T, P) row.  Every thread evaluates the opacity of its bin
+// once; the tile's 256 * ny values -- each repeated over y -- are contiguous in the container's [t][p][x][y] order and are written
+// by the whole workgroup, consecutive lanes to consecutive addresses, as 16-byte stores (one 8-byte store in front or behind where
+// the tile does not start or end on 16 bytes).  The kind's coefficients arrive as a device array and are staged in LDS.
+namespace {
+
+constexpr int KC_THREADS = 256;
+constexpr int KC_MAX_COEF = 304;
+constexpr int KC_HE_NT = 12, KC_HE_NX = 22;
+constexpr int KC_COEF_BF = 9, KC_COEF_FF = 76, KC_COEF_HE = 4 + KC_HE_NT + KC_HE_NX + KC_HE_NT * KC_HE_NX;
+
+struct KcArgs {
+    const double *coef, *wave, *temp, *press;
+    double* out;              // the slab: row first_row of the container is its row 0
+    int kind, ncoef, nbin, ny, npress, first_row;
+};
+
+// H- bound-free: [mass, mu_min, mu_0, C_0 .. C_5]
+__device__ double kc_hm_bf(const double* c, double mu) {
+    if (mu < c[1] || mu > c[2]) return 0.0;
+    const double x = (c[2] - mu) / (mu * c[2]), s = sqrt(x);        // 1/mu - 1/mu_0 without the cancellation
+    double f = c[8];
+    for (int k = 7; k >= 3; k--) f = f * s + c[k];
+    return 1e-18 * (mu * mu * mu) * (x * s) * f / c[0];
+}
+
+// H- free-free: [mass, mu_min, mu_split, 5040, then per regime the sets A .. F of six].  Next to 0.3645 micron and at low T the
+// terms of the fit cancel to one part in 1e3 ... 1e5, so the sums run in double-double (a value as an unevaluated hi + lo; the
+// error of every product comes from an fma, of every sum from the two-sum): the result is rounded once from ~100 bits.
+struct kc_dd { double hi, lo; };
+
+__device__ __forceinline__ kc_dd kc_renorm(double s, double e) {
+    kc_dd r;
+    r.hi = s + e;
+    r.lo = e - (r.hi - s);
+    return r;
+}
+
+__device__ __forceinline__ kc_dd kc_add(kc_dd a, kc_dd b) {
+    const double s = a.hi + b.hi, bb = s - a.hi;
+    const double e = (a.hi - (s - bb)) + (b.hi - bb);
+    return kc_renorm(s, e + (a.lo + b.lo));
+}
+
+__device__ __forceinline__ kc_dd kc_mul(kc_dd a, kc_dd b) {
+    const double p = a.hi * b.hi;
+    const double e = fma(a.hi, b.hi, -p) + (a.hi * b.lo + a.lo * b.hi);
+    return kc_renorm(p, e);
+}
+
+__device__ __forceinline__ kc_dd kc_of(double v) { kc_dd r; r.hi = v; r.lo = 0.0; return r; }
+
+__device__ __forceinline__ kc_dd kc_div(double a, double b) {          // a / b
+    const double q = a / b;
+    return kc_renorm(q, fma(-q, b, a) / b);
+}
+
+__device__ __forceinline__ kc_dd kc_sqrt(kc_dd a) {
+    const double s = sqrt(a.hi);
+    return kc_renorm(s, (fma(-s, s, a.hi) + a.lo) / (2.0 * s));
+}
+
+__device__ double kc_hm_ff(const double* c, double mu, double T, double P) {
+    if (mu < c[1]) return 0.0;
+    const double* s = c + 4 + (mu < c[2] ? 0 : 36);
+    const kc_dd theta = kc_div(c[3], T), root = kc_sqrt(theta), u = kc_div(1.0, mu), mu2 = kc_mul(kc_of(mu), kc_of(mu));
+    kc_dd total = kc_of(0.0);
+    for (int n = 5; n >= 0; n--) {
+        kc_dd g = kc_of(s[30 + n]);
+        for (int term = 24; term >= 6; term -= 6) g = kc_add(kc_mul(g, u), kc_of(s[term + n]));
+        g = kc_add(g, kc_mul(mu2, kc_of(s[n])));
+        total = kc_add(kc_mul(total, root), g);
+    }
+    total = kc_mul(theta, total);
+    return 1e-29 * (total.hi + total.lo) * P / c[0];
+}
+
+// He-: [mass, mu_lo, mu_hi, fill, T nodes, log10 mu nodes, log10 k [t][x]]
+__device__ double kc_he(const double* c, double mu, double T, double P) {
+    const double *tn = c + 4, *xn = tn + KC_HE_NT, *z = xn + KC_HE_NX;
+    double v = c[3];
+    if (T >= tn[0] && T <= tn[KC_HE_NT - 1] && mu >= c[1] && mu <= c[2]) {
+        const double x = log10(mu);
+        int i = 0, j = 0;
+        while (i < KC_HE_NT - 2 && tn[i + 1] <= T) i++;
+        while (j < KC_HE_NX - 2 && xn[j + 1] <= x) j++;
+        const double ft = (T - tn[i]) / (tn[i + 1] - tn[i]), fx = (x - xn[j]) / (xn[j + 1] - xn[j]);
+        const double* z0 = z + i * KC_HE_NX + j;
+        v = (z0[0] * (1 - ft) + z0[KC_HE_NX] * ft) * (1 - fx) + (z0[1] * (1 - ft) + z0[KC_HE_NX + 1] * ft) * fx;
+    }
+    return pow(10.0, v) * P / c[0];
+}
+
+__launch_bounds__(KC_THREADS) __global__ void k_ktable_continuum(KcArgs A) {
+    __shared__ double coef[KC_MAX_COEF];
+    __shared__ double val[KC_THREADS];
+    const int tid = threadIdx.x;
+    for (int k = tid; k < A.ncoef; k += KC_THREADS) coef[k] = A.coef[k];
+    __syncthreads();
+    const int x0 = blockIdx.x * KC_THREADS, cnt = min(KC_THREADS, A.nbin - x0);
+    const int row = A.first_row + blockIdx.y;
+    if (tid < cnt) {
+        const double T = A.temp[row / A.npress], P = A.press[row % A.npress];
+        const double mu = A.wave[x0 + tid] * 1e4;                   // micron, rounded as the contract rounds it
+        val[tid] = A.kind == 0 ? kc_hm_bf(coef, mu) : (A.kind == 1 ? kc_hm_ff(coef, mu, T, P) : kc_he(coef, mu, T, P));
+    }
+    __syncthreads();
+    double* dst = A.out + ((size_t)blockIdx.y * A.nbin + x0) * A.ny;
+    const int n = cnt * A.ny;
+    const int head = ((size_t)dst & 15) ? 1 : 0;
+    if (head && tid == 0) dst[0] = val[0];
+    const int pairs = (n - head) >> 1;
+    for (int q = tid; q < pairs; q += KC_THREADS) {
+        const int e = head + 2 * q;
+        double2 v;
+        v.x = val[e / A.ny];
+        v.y = val[(e + 1) / A.ny];
+        *reinterpret_cast<double2*>(dst + e) = v;
+    }
+    if (((n - head) & 1) && tid == 0) dst[n - 1] = val[(n - 1) / A.ny];
+}
+
+}  // namespace
+
+extern "C" int hx_continuum_table(hx_context* ctx, int kind, const double* coef, int ncoef, const double* wave, int nbin, int ny,
+                                  const double* temp, int ntemp, const double* press, int npress, double* out, int first_row,
+                                  int rows) {
+    if (!ctx) return HX_E_ARG;
+    HX_REQUIRE(ctx, kind >= 0 && kind <= 2, HX_E_ARG, "kind is 0 (H- bound-free), 1 (H- free-free) or 2 (He-)");
+    HX_REQUIRE(ctx, ncoef == (kind == 0 ? KC_COEF_BF : (kind == 1 ? KC_COEF_FF : KC_COEF_HE)), HX_E_ARG,
+               "the coefficient array has another length than this kind's");
+    HX_REQUIRE(ctx, coef && wave && temp && press && out, HX_E_ARG, "null array");
+    HX_REQUIRE(ctx, nbin >= 1 && nbin <= (1 << 24) && ny >= 1 && ny <= 65536, HX_E_ARG, "1 ... 2^24 bins, 1 ... 65536 Gauss points");
+    HX_REQUIRE(ctx, ntemp >= 1 && npress >= 1 && (long long)ntemp * npress <= (1 << 30), HX_E_ARG, "an empty (T, P) grid");
+    HX_REQUIRE(ctx, rows >= 1 && rows <= 65535, HX_E_ARG, "1 ... 65535 rows per call");
+    HX_REQUIRE(ctx, first_row >= 0 && (long long)first_row + rows <= (long long)ntemp * npress, HX_E_ARG,
+               "the rows reach beyond the (T, P) grid");
+    HX_REQUIRE(ctx, ((size_t)out & 7) == 0, HX_E_ARG, "the output is not aligned to 8 bytes");
+    KcArgs A;
+    A.coef = coef; A.wave = wave; A.temp = temp; A.press = press; A.out = out;
+    A.kind = kind; A.ncoef = ncoef; A.nbin = nbin; A.ny = ny; A.npress = npress; A.first_row = first_row;
+    k_ktable_continuum<<<dim3((nbin + KC_THREADS - 1) / KC_THREADS, rows), KC_THREADS, 0, ctx->stream>>>(A);
+    HX_LAUNCH_CHECK(ctx);
+    return 0;
+}

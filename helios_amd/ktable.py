@@ -505,7 +505,7 @@ def read_species_list(path):
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser(prog="ktable.py", description="species k-tables from HELIOS-K output")
-    p.add_argument("-path_to_individual_species_file", required=True)
+    p.add_argument("-path_to_individual_species_file", default=None)
     p.add_argument("-format", default="k-distribution")
     p.add_argument("-helios_k_output_format", default="binary")
     p.add_argument("-grid_format", default="fixed_resolution")
@@ -519,7 +519,12 @@ def parse_args(argv=None):
     p.add_argument("-backend", default="hip", choices=("hip", "numpy"))
     p.add_argument("-points_per_launch", type=int, default=4)
     p.add_argument("-container", default="h5", choices=("h5", "npz"))
+    p.add_argument("-continuum_species", default=None, help="analytic containers on the target grid: H- (H-_bf and H-_ff), He-")
+    p.add_argument("-rayleigh_species", default=None, help="species of scat_cross_sections: H2, He, H, CO2, CO, O2, N2, e-")
+    p.add_argument("-grid_like", default=None, help="an _opac_ip_kdistr container whose grid the analytic tables take")
     opt = p.parse_args(argv)
+    if opt.path_to_individual_species_file is None and opt.continuum_species is None and opt.rayleigh_species is None:
+        p.error("one of -path_to_individual_species_file, -continuum_species, -rayleigh_species is required")
     if opt.format == "sampling":
         raise IOError("ktable: format = sampling is not built; this tool makes k-distribution tables")
     if opt.format != "k-distribution":
@@ -529,18 +534,56 @@ def parse_args(argv=None):
     return opt
 
 
+def analytic_tables(opt, inter, ctx):
+    """-continuum_species and -rayleigh_species: the containers and the Rayleigh file on the grid of -grid_like, or on the
+    grid the tool's options define; returns the paths written"""
+    from . import continuum
+    names = continuum.continuum_species(opt.continuum_species) if opt.continuum_species is not None else []
+    rayleigh = continuum.rayleigh_species(opt.rayleigh_species) if opt.rayleigh_species is not None else []
+    if opt.grid_like is not None:
+        grid = continuum.grid_like(opt.grid_like)
+    else:
+        grid = continuum.grid_from(inter, opt.number_of_gaussian_points, *target_grid(opt.temperature_grid, opt.pressure_grid))
+    out_dir, written, builder = opt.directory_with_individual_files, [], None
+    try:
+        for name in names:
+            t0 = time.time()
+            if ctx is not None and builder is None:
+                builder = continuum.ContinuumBuilder(ctx, grid["center wavelengths"], len(grid["ypoints"]), grid["temperatures"],
+                                                     grid["pressures"])
+            data = continuum.build_continuum(name, grid, opt.backend, ctx, builder)
+            written.append(write_table("%s_opac_ip_kdistr.%s" % (os.path.join(out_dir, name), opt.container), data))
+            print("ktable: %s, %d x %d (T, P) nodes, %d bins x %d Gauss points in %.2f s -> %s"
+                  % (name, len(grid["temperatures"]), len(grid["pressures"]), len(grid["center wavelengths"]),
+                     len(grid["ypoints"]), time.time() - t0, written[-1]))
+    finally:
+        if builder is not None:
+            builder.close()
+    if rayleigh:
+        # nbin numbers per species: made on the host whatever the backend, there is no device work in it worth a launch
+        path, new, kept = continuum.write_rayleigh_file(out_dir, opt.container, grid["center wavelengths"], rayleigh)
+        written.append(path)
+        print("ktable: Rayleigh cross-sections of %s -> %s" % (", ".join(new) if new else "no new species", path))
+        if kept:
+            print("ktable: rayleigh_%s already there, left as %s" % (", rayleigh_".join(kept), "it is" if len(kept) == 1 else
+                                                                      "they are"))
+    return written
+
+
 def main(argv=None):
-    """ktable.py: one table per species of the list (and its re-gridded twin); returns the paths written"""
+    """ktable.py: one table per species of the list (and its re-gridded twin), then the analytic tables asked for; returns the
+    paths written"""
     opt = parse_args(argv)
     inter = wavelength_grid(opt.grid_format, opt.wavelength_grid.split(), opt.path_to_grid_file)
     target = target_grid(opt.temperature_grid, opt.pressure_grid) if opt.interpolate == "yes" else None
     ctx = None
-    if opt.backend == "hip":
+    if opt.backend == "hip" and (opt.path_to_individual_species_file or opt.continuum_species is not None):
         from .device import Context
         ctx = Context(int(os.environ.get("HELIOS_DEVICE", "0")))
     written = []
     try:
-        for name, path in read_species_list(opt.path_to_individual_species_file):
+        species = read_species_list(opt.path_to_individual_species_file) if opt.path_to_individual_species_file else []
+        for name, path in species:
             timing = {}
             native, ip = build_species(path, inter, opt.number_of_gaussian_points, opt.helios_k_output_format, opt.backend, ctx,
                                        opt.points_per_launch, target=target, timing=timing)
@@ -551,6 +594,8 @@ def main(argv=None):
             print("ktable: %s, %d (T, P) points at %g cm^-1 into %d bins x %d Gauss points in %.2f s -> %s"
                   % (name, timing["points"], timing["resolution"], len(inter) - 1, opt.number_of_gaussian_points,
                      timing["seconds"], written[-1]))
+        if opt.continuum_species is not None or opt.rayleigh_species is not None:
+            written += analytic_tables(opt, inter, ctx)
     finally:
         if ctx is not None:
             ctx.close()

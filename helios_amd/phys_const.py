@@ -20,3 +20,4 @@ R_SUN = 6.957e10                 # nominal solar radius, cm
 R_JUP = 7.1492e9                 # nominal equatorial Jupiter radius, cm
 R_EARTH = 6.3781e8               # nominal equatorial Earth radius, cm
 G = 6.674299999999999e-08        # gravitational constant, cgs (astropy's `.cgs` of 6.6743e-11 SI, one ulp below 6.6743e-8)
+SIGMA_T = 6.6524587321000005e-25  # Thomson cross-section, cm2 (astropy's `.cgs` of 6.6524587321e-29 m2, one ulp above 6.6524587321e-25)

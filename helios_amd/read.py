@@ -184,6 +184,12 @@ class _Table(object):
     def keys(self):
         return list(self._npz.keys()) if self._npz is not None else list(self._h5.keys())
 
+    def close(self):
+        """releases an HDF5 file, so that it may be written anew"""
+        if self._h5 is not None:
+            self._h5.close()
+            self._h5 = None
+
 
 class Read(object):
     """reads the parameter file, the command line and the input tables"""

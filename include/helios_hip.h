@@ -552,6 +552,20 @@ int hx_ktable_regrid(hx_ktable* kt, int nt_old, int np_old, int nt_new, int np_n
                      const double* temp_new, const double* logp_new);
 int hx_ktable_get(hx_ktable* kt, const char* name, void* out, size_t out_bytes);
 
+/* ---- (7) the analytic containers of the k-table tool: H- bound-free, H- free-free, He- (csrc/ktable.hip, k_ktable_continuum;
+ * the contract and the host side are helios_amd/continuum.py) --------------------------------------------------------------------
+ * Fills `rows` (T, P) rows of a container kpoints[t][p][x][y] from row first_row on (row = p + npress * t) into out[rows][nbin][ny]:
+ * the opacity of bin x at (T, P), repeated over y.  All arrays are DEVICE arrays: wave[nbin] bin centres in cm, temp[ntemp],
+ * press[npress], and the kind's coefficients (helios_amd/continuum_data.py holds the numbers):
+ *   kind 0, H- bound-free   9:   m_H [g], mu_min, mu_0 [micron], C_0 .. C_5
+ *   kind 1, H- free-free    76:  m_H, mu_min, mu_split, 5040 K, then for mu < mu_split and for the rest A[6], B[6], ..., F[6]
+ *   kind 2, He-             302: m_He, the least and the greatest mu whose log10 lies in the table, log10 k outside it, 12
+ *                                temperatures, 22 log10 mu, log10 k [12][22]
+ * At most 65535 rows per call; the call returns when the kernel is launched.
+ */
+int hx_continuum_table(hx_context* ctx, int kind, const double* coef, int ncoef, const double* wave, int nbin, int ny,
+                       const double* temp, int ntemp, const double* press, int npress, double* out, int first_row, int rows);
+
 #ifdef __cplusplus
 }
 #endif

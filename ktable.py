@@ -10,6 +10,12 @@ The species file has a header line, then `name directory` per species; a directo
 `<name>_opac_kdistr.h5` on the files' own (T, P) nodes and, unless `-interpolate no`, `<name>_opac_ip_kdistr.h5` on the
 reference's final grid (or -temperature_grid / -pressure_grid) -- the container helios.py's on-the-fly mixing and premix.py
 read.  `-backend numpy` computes the same on the CPU; `-container npz` writes .npz.  Only the k-distribution format is built.
+
+    python ktable.py -continuum_species "H-,He-" -rayleigh_species "H2,He" -grid_like opac/H2O_opac_ip_kdistr.h5 \\
+        -directory_with_individual_files opac/
+
+writes the analytic tables next to them: `H-_bf`, `H-_ff` and `He-` containers and `scat_cross_sections.h5`, on the grid of
+the container named (without -grid_like: on the grid the options above define).
 """
 import sys
 
