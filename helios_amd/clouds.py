@@ -7,6 +7,8 @@ parameter reader).  Host-only, once per run.  Kept as in the reference on purpos
 is weighted with the SCATTERING cross-section of each radius, not with g_0 itself (clouds.py:108),
 so that cloudy runs reproduce the reference's fluxes.
 """
+import os
+
 import numpy as np
 
 from . import tools as tls
@@ -104,6 +106,48 @@ class Cloud(object):
             self.f_one_cloud_lay = on_profile(p_lay)
             if quant.iso == 0:
                 self.f_one_cloud_int = on_profile(p_int)
+
+    # ---- deck description: what the device needs to build the planes itself ---------------------------------
+    @classmethod
+    def mie_table(cls, mie_path, cache=None):
+        """the Mie table of one aerosol directory as arrays: wavelengths [nw] in cm, scattering and absorption cross-sections
+        [radius][wavelength] on the LX-MIE radius grid -- what calc_weighted_cross_sections_... reads per deck.  `cache`
+        (a dict that lives as long as the process's sweep) keeps one table per directory, keyed by its real path"""
+        key = os.path.realpath(str(mie_path))
+        if cache is not None and key in cache:
+            return cache[key]
+        per_r = [cls.read_mie_file(mie_path + "r{:.6f}.dat".format(r)) for r in R_VALUES]
+        table = dict(path=key, lamda_mie=np.ascontiguousarray(per_r[0][0], dtype=np.float64),
+                     scat=np.ascontiguousarray([t[1] for t in per_r], dtype=np.float64),
+                     absorb=np.ascontiguousarray([t[2] for t in per_r], dtype=np.float64))
+        if cache is not None:
+            cache[key] = table
+        return table
+
+    def cloud_deck_description(self, quant, cache=None):
+        """next to cloud_pre_processing: the decks as the device takes them (RTBatch.set_column_cloud_decks) -- per deck its
+        Mie table, the radius weights pdf * DELTA_R and the mixing-ratio profiles of create_cloud_deck -- instead of the six
+        planes, which are then built on the device.  Sets the total mixing ratio (the output files print it) and leaves the
+        planes empty on the Store; returns and keeps the description as quant.cloud_decks"""
+        L, I = int(quant.nlayer), int(quant.ninterface)
+        quant.f_all_clouds_lay, quant.f_all_clouds_int = np.zeros(L), np.zeros(I)
+        for stem in ("abs_cross_all_clouds", "scat_cross_all_clouds", "g_0_all_clouds"):
+            setattr(quant, stem + "_lay", np.zeros(0))
+            setattr(quant, stem + "_int", np.zeros(0))
+        nd = int(self.nr_cloud_decks)
+        tables, weights = [], []
+        f_lay, f_int = np.zeros((nd, L)), np.zeros((nd, I))
+        for nr in range(nd):
+            tables.append(self.mie_table(self.mie_path[nr], cache))
+            weights.append(self.lognorm_pdf(R_VALUES, self.cloud_r_mode[nr], self.cloud_r_std_dev[nr]) * DELTA_R)
+            self.create_cloud_deck(nr, quant)
+            f_lay[nr], f_int[nr] = self.f_one_cloud_lay, self.f_one_cloud_int
+            quant.f_all_clouds_lay[:] += f_lay[nr]
+            if quant.iso == 0:
+                quant.f_all_clouds_int[:] += f_int[nr]
+        quant.cloud_decks = dict(tables=tables, radius_weight=np.array(weights, np.float64).reshape(nd, len(R_VALUES)),
+                                 f_lay=f_lay, f_int=f_int)
+        return quant.cloud_decks
 
     def add_individual_cloud_decks_to_total(self, quant):
         a, s, g = (np.asarray(v, float) for v in (self.abs_cross_one_cloud, self.scat_cross_one_cloud, self.g_0_one_cloud))

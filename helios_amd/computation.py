@@ -551,11 +551,21 @@ class Compute(object):
                     rt.set_column_table(c, index[id(qc.opac_k)])
         if self._kappa_from_table(q):
             rt.set_kappa_table(q.entr_temp, q.entr_press, q.entr_kappa, q.entr_c_p)
+        mie_index = {}
         for c, qc in enumerate(quants):
             qc.rt, qc.rt_col = rt, c
             rt.set_column_profile(c, qc.p_lay, qc.p_int, qc.T_lay, qc.surf_albedo,
                                   qc.starflux if len(np.atleast_1d(qc.starflux)) == _i(qc.nbin) else None)
-            if qc.clouds == 1:
+            decks = getattr(qc, "cloud_decks", None)
+            if qc.clouds == 1 and decks is not None:
+                # the planes are built on the device (Cloud.cloud_deck_description): every distinct Mie table of the batch goes
+                # there once -- the Stores of a sweep that name the same directory hold the same table object
+                for t in decks["tables"]:
+                    if id(t) not in mie_index:
+                        mie_index[id(t)] = rt.add_mie_table(t["lamda_mie"], t["scat"], t["absorb"])
+                rt.set_column_cloud_decks(c, [mie_index[id(t)] for t in decks["tables"]], decks["radius_weight"],
+                                          decks["f_lay"], None if qc.iso == 1 else decks["f_int"])
+            elif qc.clouds == 1:
                 rt.set_column_clouds(c, qc.abs_cross_all_clouds_lay, qc.abs_cross_all_clouds_int,
                                      qc.scat_cross_all_clouds_lay, qc.scat_cross_all_clouds_int,
                                      qc.g_0_all_clouds_lay, qc.g_0_all_clouds_int)

@@ -42,6 +42,13 @@ struct TableSet {
     const double *k, *scat_cross, *meanmass;
 };
 
+// One aerosol's Mie table on the device (hx_rt_add_mie_table): wavelengths [nw] in cm, ascending; scattering and absorption
+// cross-sections [nr][nw] per particle radius.  Also the record k_cloud_deck_spectra reads (hx_rt::mie_dev).
+struct MieTable {
+    const double *lam, *scat, *absorb;
+    int nw, nr;
+};
+
 struct ProfileEntry {
     std::string name;
     hipEvent_t e0, e1;
@@ -130,6 +137,17 @@ struct hx_rt {
     int entr_ntemp = 0, entr_npress = 0;
     double* add_heat_dens = nullptr;   // L: additional heating density [erg cm^-3 s^-1]; flux = density * layer height
     bool has_heating = false;
+
+    // cloud decks built on the device (clouds.hip): the batch's Mie tables, resident once each; the decks' re-binned spectra
+    // [C][cloud_ndecks][3][X] (absorption, scattering, the scattering-weighted third one); the staging of one
+    // hx_rt_set_column_cloud_decks call (radius weights, mixing-ratio profiles, table indices)
+    std::vector<hx::MieTable> mie;
+    hx::MieTable* mie_dev = nullptr;
+    double* cloud_spec = nullptr;
+    int cloud_ndecks = 0;          // 0: no deck call yet; the first one fixes it
+    double* cloud_stage = nullptr;
+    int* cloud_stage_index = nullptr;
+    int cloud_stage_nr = 0;
 
     // hx_rt_flags.matrix: `flux calculation method = matrix`, the direct solve as three scans on the coefficient tiles
     // (k_rt_flux<.., true>)

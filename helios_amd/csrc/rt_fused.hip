@@ -411,7 +411,8 @@ int hx_rt_create(hx_context* ctx, const hx_rt_dims* dims, const hx_rt_flags* fla
                  const hx_rt_column* columns, hx_rt** out_rt) {
     if (!ctx || !dims || !flags || !columns || !out_rt) return HX_E_ARG;
     *out_rt = nullptr;
-    HX_REQUIRE(ctx, dims->nbin > 0 && dims->ny > 0 && dims->nlayer >= 2 && dims->ncol > 0, HX_E_ARG,
+    // (one layer: a batch that holds inputs and cloud planes -- the setters and hx_rt_get; the iteration needs two, RT_NEED_LOOP)
+    HX_REQUIRE(ctx, dims->nbin > 0 && dims->ny > 0 && dims->nlayer >= 1 && dims->ncol > 0, HX_E_ARG,
                "bad dimensions");
     HX_REQUIRE(ctx, dims->plancktable_dim >= 10 && dims->plancktable_step > 0, HX_E_ARG,
                "bad Planck-table dimensions");
@@ -574,6 +575,14 @@ int hx_rt_destroy(hx_rt* rt) {
 
 // A setter changed what the launches are given: captured graphs hold older arguments (each compares its own generation),
 // and spectral flux tiles re-created for hx_rt_get are no longer the last solve's.
+// the refresh and the iterations interpolate between neighbouring layers: refused for a one-layer batch before any launch
+#define RT_NEED_LOOP(rt)                                                                                             \
+    do {                                                                                                             \
+        if ((rt)->L < 2)                                                                                             \
+            return hx_fail((rt)->ctx, HX_E_UNSUPPORTED, "%s: the batch has %d layer; refresh and iterations need at " \
+                           "least 2", __func__, (rt)->L);                                                            \
+    } while (0)
+
 static inline void rt_touch(hx_rt* rt) {
     rt->graph_gen++;
     rt->solve_serial++;
@@ -1036,6 +1045,7 @@ static int refresh_species(hx_rt* rt) {
 
 int hx_rt_refresh(hx_rt* rt) {
     if (!rt) return HX_E_ARG;  // e.g. a call after hx_rt_destroy
+    RT_NEED_LOOP(rt);
     hx_context* ctx = rt->ctx;
     rt->solve_serial++;
     HX_REQUIRE(ctx, rt->have_grid && rt->have_tables && rt->have_planck, HX_E_STATE,
@@ -1221,6 +1231,7 @@ static int sync_iteration_counter(hx_rt* rt, int itervalue) {
 
 int hx_rt_step(hx_rt* rt, int itervalue, int step_temperature) {
     if (!rt) return HX_E_ARG;  // e.g. a call after hx_rt_destroy
+    RT_NEED_LOOP(rt);
     int rc = sync_iteration_counter(rt, itervalue);
     if (rc) return rc;
     bool nodes_done = false;
@@ -1289,6 +1300,7 @@ int kappa_cp_from_table(hx_rt* rt, bool refresh_T_int) {
 // computation.py:199-250); needs hx_rt_set_kappa_table
 int hx_rt_kappa_cp_refresh(hx_rt* rt) {
     if (!rt) return HX_E_ARG;
+    RT_NEED_LOOP(rt);
     HX_REQUIRE(rt->ctx, rt->entr_kappa != nullptr, HX_E_STATE, "no kappa / c_p table set");
     return kappa_cp_from_table(rt, true);
 }
@@ -1315,6 +1327,7 @@ int hx_rt_set_kappa_table(hx_rt* rt, const double* entr_temp, int entr_ntemp, co
 // adjustment of the temperature profile (computation.py:1027-1047)
 int hx_rt_conv_adjust(hx_rt* rt, int itervalue) {
     if (!rt) return HX_E_ARG;  // e.g. a call after hx_rt_destroy
+    RT_NEED_LOOP(rt);
     hx_context* ctx = rt->ctx;
     HX_REQUIRE(ctx, rt->have_grid && rt->have_tables, HX_E_STATE, "hx_rt_conv_adjust before the tables are set");
     if (itervalue % 10 == 0) {   // computation.py:1030-1036: mu of the profile BEFORE the adjustment
@@ -1356,6 +1369,7 @@ int hx_rt_conv_adjust(hx_rt* rt, int itervalue) {
 // temperature step (computation.py:1048-1145).  A column whose loop has ended is frozen (`done`, `iters_done`).
 int hx_rt_conv_advance(hx_rt* rt, int itervalue) {
     if (!rt) return HX_E_ARG;  // e.g. a call after hx_rt_destroy
+    RT_NEED_LOOP(rt);
     hx_context* ctx = rt->ctx;
     bool nodes_done = false;
     if (itervalue % 10 == 0 || !rt->refreshed) {
@@ -1489,6 +1503,7 @@ static int build_iteration_graph(hx_rt* rt, bool with_refresh) {
 
 int hx_rt_run(hx_rt* rt, int itervalue, int nsteps) {
     if (!rt) return HX_E_ARG;  // e.g. a call after hx_rt_destroy
+    RT_NEED_LOOP(rt);
     for (int n = 0; n < nsteps;) {
         const int it = itervalue + n;
         const bool decade = it % 10 == 0 && nsteps - n >= GRAPH_ITERATIONS + 1 && (rt->d.nspecies == 0 || !rt->species_dev_stale);
@@ -1637,6 +1652,12 @@ int hx_rt_get(hx_rt* rt, int col, const char* name, void* out, size_t out_bytes)
         memcpy(out, &v, sizeof(v));
         return 0;
     }
+    if (strcmp(name, "mie_table_count") == 0) {   // host-side, any column (-1): int32, the Mie tables the batch holds
+        HX_REQUIRE(rt->ctx, out_bytes == sizeof(int32_t), HX_E_ARG, "mie_table_count is one int32");
+        const int32_t v = (int32_t)rt->mie.size();
+        memcpy(out, &v, sizeof(v));
+        return 0;
+    }
     HX_REQUIRE(rt->ctx, col >= 0 && col < rt->C, HX_E_ARG, "column index out of range");
     if (strcmp(name, "premixed_table") == 0) {   // host-side: int32, the index of the column's table set
         HX_REQUIRE(rt->ctx, out_bytes == sizeof(int32_t), HX_E_ARG, "premixed_table is one int32");
@@ -1675,6 +1696,21 @@ int hx_rt_get(hx_rt* rt, int col, const char* name, void* out, size_t out_bytes)
     if (n == "opac_wg_int") return get_plain(rt, rt->opac_wg_int + c * nc * I, nc * I * 8, out, out_bytes);
     if (n == "scat_cross_lay") return get_plain(rt, rt->scat_cross_lay + c * X * I, X * L * 8, out, out_bytes);
     if (n == "scat_cross_int") return get_plain(rt, rt->scat_cross_int + c * X * I, X * I * 8, out, out_bytes);
+    // the cloud planes, whichever of hx_rt_set_column_clouds and hx_rt_set_column_cloud_decks filled them last
+    if (n == "abs_cross_all_clouds_lay") return get_plain(rt, rt->cl_abs_lay + c * X * I, X * L * 8, out, out_bytes);
+    if (n == "abs_cross_all_clouds_int") return get_plain(rt, rt->cl_abs_int + c * X * I, X * I * 8, out, out_bytes);
+    if (n == "scat_cross_all_clouds_lay") return get_plain(rt, rt->cl_sc_lay + c * X * I, X * L * 8, out, out_bytes);
+    if (n == "scat_cross_all_clouds_int") return get_plain(rt, rt->cl_sc_int + c * X * I, X * I * 8, out, out_bytes);
+    if (n == "g_0_all_clouds_lay" || n == "g_0_all_clouds_int") {
+        HX_REQUIRE(rt->ctx, rt->f.clouds == 1, HX_E_STATE, "object was created with clouds = 0");
+        return n == "g_0_all_clouds_lay" ? get_plain(rt, rt->cl_g0_lay + c * X * I, X * L * 8, out, out_bytes)
+                                         : get_plain(rt, rt->cl_g0_int + c * X * I, X * I * 8, out, out_bytes);
+    }
+    if (n == "cloud_deck_spectra") {   // [ndecks][3][nbin] of the column's last hx_rt_set_column_cloud_decks
+        HX_REQUIRE(rt->ctx, rt->cloud_ndecks > 0, HX_E_STATE, "no cloud decks have been set (hx_rt_set_column_cloud_decks)");
+        const size_t per = (size_t)rt->cloud_ndecks * 3 * X;
+        return get_plain(rt, rt->cloud_spec + c * per, per * 8, out, out_bytes);
+    }
     if (n == "g_0_tot_lay") return get_plain(rt, rt->g0_tot_lay + c * X * I, X * L * 8, out, out_bytes);
     if (n == "g_0_tot_int") return get_plain(rt, rt->g0_tot_int + c * X * I, X * I * 8, out, out_bytes);
     // mixing-ratio profiles as the last refresh used them, [nspecies][ninterface] (layer rows: the first nlayer entries)

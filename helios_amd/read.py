@@ -296,9 +296,10 @@ class Read(object):
         n_decks = max(int(cloud.nr_cloud_decks), 0)
 
         def per_deck(key, conv, flag):
-            """one value per deck from the parameter file; a command-line flag sets a single deck (read.py:759-787)"""
+            """one value per deck from the parameter file; a command-line flag sets a single deck (read.py:759-787) -- or
+            several, space-separated inside the one value (`-aerosol_radius_mode "1 5"`), as a cloud sweep writes them"""
             if flag and getattr(args, flag) is not None:
-                return [conv(getattr(args, flag))]
+                return [conv(v) for v in str(getattr(args, flag)).split()]
             return [conv(v) for v in str(val[key]).split()[:n_decks]]
         cloud.mie_path = per_deck("mie_path", str, "path_to_mie_files")
         cloud.cloud_r_mode = per_deck("cloud_r_mode", f64, "aerosol_radius_mode")

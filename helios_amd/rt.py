@@ -158,6 +158,37 @@ class RTBatch(object):
         self._ck(self._l.hx_rt_set_column_clouds(self.handle, col, *[_dp(a) for a in arrs]),
                  "hx_rt_set_column_clouds")
 
+    def add_mie_table(self, lamda_mie, scat, absorb):
+        """one aerosol's Mie table, resident once per batch: wavelengths [nw] in cm (ascending), scattering and absorption
+        cross-sections [nr][nw] per particle radius; returns its index"""
+        lam, sc, ab = _f64(lamda_mie), _f64(scat), _f64(absorb)
+        if sc.ndim != 2 or sc.shape != ab.shape or sc.shape[1] != lam.size:
+            raise ValueError("add_mie_table: scat %r and absorb %r must both be [nr][%d wavelengths]"
+                             % (sc.shape, ab.shape, lam.size))
+        idx = ctypes.c_int32(-1)
+        self._ck(self._l.hx_rt_add_mie_table(self.handle, _dp(lam), int(lam.size), _dp(sc), _dp(ab), int(sc.shape[0]),
+                                             ctypes.byref(idx)), "hx_rt_add_mie_table")
+        return int(idx.value)
+
+    def mie_table_count(self):
+        return int(self.get("mie_table_count", -1)[0])
+
+    def set_column_cloud_decks(self, col, mie_index, radius_weight, f_lay, f_int=None):
+        """the cloud decks of column `col` (< 0: all), built on the device: per deck the index of its Mie table, the radius
+        weights [ndecks][nr] and the mixing-ratio profiles [ndecks][nlayer] / [ndecks][ninterface] (f_int = None with
+        isothermal layers); fills the column's six cloud planes"""
+        idx = np.ascontiguousarray(mie_index, dtype=np.int32).reshape(-1)
+        w, fl = np.atleast_2d(_f64(radius_weight)), np.atleast_2d(_f64(f_lay))
+        fi = None if f_int is None else np.atleast_2d(_f64(f_int))
+        nd = idx.size
+        if w.shape[0] != nd or fl.shape != (nd, self.nlayer) or (fi is not None and fi.shape != (nd, self.ninterface)):
+            raise ValueError("set_column_cloud_decks: %d decks need radius_weight [%d][nr], f_lay [%d][%d] and f_int [%d][%d]"
+                             % (nd, nd, nd, self.nlayer, nd, self.ninterface))
+        self._ck(self._l.hx_rt_set_column_cloud_decks(self.handle, int(col), nd, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                      _dp(w), int(w.shape[1]), _dp(fl), _dp(fi)),
+                 "hx_rt_set_column_cloud_decks")
+        self._cloud_ndecks = nd
+
     def set_column_heating(self, col, F_add_heat_lay, F_add_heat_sum):
         a, b = _f64(F_add_heat_lay), _f64(F_add_heat_sum)
         self._ck(self._l.hx_rt_set_column_heating(self.handle, col, _dp(a), _dp(b)), "hx_rt_set_column_heating")
@@ -242,6 +273,11 @@ class RTBatch(object):
             "kappa_lay": (L, np.float64), "kappa_int": (L + 1, np.float64), "c_p_lay": (L, np.float64),
             "F_smooth_sum": (L, np.float64), "F_add_heat_lay": (L, np.float64), "F_add_heat_sum": (L, np.float64),
             "planck_grid": ((self.dims.plancktable_dim + 1) * X, np.float64),
+            "abs_cross_all_clouds_lay": (X * L, np.float64), "abs_cross_all_clouds_int": (X * I, np.float64),
+            "scat_cross_all_clouds_lay": (X * L, np.float64), "scat_cross_all_clouds_int": (X * I, np.float64),
+            "g_0_all_clouds_lay": (X * L, np.float64), "g_0_all_clouds_int": (X * I, np.float64),
+            "cloud_deck_spectra": (max(1, getattr(self, "_cloud_ndecks", 0)) * 3 * X, np.float64),
+            "mie_table_count": (1, np.int32),
             "vmr_lay": (max(1, self.dims.nspecies) * I, np.float64), "vmr_int": (max(1, self.dims.nspecies) * I, np.float64),
         }
         return table[name]

@@ -28,9 +28,16 @@ from . import write as write_mod
 # (T, P) mixing-ratio tables on the device, hx_rt_set_column_vmr_table; path_to_opacity_file: the same sweep on the premixed
 # path, one premixed k-table file per chemistry -- every distinct table is resident once per GPU and every column reads its
 # own, hx_rt_add_premixed_tables / hx_rt_set_column_table)
+# (the cloud options: every column describes its own decks -- aerosol, size distribution, base and vertical profile; several
+# decks are space-separated inside one value, as on the command line: "aerosol_radius_mode=1 5,10 5" is two columns of two
+# decks.  The number of decks defines the batch.  The planes are built on the device per column from Mie tables resident once
+# per batch, hx_rt_add_mie_table / hx_rt_set_column_cloud_decks -- or on the host, HELIOS_CLOUD_DECKS)
+CLOUD_OPTIONS = ("path_to_mie_files", "aerosol_radius_mode", "aerosol_radius_geometric_std_dev", "cloud_bottom_pressure",
+                 "cloud_bottom_mixing_ratio", "cloud_to_gas_scale_height_ratio", "path_to_file_with_cloud_data", "aerosol_name")
 PER_COLUMN_OPTIONS = ("internal_temperature", "f_factor", "stellar_zenith_angle", "surface_albedo", "surface_gravity",
                       "orbital_distance", "radius_planet", "radius_star", "temperature_star",
-                      "radiative_equilibrium_criterion", "directory_with_fastchem_files", "path_to_opacity_file", "name")
+                      "radiative_equilibrium_criterion", "directory_with_fastchem_files", "path_to_opacity_file",
+                      "name") + CLOUD_OPTIONS
 
 _TABLE_NAMES = ("opacity_mixing", "opac_k", "opac_scat_cross", "opac_meanmass", "opac_wave", "opac_interwave",
                 "opac_deltawave", "gauss_y", "ktemp", "kpress", "nbin", "ny", "ntemp", "npress")
@@ -46,6 +53,18 @@ def expand_sweep(spec):
             raise ValueError("option '%s' cannot vary inside one batch; allowed: %s" % (key, ", ".join(PER_COLUMN_OPTIONS)))
         axes.append([(key, v.strip()) for v in values.split(",") if v.strip()])
     return [dict(combo) for combo in itertools.product(*axes)] if axes else [{}]
+
+
+def cloud_deck_mode(overrides_list):
+    """where the cloud planes of a sweep's columns are built, HELIOS_CLOUD_DECKS=host|device: on the host by
+    Cloud.cloud_pre_processing and uploaded, or on the device from the deck descriptions.  Default: device when a cloud option
+    is among the sweep's axes, host otherwise (no result of a sweep without a cloud axis moves)"""
+    mode = os.environ.get("HELIOS_CLOUD_DECKS")
+    if mode is None:
+        return "device" if any(k in CLOUD_OPTIONS for ov in overrides_list for k in ov) else "host"
+    if mode not in ("host", "device"):
+        raise ValueError("HELIOS_CLOUD_DECKS=%s: the cloud planes are built on 'host' or 'device'" % mode)
+    return mode
 
 
 def _table_entry(keeper):
@@ -109,7 +128,12 @@ def _prepare_column(base_argv, overrides, shared):
         hsfunc.approx_f_from_formula(keeper, reader)
     hsfunc.calc_F_intern(keeper)
     add_heat.load_heating_terms_or_not(keeper)
-    reader.cloud.cloud_pre_processing(keeper)
+    if shared.get("cloud_decks", "host") == "device" and keeper.clouds == 1:
+        # the decks' description only: the planes are built on the device (make_rt_batch); a Mie directory is read once per
+        # process, as the table files are
+        reader.cloud.cloud_deck_description(keeper, shared.setdefault("mie", {}))
+    else:
+        reader.cloud.cloud_pre_processing(keeper)
     keeper.create_zero_arrays()
     # the table's arrays are in their final form already and stay ONE per process (_table_entry)
     keeper.convert_input_list_to_array(skip=[n for n, v in tables[key].items() if isinstance(v, np.ndarray)])
@@ -269,6 +293,11 @@ def _convection_loop(computer, quants, rt):
 
 def _finish_column(computer, q, reader, writer):
     """post-loop diagnostics and output files of one column (helios.py:88-126), on the Store's own device arrays"""
+    if getattr(q, "cloud_decks", None) is not None and q.clouds == 1:
+        # planes built on the device: the diagnostics and the output files read them from the Store
+        for n in ("abs_cross_all_clouds", "scat_cross_all_clouds", "g_0_all_clouds"):
+            for lev in ("_lay", "_int"):
+                setattr(q, n + lev, q.rt.get(n + lev, q.rt_col))
     tables = {n: getattr(q, n, None) for n in ("opac_k", "opac_scat_cross", "opac_meanmass")}
     for n in tables:                  # the look-up tables live in the batch; the diagnostics do not touch them
         setattr(q, n, np.zeros(1))
@@ -364,9 +393,10 @@ def run_sweep(base_argv, overrides_list, dist=None, coll_device="cpu", write_out
     # HELIOS_SWEEP_PARTITION=dynamic[:chunk]: a shared work list instead -- every rank claims `chunk` columns (default:
     # an eighth of its even share), runs them as one batch, retires them and claims again until the list is empty
     mode = os.environ.get("HELIOS_SWEEP_PARTITION", "cyclic")
+    decks_on = cloud_deck_mode(overrides_list)      # (refuses an unknown HELIOS_CLOUD_DECKS before anything is set up)
     computer = comp.Compute()
     writer = write_mod.Write()
-    shared = {}
+    shared = {"cloud_decks": decks_on}
     columns = []
     import time
     timing = dict(batch=0.0, loops=0.0, finish=0.0)

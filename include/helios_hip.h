@@ -367,6 +367,8 @@ typedef struct hx_rt_column {
 } hx_rt_column;
 
 int hx_rt_struct_sizes(int* dims_size, int* flags_size, int* column_size);
+/* nlayer >= 1.  A one-layer batch takes every input and builds and returns cloud planes; hx_rt_refresh, hx_rt_step, hx_rt_run,
+ * hx_rt_kappa_cp_refresh and the hx_rt_conv_* calls need two layers and return HX_E_UNSUPPORTED for it, before any launch. */
 int hx_rt_create(hx_context* ctx, const hx_rt_dims* dims, const hx_rt_flags* flags,
                  const hx_rt_column* columns, hx_rt** out_rt);
 int hx_rt_destroy(hx_rt* rt);
@@ -426,6 +428,27 @@ int hx_rt_set_column_clouds(hx_rt* rt, int col, const double* abs_cross_lay,
                             const double* g_0_int);
 int hx_rt_set_column_heating(hx_rt* rt, int col, const double* F_add_heat_lay,
                              const double* F_add_heat_sum);
+/* Cloud decks built on the device (helios_amd/csrc/clouds.hip), the counterpart of Cloud.cloud_pre_processing for the columns
+ * of a batch.  hx_rt_add_mie_table makes one aerosol's Mie table resident -- lamda_mie[nw] in cm, strictly ascending;
+ * scat[nr][nw] and absorb[nr][nw], one row per particle radius -- once per batch, however many columns or decks use it, and
+ * returns its index.  hx_rt_set_column_cloud_decks describes the ndecks decks of column col (col < 0: all columns): per deck the
+ * index of its Mie table, the radius weights radius_weight[ndecks][nr] (size-distribution density times radius interval) and the
+ * mixing-ratio profiles f_lay[ndecks][nlayer], f_int[ndecks][ninterface] (f_int = NULL with iso = 1: the interface planes stay as
+ * they are).  It forms the weighted sums over the radii, re-bins them onto the bins of hx_rt_set_grid under the contract of
+ * tools.convert_spectrum with int_lambda = opac_interwave (absorption and scattering: type "log", evaluated as exp of a sum of
+ * logarithms; the third spectrum, the scattering-weighted sum again: type "linear") and writes the column's six cloud planes:
+ * sums over the decks in deck order of f * a, f * s and f * (g * s), products and sums rounded separately, the last divided by
+ * the scattering sum where that is > 0.  The number of decks is fixed by the batch's first call.  Whichever of this call and
+ * hx_rt_set_column_clouds comes last owns a column's planes.
+ * hx_rt_get reads back "mie_table_count" (col = -1, one int32), the six planes under their names "abs_cross_all_clouds_lay",
+ * "scat_cross_all_clouds_lay", "g_0_all_clouds_lay" ([nlayer][nbin]) and "..._int" ([ninterface][nbin]), and
+ * "cloud_deck_spectra" ([ndecks][3][nbin]: absorption, scattering, third spectrum of the column's last deck call).
+ * Errors name the offending value -- a table index out of range, nr not matching the table, clouds = 0 in the batch's flags,
+ * wavelengths not ascending -- and launch nothing; the batch stays usable and destroyable. */
+int hx_rt_add_mie_table(hx_rt* rt, const double* lamda_mie, int nw, const double* scat, const double* absorb, int nr,
+                        int* out_index);
+int hx_rt_set_column_cloud_decks(hx_rt* rt, int col, int ndecks, const int* mie_index, const double* radius_weight, int nr,
+                                 const double* f_lay, const double* f_int);
 int hx_rt_set_temperatures(hx_rt* rt, int col, const double* T_lay);
 int hx_rt_set_convergence_limit(hx_rt* rt, int col, double limit);
 /* builds the Planck table (+ incident-energy correction) on the device */
