@@ -37,7 +37,7 @@ CLOUD_OPTIONS = ("path_to_mie_files", "aerosol_radius_mode", "aerosol_radius_geo
 PER_COLUMN_OPTIONS = ("internal_temperature", "f_factor", "stellar_zenith_angle", "surface_albedo", "surface_gravity",
                       "orbital_distance", "radius_planet", "radius_star", "temperature_star",
                       "radiative_equilibrium_criterion", "directory_with_fastchem_files", "path_to_opacity_file",
-                      "name") + CLOUD_OPTIONS
+                      "dataset_in_stellar_spectrum_file", "path_to_stellar_spectrum_file", "name") + CLOUD_OPTIONS
 
 _TABLE_NAMES = ("opacity_mixing", "opac_k", "opac_scat_cross", "opac_meanmass", "opac_wave", "opac_interwave",
                 "opac_deltawave", "gauss_y", "ktemp", "kpress", "nbin", "ny", "ntemp", "npress")
@@ -77,6 +77,23 @@ def _table_entry(keeper):
             v = getattr(keeper, n)
             entry[n] = keeper.as_input_array(v) if isinstance(v, (np.ndarray, list, tuple)) else v
     return entry
+
+
+def _read_star(reader, keeper, shared):
+    """Read.read_star with every stellar spectrum file opened once per process: the columns of a sweep over
+    dataset_in_stellar_spectrum_file name data sets of the same file (star.py writes them side by side)"""
+    files = shared.setdefault("stellar_files", {})
+
+    def opened(path):
+        key = os.path.realpath(str(path))
+        if key not in files:
+            files[key] = read_mod.Read._open_table(path)
+        return files[key]
+    reader._open_table = opened
+    try:
+        reader.read_star(keeper)
+    finally:
+        del reader._open_table
 
 
 def _prepare_column(base_argv, overrides, shared):
@@ -119,7 +136,7 @@ def _prepare_column(base_argv, overrides, shared):
     reader.read_kappa_table_or_use_constant_kappa(keeper)
     reader.read_or_fill_surf_albedo_array(keeper)
     keeper.dimensions()
-    reader.read_star(keeper)
+    _read_star(reader, keeper, shared)
     hsfunc.planet_param(keeper, reader)
     hsfunc.set_up_numerical_parameters(keeper)
     hsfunc.construct_grid(keeper)
@@ -158,7 +175,8 @@ def _batch_signature(q):
                  for sp in (getattr(q, "species_list", None) or [])) if str(q.opacity_mixing) == "on-the-fly" else ()
     return (int(q.nbin), int(q.ny), int(q.nlayer), int(q.scat), int(q.dir_beam), int(q.clouds), int(q.scat_corr),
             int(q.smooth), int(q.convection), str(q.opacity_mixing), float(q.g_0), float(q.epsi), str(q.planet_type),
-            int(q.iso), int(q.singlewalk), str(q.flux_calc_method), chem, _table_grid_digest(q))
+            int(q.iso), int(q.singlewalk), str(q.flux_calc_method), chem, _table_grid_digest(q),
+            int(getattr(q, "real_star", 0)))      # (a flag of the whole batch: black-body stars and spectra from a file do not mix)
 
 
 def _radiation_loop(computer, quants, rt):

@@ -589,6 +589,39 @@ int hx_ktable_get(hx_ktable* kt, const char* name, void* out, size_t out_bytes);
 int hx_continuum_table(hx_context* ctx, int kind, const double* coef, int ncoef, const double* wave, int nbin, int ny,
                        const double* temp, int ntemp, const double* press, int npress, double* out, int first_row, int rows);
 
+/* ---- (8) stellar spectra from model grids, re-binned onto the opacity grid (csrc/star.hip; the contract and the host side are
+ * helios_amd/star.py) -----------------------------------------------------------------------------------------------------------
+ * The reference's star tool: a star's spectrum is the blend of up to eight corner spectra of a model grid (or a spectrum put as
+ * it is), re-binned onto the opacity grid by the linear mode of its convert_spectrum, bins that the table does not cover taking
+ * pi x the analytic Planck integral over the bin.  All stars of one handle share the tabulated wavelengths and the grid.
+ *
+ *   hx_star_create      tabulated wavelengths, corner slots, stars, bins, and the number of trapezoids of a long bin that are
+ *                       staged and summed at a time (a power of two of 64 ... 2048; part of the result's definition: a bin of
+ *                       more than 16 points is the in-order sum of its chunks' tree sums, a shorter one the plain running sum)
+ *   hx_star_add_corner  fp32 flux[n_points] of one corner file into a slot; a file that several stars use is added once
+ *   hx_star_set_grid    lamda[n_points] ascending (cm), interfaces[n_bins + 1] ascending, and per interface: state 0 when it lies
+ *                       below the first or above the last tabulated wavelength (its value stays 0), else 1 with p_bot = the
+ *                       number of tabulated wavelengths below it, less one (-1 on the first one: the index wraps, as the
+ *                       reference's does).  Indices that would read outside the table are refused with HX_E_ARG
+ *   hx_star_set_star    star s = (sum over n_terms of ((f[slots[k]] * w[3k]) * w[3k + 1]) * w[3k + 2]) / divisor, in that order,
+ *                       fp64; 1, 2, 4 or 8 terms, factors a branch does not have are 1
+ *   hx_star_put_flux    fp64 flux[n_points] of star s as it is, in place of a blend
+ *   hx_star_run         stages 1 (blend), 2 (Planck values at bb_temp[s]; 0 K: none, the values are 0; bb_prefactor[s] is
+ *                       2 (k/h)^3 k T^4 / c^2 as the host forms it, hc and kb the host's constants), 4 (re-binning), or their
+ *                       sum, for the stars 0 ... n_stars - 1.  Returns when the kernels are launched
+ *   hx_star_get         "flux" [s][n_points], "converted" and "planck" [s][n_bins], "timing_ms" (double[4]: ms in k_star_blend,
+ *                       in k_star_planck_bins, in the re-binning kernels; runs)
+ */
+typedef struct hx_star hx_star;
+int hx_star_create(hx_context* ctx, int n_points, int n_corners, int n_stars, int n_bins, int chunk, hx_star** out_st);
+int hx_star_destroy(hx_star* st);
+int hx_star_add_corner(hx_star* st, int slot, const void* flux_f32);
+int hx_star_set_grid(hx_star* st, const double* lamda, const double* interfaces, const int* p_bot, const int* state);
+int hx_star_set_star(hx_star* st, int s, int n_terms, const int* slots, const double* weights, double divisor);
+int hx_star_put_flux(hx_star* st, int s, const double* flux);
+int hx_star_run(hx_star* st, int n_stars, const double* bb_temp, const double* bb_prefactor, double hc, double kb, int stages);
+int hx_star_get(hx_star* st, const char* name, void* out, size_t out_bytes);
+
 #ifdef __cplusplus
 }
 #endif
