@@ -3,9 +3,10 @@
 // source/computation.py:992-1174).  Here one workgroup per column runs it, so that the fused path needs no
 // host round trip inside the convection loop either.
 //
-// The logic is sequential over at most a few hundred layers and is executed by thread 0 exactly in the
-// order of helios_amd/host_functions.py (which tests/test_host_golden.py pins to the reference's Python);
-// only the pressure-ratio powers -- independent of temperature -- are tabulated by all threads first:
+// The zone arithmetic (conv_correct_zones, conv_stitch_holes) is sequential over at most a few hundred layers and is
+// executed by thread 0 exactly in the order of helios_amd/host_functions.py (which tests/test_host_golden.py pins to the
+// reference's Python); the element-wise checks and the zone boundaries are workgroup-cooperative (below), and the
+// pressure-ratio powers -- independent of temperature -- are tabulated by all threads first:
 //     lim+(i) = (T[i] * f1p[i]) * f2p[i]   adiabat through layer i, kappa * (1 + 1e-6)   (conv_check)
 //     lim-(i) = (T[i] * f1m[i]) * f2m[i]   the same with kappa * (1 - 1e-6)              (mark_convective_layers)
 //     up[i]   = (p_lay[i]/p_int[i])^kappa_int[i],  nxt[i] = (p_int[i+1]/p_lay[i])^kappa_lay[i]   (conv_correct)
@@ -104,27 +105,7 @@ __device__ inline void conv_stage_out(const ConvColumn& c, const ConvColumn& g, 
     }
 }
 
-// ---- everything below: one thread -------------------------------------------------------------------------
-
-// host_functions.py:337-365; returns the number of flagged entries
-__device__ inline int conv_check(const ConvColumn& c, const ConvTables& t) {
-    const int L = c.L;
-    int n = 0;
-    for (int i = 0; i <= L; i++) c.conv_unstable[i] = 0;
-    for (int i = 0; i < L - 1; i++) {
-        if (c.p_lay[i] <= 1e1) break;  // the top of the atmosphere is left alone
-        if (c.T[i + 1] < (c.T[i] * t.f1p[i]) * t.f2p[i]) {
-            c.conv_unstable[i] = 1;
-            c.conv_unstable[i + 1] = 1;
-        }
-    }
-    if (c.T[0] < c.T[L] * t.surf_p) {
-        c.conv_unstable[L] = 1;
-        c.conv_unstable[0] = 1;
-    }
-    for (int i = 0; i <= L; i++) n += c.conv_unstable[i];
-    return n;
-}
+// ---- one thread (thread 0 of the workgroup-cooperative forms below calls them) -----------------------------------
 
 // host_functions.py:585-635: radiative gaps thinner than one scale height between two zones are closed
 __device__ inline void conv_stitch_holes(const ConvColumn& c, ConvTables& t) {
@@ -147,44 +128,6 @@ __device__ inline void conv_stitch_holes(const ConvColumn& c, ConvTables& t) {
         if (p_top / p_bot > 1 / 2.718281828459045)
             for (int m = t.ends[n] + 1; m < t.starts[n + 1]; m++) c.conv_layer[m] = 1;
     }
-}
-
-// host_functions.py:545-582
-__device__ inline void conv_mark_layers(const ConvColumn& c, ConvTables& t, int stitching) {
-    const int L = c.L;
-    c.conv_layer[L] = 0;
-    c.conv_layer[0] = 0;
-    for (int i = 0; i < L - 1; i++) {
-        if (c.p_lay[i] <= 1e1) break;
-        if (c.T[i + 1] < (c.T[i] * t.f1m[i]) * t.f2m[i]) {
-            c.conv_layer[i] = 1;
-            c.conv_layer[i + 1] = 1;
-        } else {
-            c.conv_layer[i + 1] = 0;
-        }
-    }
-    for (int i = 0; i < L - 1; i++)  // no temperature kinks at the top edge of a zone
-        if (c.T[i + 1] > c.T[i]) c.conv_layer[i] = 0;
-    if (c.T[0] < c.T[L] * t.surf_m) {
-        c.conv_layer[L] = 1;
-        c.conv_layer[0] = 1;
-    }
-    if (stitching == 1 && c.itervalue > 5000) conv_stitch_holes(c, t);
-}
-
-// contiguous runs of flagged layers, the surface "ghost layer" (index L) counted as layer -1
-__device__ inline int conv_zones(const ConvColumn& c, ConvTables& t) {
-    const int L = c.L;
-    for (int i = 0; i < L; i++) t.in_zone[i + 1] = (c.conv_unstable[i] == 1 || c.conv_layer[i] == 1) ? 1 : 0;
-    t.in_zone[0] = (c.conv_unstable[L] == 1 || c.conv_layer[L] == 1) ? 1 : 0;
-    t.in_zone[L + 1] = 0;
-    int ns = 0, ne = 0;
-    for (int i = -1; i < L; i++) {
-        if (!t.in_zone[i + 1]) continue;
-        if (i == -1 || !t.in_zone[i]) t.starts[ns++] = i;
-        if (!t.in_zone[i + 2]) t.ends[ne++] = i;
-    }
-    return ns == ne ? ns : 0;
 }
 
 // host_functions.py:368-506: every zone goes onto the adiabat of its enthalpy-conserving mean potential temperature
@@ -232,23 +175,6 @@ __device__ inline void conv_correct_zones(const ConvColumn& c, ConvTables& t, in
     }
 }
 
-__device__ inline void conv_correct(const ConvColumn& c, ConvTables& t, int fudging) {
-    conv_correct_zones(c, t, fudging, conv_zones(c, t));
-}
-
-// host_functions.py:509-542
-__device__ inline void convective_adjustment(const ConvColumn& c, ConvTables& t) {
-    int unstable = conv_check(c, t);
-    int guard = 0;
-    while (unstable > 0 && guard++ < 100000) {
-        conv_mark_layers(c, t, 0);
-        conv_correct(c, t, 0);
-        unstable = conv_check(c, t);
-    }
-    conv_mark_layers(c, t, 1);
-    conv_correct(c, t, 1);
-}
-
 // ---- workgroup-cooperative forms (all threads call them; they contain barriers) -------------------------------
 // The element-wise parts of conv_check / conv_mark_layers are evaluated by all threads; what the reference's
 // sequential loops leave behind is reproduced exactly:
@@ -271,7 +197,8 @@ __device__ inline void conv_find_lim(const ConvColumn& c, ConvShared& sh, int ti
     __syncthreads();
 }
 
-// conv_zones by the whole workgroup: the flags by all threads, the (few) zone boundaries compacted by the first
+// the zones of conv_correct (contiguous runs of flagged layers, the surface "ghost layer" -- index L -- counted as
+// layer -1) by the whole workgroup: the flags by all threads, the (few) zone boundaries compacted by the first
 // wavefront with ballots, in ascending order as the sequential walk finds them.  Returns the number of zones (uniform).
 __device__ inline int conv_zones_wg(const ConvColumn& c, ConvTables& t, ConvShared& sh, int tid, int nthr) {
     const int L = c.L;
@@ -368,7 +295,7 @@ __device__ inline void convective_adjustment_wg(const ConvColumn& c, ConvTables&
     __syncthreads();
 }
 
-// check_for_radiative_eq by all threads; returns the criterion (uniform)
+// check_for_radiative_eq (host_functions.py:251-286) by all threads; fills marked_red, returns the criterion (uniform)
 __device__ inline int conv_radiative_eq_wg(const ConvColumn& c, ConvShared& sh, int* s_convective, int tid, int nthr) {
     const int L = c.L;
     const double norm = c.F_down_tot[L] + c.F_intern;
@@ -389,25 +316,6 @@ __device__ inline int conv_radiative_eq_wg(const ConvColumn& c, ConvShared& sh, 
     if (conv) atomicAdd(s_convective, conv);
     __syncthreads();
     return sh.count == (L + 1) - *s_convective ? 1 : 0;
-}
-
-// host_functions.py:251-286: local radiative equilibrium of the non-convective layers; fills marked_red
-__device__ inline int conv_radiative_eq(const ConvColumn& c) {
-    const int L = c.L;
-    const double norm = c.F_down_tot[L] + c.F_intern;
-    int converged = 0, convective = 0;
-    for (int i = 0; i <= L; i++) {
-        c.marked_red[i] = 0;
-        convective += c.conv_layer[i];
-        if (c.conv_layer[i] != 0) continue;
-        const double dF = i < L ? fabs(c.F_intern + c.F_add_heat_sum[i] + c.F_smooth_sum[i] - c.F_net[i + 1])
-                                : fabs(c.F_intern - c.F_net[0]);
-        if (dF < c.rad_convergence_limit * norm)
-            converged++;
-        else
-            c.marked_red[i] = 1;
-    }
-    return converged == (L + 1) - convective ? 1 : 0;
 }
 
 }  // namespace hx
