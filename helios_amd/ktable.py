@@ -522,9 +522,26 @@ def parse_args(argv=None):
     p.add_argument("-continuum_species", default=None, help="analytic containers on the target grid: H- (H-_bf and H-_ff), He-")
     p.add_argument("-rayleigh_species", default=None, help="species of scat_cross_sections: H2, He, H, CO2, CO, O2, N2, e-")
     p.add_argument("-grid_like", default=None, help="an _opac_ip_kdistr container whose grid the analytic tables take")
+    p.add_argument("-individual_species_calculation", default=None, choices=("yes", "no"),
+                   help="stage 1; by default exactly when -path_to_individual_species_file is given")
+    p.add_argument("-mixed_table_production", default="no", choices=("yes", "no"),
+                   help="stage 2: mixed_opac_kdistr from the containers of -directory_with_individual_files (ktable_mix.py)")
+    p.add_argument("-path_to_final_species_file", default=None)
+    p.add_argument("-path_to_fastchem_output", default=None)
+    p.add_argument("-mixed_table_output_directory", default="./output/")
+    p.add_argument("-units_of_mixed_opacity_table", default="CGS", choices=("CGS", "MKS"))
+    p.add_argument("-sweep", default=None, help="\"path_to_fastchem_output=a/,b/\": one mixed table per FastChem directory")
     opt = p.parse_args(argv)
-    if opt.path_to_individual_species_file is None and opt.continuum_species is None and opt.rayleigh_species is None:
-        p.error("one of -path_to_individual_species_file, -continuum_species, -rayleigh_species is required")
+    if opt.individual_species_calculation is None:
+        opt.individual_species_calculation = "yes" if opt.path_to_individual_species_file is not None else "no"
+    elif opt.individual_species_calculation == "yes" and opt.path_to_individual_species_file is None:
+        p.error("-individual_species_calculation yes needs -path_to_individual_species_file")
+    if (opt.individual_species_calculation == "no" and opt.continuum_species is None and opt.rayleigh_species is None
+            and opt.mixed_table_production != "yes"):
+        p.error("one of -path_to_individual_species_file, -continuum_species, -rayleigh_species, -mixed_table_production yes "
+                "is required")
+    if opt.sweep is not None and opt.mixed_table_production != "yes":
+        p.error("-sweep goes with -mixed_table_production yes")
     if opt.format == "sampling":
         raise IOError("ktable: format = sampling is not built; this tool makes k-distribution tables")
     if opt.format != "k-distribution":
@@ -571,18 +588,19 @@ def analytic_tables(opt, inter, ctx):
 
 
 def main(argv=None):
-    """ktable.py: one table per species of the list (and its re-gridded twin), then the analytic tables asked for; returns the
-    paths written"""
+    """ktable.py: one table per species of the list (and its re-gridded twin), then the analytic tables asked for, then the
+    mixed table; returns the paths written"""
     opt = parse_args(argv)
     inter = wavelength_grid(opt.grid_format, opt.wavelength_grid.split(), opt.path_to_grid_file)
     target = target_grid(opt.temperature_grid, opt.pressure_grid) if opt.interpolate == "yes" else None
     ctx = None
-    if opt.backend == "hip" and (opt.path_to_individual_species_file or opt.continuum_species is not None):
+    stage1, stage2 = opt.individual_species_calculation == "yes", opt.mixed_table_production == "yes"
+    if opt.backend == "hip" and (stage1 or opt.continuum_species is not None or stage2):
         from .device import Context
         ctx = Context(int(os.environ.get("HELIOS_DEVICE", "0")))
     written = []
     try:
-        species = read_species_list(opt.path_to_individual_species_file) if opt.path_to_individual_species_file else []
+        species = read_species_list(opt.path_to_individual_species_file) if stage1 else []
         for name, path in species:
             timing = {}
             native, ip = build_species(path, inter, opt.number_of_gaussian_points, opt.helios_k_output_format, opt.backend, ctx,
@@ -596,6 +614,9 @@ def main(argv=None):
                      timing["seconds"], written[-1]))
         if opt.continuum_species is not None or opt.rayleigh_species is not None:
             written += analytic_tables(opt, inter, ctx)
+        if stage2:
+            from . import ktable_mix
+            written += ktable_mix.run(opt, inter, ctx)
     finally:
         if ctx is not None:
             ctx.close()

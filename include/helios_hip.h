@@ -622,6 +622,43 @@ int hx_star_put_flux(hx_star* st, int s, const double* flux);
 int hx_star_run(hx_star* st, int n_stars, const double* bb_temp, const double* bb_prefactor, double hc, double kb, int stages);
 int hx_star_get(hx_star* st, const char* name, void* out, size_t out_bytes);
 
+/* ---- (9) the mixing stage of the k-table tool: premixed tables by weighted sum (csrc/ktable_mix.hip; the contract and the host
+ * side are helios_amd/ktable_mix.py) ------------------------------------------------------------------------------------------
+ * Stage 2 of the reference's k-table tool (combination.py): kpoints[t][p][x][y] = sum over the absorbers, in slot order, of
+ * m_s[t,p] * k_s[t][p][x][y], and scat[t][p][x] = sum over the scattering species, in slot order, of x_s[t,p] * sigma_s; one
+ * rounded product and one rounded add per term.  The species' tables on the final grid stay on the device: a further chemistry
+ * is one hx_ktmix_run.
+ *
+ *   hx_ktmix_create              bins, Gauss points, nodes of the final grid (node = p + np * t), species slots.  Allocates the
+ *                                accumulator and the Rayleigh table, each with one guard row behind it that no kernel touches;
+ *                                a species' slot is allocated when its table arrives.  An allocation that the device's free
+ *                                memory cannot hold is refused with the number of bytes in the message
+ *   hx_ktmix_set_grid            wave[nbin] bin centres (cm), temp[nt] (K), press[np] (dyne cm^-2), all > 0
+ *   hx_ktmix_set_species         a table [nt][np][nbin][ny] on the final grid into slot s, uploaded in pieces of 64 MiB; NULL: the
+ *                                species does not absorb (its slot is freed)
+ *   hx_ktmix_set_species_native  a table on its own nt_old x np_old nodes: uploaded, re-gridded into the slot by k_ktmix_regrid
+ *                                (hx_ktable_regrid's plan arrays, branches and term order), the native copy freed
+ *   hx_ktmix_set_rayleigh        sigma[nbin] of slot s; is_h2o = 1 (with sigma NULL): water vapour, evaluated per node and bin
+ *                                by stage 2's own formula; NULL and 0: the species contributes nothing
+ *   hx_ktmix_run                 one chemistry: mmr[nspecies][nt * np] (the mass mixing ratios, read for the absorbing slots)
+ *                                and vmr_scat[nspecies][nt * np]; both tables are refilled from zeros
+ *   hx_ktmix_get                 "kpoints", "scat_cross", "species_<s>" (the slot), "kpoints_guard" [nbin * ny] and
+ *                                "scat_cross_guard" [nbin] (the guard rows: every double the bit pattern 0x7ff8dead0badbeef),
+ *                                "timing_ms" (double[4]: ms in k_ktmix_sum and in k_ktmix_scat of the last run, ms in
+ *                                k_ktmix_regrid so far, runs)
+ */
+typedef struct hx_ktmix hx_ktmix;
+int hx_ktmix_create(hx_context* ctx, int nbin, int ny, int nt, int np, int nspecies, hx_ktmix** out_km);
+int hx_ktmix_destroy(hx_ktmix* km);
+int hx_ktmix_set_grid(hx_ktmix* km, const double* wave, const double* temp, const double* press);
+int hx_ktmix_set_species(hx_ktmix* km, int s, const double* k_on_final_grid);
+int hx_ktmix_set_species_native(hx_ktmix* km, int s, const double* k_native, int nt_old, int np_old, const int* t_left,
+                                const int* t_reduced, const int* p_left, const int* p_reduced, const double* temp_old,
+                                const double* logp_old, const double* temp_new, const double* logp_new);
+int hx_ktmix_set_rayleigh(hx_ktmix* km, int s, const double* sigma, int is_h2o);
+int hx_ktmix_run(hx_ktmix* km, const double* mmr, const double* vmr_scat);
+int hx_ktmix_get(hx_ktmix* km, const char* name, void* out, size_t out_bytes);
+
 #ifdef __cplusplus
 }
 #endif
