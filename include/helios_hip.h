@@ -659,6 +659,28 @@ int hx_ktmix_set_rayleigh(hx_ktmix* km, int s, const double* sigma, int is_h2o);
 int hx_ktmix_run(hx_ktmix* km, const double* mmr, const double* vmr_scat);
 int hx_ktmix_get(hx_ktmix* km, const char* name, void* out, size_t out_bytes);
 
+/* ---- (10) Lorenz-Mie series per (size parameter, refractive index) pair (csrc/mie.hip; the contract and the host side are
+ * helios_amd/mie.py) ----------------------------------------------------------------------------------------------------------
+ * Per pair: N = floor(x + 4.05 x^(1/3) + 2) terms of a_n, b_n with D_n(m x) started at N from Lentz's continued fraction, taken
+ * downward and kept in a bounded device buffer laid out [n][lane] per wavefront; Q_ext, Q_sca and g from the upward sums.  One
+ * thread per pair, a wavefront's pairs consecutive in `order`; the buffer is filled and k_mie launched as often as the pairs need.
+ *
+ *   hx_mie_create   pairs per run at most, and the bytes of the D buffer (16 per term and pair, and 16 more per pair)
+ *   hx_mie_run      x[n_pairs] finite and > 0, m_re > 0, m_im >= 0, order[n_pairs] a permutation of 0 ... n_pairs - 1: the
+ *                   sequence in which the pairs are dealt to lanes (by N, descending, for wavefronts of equal loop lengths).
+ *                   Refused with HX_E_ARG and the offending value in the message, before anything is launched: a value outside
+ *                   these ranges, an order that is no permutation, a pair whose D_n alone exceed the buffer.  The handle stays
+ *                   usable.  Returns when the results are there
+ *   hx_mie_get      "q_ext", "q_sca", "g" (the first out_bytes / 8 pairs, in the order of the input), "guard" (double[5]: the
+ *                   double behind each of the three result arrays and the two behind the D buffer, every one the bit pattern
+ *                   0x7ff8dead0badbeef), "timing_ms" (double[2]: ms in k_mie and its launches, of the last run)
+ */
+typedef struct hx_mie hx_mie;
+int hx_mie_create(hx_context* ctx, int n_pairs_max, size_t scratch_bytes, hx_mie** out_mie);
+int hx_mie_destroy(hx_mie* mie);
+int hx_mie_run(hx_mie* mie, int n_pairs, const double* x, const double* m_re, const double* m_im, const int* order);
+int hx_mie_get(hx_mie* mie, const char* name, void* out, size_t out_bytes);
+
 #ifdef __cplusplus
 }
 #endif
