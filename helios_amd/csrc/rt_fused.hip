@@ -1137,7 +1137,7 @@ int hx_rt_refresh(hx_rt* rt) {
     return 0;
 }
 
-namespace { int kappa_cp_from_table(hx_rt* rt, bool refresh_T_int); }
+namespace { int kappa_cp_from_table(hx_rt* rt, bool refresh_T_int, bool time_stepped_only = false); }
 
 // debug = 1: the negative-flux warnings of fband_noniso (kernels.cu:1663 ff.) as counts over the state the sweeps leave
 // behind (up-fluxes always, down-fluxes when they are kept: hx_rt_set_state "keep_down")
@@ -1180,8 +1180,11 @@ static int rt_step_kernels(hx_rt* rt, int itervalue, int step_temperature, bool 
         k_rt_totals_a<<<dim3(rt->nchunk, rt->C), 256, 0, ctx->stream>>>(a);
         HX_LAUNCH_CHECK(ctx);
     }
-    if (rt->entr_kappa && rt->cols[0].physical_tstep != 0 && itervalue % 10 == 0) {   // computation.py:921-923
-        int rc = kappa_cp_from_table(rt, false);    // (reads temperatures and pressures, not the fluxes: before or behind the first level alike)
+    if (rt->entr_kappa && itervalue % 10 == 0) {   // computation.py:921-923, for the columns that are time-stepped: each column's
+        bool time_stepped = false;                 // own physical_tstep decides, as it does in rad_temp_step (graph_wanted likewise)
+        for (const auto& c : rt->cols) time_stepped = time_stepped || c.physical_tstep != 0;
+        // (reads temperatures and pressures, not the fluxes: before or behind the first level alike)
+        int rc = time_stepped ? kappa_cp_from_table(rt, false, true) : 0;
         if (rc) return rc;
     }
     {
@@ -1269,7 +1272,8 @@ ConvKArgs make_conv_args(hx_rt* rt, int itervalue) {
 namespace {
 
 // kappa_lay, kappa_int and c_p_lay from the table at the current temperatures (computation.py:199-250)
-int kappa_cp_from_table(hx_rt* rt, bool refresh_T_int) {
+// (`time_stepped_only`: of the columns with a physical time step alone; the others keep theirs as a batch of their own would)
+int kappa_cp_from_table(hx_rt* rt, bool refresh_T_int, bool time_stepped_only) {
     hx_context* ctx = rt->ctx;
     const int L = rt->L, I = rt->I;
     if (refresh_T_int) {
@@ -1277,6 +1281,7 @@ int kappa_cp_from_table(hx_rt* rt, bool refresh_T_int) {
         HX_LAUNCH_CHECK(ctx);
     }
     for (int c = 0; c < rt->C; c++) {
+        if (time_stepped_only && rt->cols[c].physical_tstep == 0) continue;
         const double* T_lay = rt->T_lay + (size_t)c * (L + 1);
         const double* T_int = rt->T_int + (size_t)c * I;
         const double* p_lay = rt->p_lay + (size_t)c * L;
@@ -1644,6 +1649,12 @@ int hx_rt_get(hx_rt* rt, int col, const char* name, void* out, size_t out_bytes)
                                rt->coef_tpb, rt->coef_bytes, rt->generic_scans ? 1 : 0};
         HX_REQUIRE(rt->ctx, out_bytes == sizeof(v), HX_E_ARG, "flux_tiling is 14 int32");
         memcpy(out, v, sizeof(v));
+        return 0;
+    }
+    if (strcmp(name, "totals_chunks") == 0) {   // host-side, any column (-1): int32, the bin chunks of the wavelength totals
+        HX_REQUIRE(rt->ctx, out_bytes == sizeof(int32_t), HX_E_ARG, "totals_chunks is one int32");
+        const int32_t v = rt->nchunk;
+        memcpy(out, &v, sizeof(v));
         return 0;
     }
     if (strcmp(name, "premixed_table_count") == 0) {   // host-side, any column (-1): int32, the table sets the batch holds

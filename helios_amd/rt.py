@@ -318,6 +318,13 @@ class RTBatch(object):
                  "hx_rt_get(coef_plane_bytes)")
         return int(out[0])
 
+    def totals_chunks(self):
+        """the number of bin chunks the wavelength totals are summed in (k_rt_totals_a's grid)"""
+        out = np.zeros(1, np.int32)
+        self._ck(self._l.hx_rt_get(self.handle, -1, b"totals_chunks", out.ctypes.data_as(ctypes.c_void_p), out.nbytes),
+                 "hx_rt_get(totals_chunks)")
+        return int(out[0])
+
     _TILING = ("k", "ROWS", "threads", "nparts", "nxb", "ypb", "NW", "nplane", "has_vp", "pl_vp", "pl_dd", "coef_tpb",
                "coef_bytes", "generic_scans")
 

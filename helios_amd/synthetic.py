@@ -41,7 +41,7 @@ def tp_grid(ntemp=30, npress=20):
 
 def _smooth5(a):
     k = np.ones(5) / 5.0
-    pad = np.concatenate([a[:2][::-1], a, a[-2:][::-1]])
+    pad = np.pad(a, 2, mode="symmetric")        # (a single bin too)
     return np.convolve(pad, k, mode="valid")
 
 
