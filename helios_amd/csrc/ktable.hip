@@ -11,10 +11,9 @@
 // block, the others i with i + j): every comparator leaves the larger key at the higher index, so padding of +inf behind the
 // n keys would never move, and comparators that reach beyond n are skipped instead of padded for.
 #include <algorithm>
-#include <string>
 #include <vector>
 
-#include "hx_common.h"
+#include "hx_tool.h"
 
 namespace {
 
@@ -307,26 +306,72 @@ struct hx_ktable {
     float* opac;
     kt_key* scratch;
     size_t ip_nodes;
-    bool have_grid, pending;
-    hipEvent_t ev0, ev1;
-    double timing[4];      // kernel ms of k_ktable_bins, launches, ms of the re-gridding, (T, P) points done
+    bool have_grid;
+    hx_owned owned;
+    hx_stream_timer timer;     // around the last launch of k_ktable_bins; settled by the next call
+    double timing[4];          // kernel ms of k_ktable_bins, launches, ms of the re-gridding, (T, P) points done
 };
 
-static int kt_free(hx_ktable* kt, void* p) { return p ? hx_free(kt->ctx, p) : 0; }
+static int kt_settle(hx_ktable* kt) { return hx_stream_timer_settle(kt->ctx, kt->timer, &kt->timing[0]); }
 
-// the kernel time of the last launch, once it has ended
-static int kt_settle(hx_ktable* kt) {
-    if (!kt->pending) return 0;
-    hx_context* ctx = kt->ctx;
-    HX_HIP(ctx, hipEventSynchronize(kt->ev1));
-    float ms = 0;
-    HX_HIP(ctx, hipEventElapsedTime(&ms, kt->ev0, kt->ev1));
-    kt->timing[0] += ms;
-    kt->pending = false;
+extern "C" {
+
+// the one re-gridding of the library: hx_ktable_regrid and hx_ktmix_set_species_native (ktable_mix.hip) both end here
+int hx_internal_regrid_check(hx_context* ctx, const char* fn, const hx_regrid_plan* P) {
+#define RG_REQUIRE(cond, msg)                                                 \
+    do {                                                                      \
+        if (!(cond)) return hx_fail(ctx, HX_E_ARG, "%s: %s", fn, (msg));      \
+    } while (0)
+    RG_REQUIRE(P->nt_new >= 1 && P->np_new >= 1, "an empty target grid");
+    RG_REQUIRE(P->t_left && P->t_reduced && P->p_left && P->p_reduced && P->temp_old && P->logp_old && P->temp_new && P->logp_new,
+               "null array");
+    // a node that is not clamped reads its left neighbour and the one after it
+    for (int i = 0; i < P->nt_new; i++)
+        RG_REQUIRE(P->t_left[i] >= 0 && P->t_left[i] + (P->t_reduced[i] ? 0 : 1) < P->nt_old, "temperature plan out of range");
+    for (int j = 0; j < P->np_new; j++)
+        RG_REQUIRE(P->p_left[j] >= 0 && P->p_left[j] + (P->p_reduced[j] ? 0 : 1) < P->np_old, "pressure plan out of range");
+#undef RG_REQUIRE
     return 0;
 }
 
-extern "C" {
+int hx_internal_regrid(hx_context* ctx, const char* fn, const hx_regrid_plan* P, const double* k_old, double* k_new, size_t nc,
+                       double* ms) {
+    int rc = hx_internal_regrid_check(ctx, fn, P);
+    if (rc) return rc;
+    const int nt_old = P->nt_old, np_old = P->np_old, nt_new = P->nt_new, np_new = P->np_new;
+    const size_t ni = (size_t)2 * (nt_new + np_new), nd = (size_t)nt_old + np_old + nt_new + np_new;
+    int* d_i = nullptr;
+    double* d_d = nullptr;
+    std::vector<int> hi;
+    std::vector<double> hd;
+    hi.insert(hi.end(), P->t_left, P->t_left + nt_new); hi.insert(hi.end(), P->t_reduced, P->t_reduced + nt_new);
+    hi.insert(hi.end(), P->p_left, P->p_left + np_new); hi.insert(hi.end(), P->p_reduced, P->p_reduced + np_new);
+    hd.insert(hd.end(), P->temp_old, P->temp_old + nt_old); hd.insert(hd.end(), P->logp_old, P->logp_old + np_old);
+    hd.insert(hd.end(), P->temp_new, P->temp_new + nt_new); hd.insert(hd.end(), P->logp_new, P->logp_new + np_new);
+    rc = hx_alloc(ctx, ni * 4, (void**)&d_i);
+    if (!rc) rc = hx_alloc(ctx, nd * 8, (void**)&d_d);
+    if (!rc) rc = hx_h2d(ctx, d_i, hi.data(), ni * 4);
+    if (!rc) rc = hx_h2d(ctx, d_d, hd.data(), nd * 8);
+    double took = 0.0;
+    if (!rc) {
+        KtRegrid R;
+        R.k_old = k_old; R.k_new = k_new;
+        R.t_left = d_i; R.t_red = d_i + nt_new; R.p_left = d_i + 2 * nt_new; R.p_red = d_i + 2 * nt_new + np_new;
+        R.T = d_d; R.lp = d_d + nt_old; R.Tn = d_d + nt_old + np_old; R.lpn = d_d + nt_old + np_old + nt_new;
+        R.nc = (int)nc; R.np_old = np_old; R.np_new = np_new; R.total = (size_t)nt_new * np_new * nc;
+        const int grid = (int)std::min<size_t>((R.total + 255) / 256, 65536);
+        rc = hx_timer_start(ctx);
+        if (!rc) {
+            k_ktable_regrid<<<grid, 256, 0, ctx->stream>>>(R);
+            rc = hipGetLastError() == hipSuccess ? 0 : hx_fail(ctx, HX_E_ARG, "%s: k_ktable_regrid launch failed", fn);
+        }
+        if (!rc) rc = hx_timer_stop_ms(ctx, &took);
+    }
+    (void)hx_free(ctx, d_i);
+    (void)hx_free(ctx, d_d);
+    if (!rc) *ms += took;
+    return rc;
+}
 
 int hx_ktable_create(hx_context* ctx, int n_points, int n_bins, int n_gauss, int n_tp, int max_tp_per_launch, int lds_points,
                      hx_ktable** out_kt) {
@@ -341,15 +386,15 @@ int hx_ktable_create(hx_context* ctx, int n_points, int n_bins, int n_gauss, int
     kt->ctx = ctx;
     kt->N = n_points; kt->nbin = n_bins; kt->ng = n_gauss; kt->ntp = n_tp;
     kt->maxtp = std::min(max_tp_per_launch, n_tp); kt->cap = lds_points;
-    int rc = hx_alloc(ctx, (size_t)n_points * 8, (void**)&kt->lam);
-    if (!rc) rc = hx_alloc(ctx, (size_t)(n_bins + 1) * 8, (void**)&kt->inter);
-    if (!rc) rc = hx_alloc(ctx, (size_t)n_gauss * 8, (void**)&kt->yg);
-    if (!rc) rc = hx_alloc(ctx, (size_t)n_bins * 4, (void**)&kt->bstart);
-    if (!rc) rc = hx_alloc(ctx, (size_t)n_bins * 4, (void**)&kt->bend);
-    if (!rc) rc = hx_alloc(ctx, (size_t)kt->maxtp * n_points * 4, (void**)&kt->opac);
-    if (!rc) rc = hx_alloc(ctx, (size_t)n_tp * n_bins * n_gauss * 8, (void**)&kt->out);
-    if (!rc) rc = hipEventCreate(&kt->ev0) == hipSuccess && hipEventCreate(&kt->ev1) == hipSuccess
-                      ? 0 : hx_fail(ctx, HX_E_ARG, "hipEventCreate failed");
+    hx_owned& o = kt->owned;
+    int rc = hx_owned_alloc(ctx, o, (size_t)n_points * 8, &kt->lam);
+    if (!rc) rc = hx_owned_alloc(ctx, o, (size_t)(n_bins + 1) * 8, &kt->inter);
+    if (!rc) rc = hx_owned_alloc(ctx, o, (size_t)n_gauss * 8, &kt->yg);
+    if (!rc) rc = hx_owned_alloc(ctx, o, (size_t)n_bins * 4, &kt->bstart);
+    if (!rc) rc = hx_owned_alloc(ctx, o, (size_t)n_bins * 4, &kt->bend);
+    if (!rc) rc = hx_owned_alloc(ctx, o, (size_t)kt->maxtp * n_points * 4, &kt->opac);
+    if (!rc) rc = hx_owned_alloc(ctx, o, (size_t)n_tp * n_bins * n_gauss * 8, &kt->out);
+    if (!rc) rc = hx_stream_timer_create(ctx, kt->timer);
     if (!rc) rc = hipFuncSetAttribute((const void*)k_ktable_bins, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       KT_MAX_LDS_POINTS * (int)sizeof(kt_key)) == hipSuccess
                       ? 0 : hx_fail(ctx, HX_E_UNSUPPORTED, "k_ktable_bins: 128 KiB of dynamic LDS were refused");
@@ -364,10 +409,8 @@ int hx_ktable_create(hx_context* ctx, int n_points, int n_bins, int n_gauss, int
 int hx_ktable_destroy(hx_ktable* kt) {
     if (!kt) return HX_E_ARG;
     (void)hx_sync(kt->ctx);
-    void* all[] = {kt->lam, kt->inter, kt->yg, kt->bstart, kt->bend, kt->opac, kt->out, kt->ip, kt->scratch};
-    for (void* p : all) (void)kt_free(kt, p);
-    if (kt->ev0) (void)hipEventDestroy(kt->ev0);
-    if (kt->ev1) (void)hipEventDestroy(kt->ev1);
+    hx_owned_free_all(kt->ctx, kt->owned);
+    hx_stream_timer_destroy(kt->timer);
     delete kt;
     return 0;
 }
@@ -392,7 +435,7 @@ int hx_ktable_set_grid(hx_ktable* kt, const double* lamda, const int* bin_start,
     if (!rc) rc = hx_h2d(ctx, kt->bend, bin_end, (size_t)kt->nbin * 4);
     if (!rc) rc = hx_h2d(ctx, kt->inter, interfaces, (size_t)(kt->nbin + 1) * 8);
     if (!rc) rc = hx_h2d(ctx, kt->yg, gauss_y, (size_t)kt->ng * 8);
-    if (!rc && longest > kt->cap && !kt->scratch) rc = hx_alloc(ctx, (size_t)kt->maxtp * kt->N * 8, (void**)&kt->scratch);
+    if (!rc && longest > kt->cap && !kt->scratch) rc = hx_owned_alloc(ctx, kt->owned, (size_t)kt->maxtp * kt->N * 8, &kt->scratch);
     if (rc) return rc;
     kt->have_grid = true;
     return 0;
@@ -412,11 +455,12 @@ int hx_ktable_run(hx_ktable* kt, const void* opac_f32, int n_tp, int first_tp) {
     A.opac = kt->opac; A.scratch = kt->scratch;
     A.out = kt->out + (size_t)first_tp * kt->nbin * kt->ng;
     A.N = kt->N; A.nbin = kt->nbin; A.ng = kt->ng; A.cap = kt->cap;
-    HX_HIP(ctx, hipEventRecord(kt->ev0, ctx->stream));
+    rc = hx_stream_timer_start(ctx, kt->timer);
+    if (rc) return rc;
     k_ktable_bins<<<dim3(kt->nbin, n_tp), KT_THREADS, (size_t)kt->cap * sizeof(kt_key), ctx->stream>>>(A);
     HX_LAUNCH_CHECK(ctx);
-    HX_HIP(ctx, hipEventRecord(kt->ev1, ctx->stream));
-    kt->pending = true;
+    rc = hx_stream_timer_stop(ctx, kt->timer);
+    if (rc) return rc;
     kt->timing[1] += 1.0;
     kt->timing[3] += n_tp;
     return 0;
@@ -429,52 +473,17 @@ int hx_ktable_regrid(hx_ktable* kt, int nt_old, int np_old, int nt_new, int np_n
     hx_context* ctx = kt->ctx;
     HX_REQUIRE(ctx, nt_old >= 1 && np_old >= 1 && (long long)nt_old * np_old == kt->ntp, HX_E_ARG,
                "nt_old x np_old is not the table's number of (T, P) points");
-    HX_REQUIRE(ctx, nt_new >= 1 && np_new >= 1, HX_E_ARG, "an empty target grid");
-    HX_REQUIRE(ctx, t_left && t_reduced && p_left && p_reduced && temp_old && logp_old && temp_new && logp_new, HX_E_ARG,
-               "null array");
-    // a node that is not clamped reads its left neighbour and the one after it
-    for (int i = 0; i < nt_new; i++)
-        HX_REQUIRE(ctx, t_left[i] >= 0 && t_left[i] + (t_reduced[i] ? 0 : 1) < nt_old, HX_E_ARG, "temperature plan out of range");
-    for (int j = 0; j < np_new; j++)
-        HX_REQUIRE(ctx, p_left[j] >= 0 && p_left[j] + (p_reduced[j] ? 0 : 1) < np_old, HX_E_ARG, "pressure plan out of range");
-    int rc = kt_settle(kt);
+    const hx_regrid_plan plan = {nt_old, np_old, nt_new, np_new, t_left, t_reduced, p_left, p_reduced,
+                                 temp_old, logp_old, temp_new, logp_new};
+    int rc = hx_internal_regrid_check(ctx, __func__, &plan);
+    if (!rc) rc = kt_settle(kt);
     if (rc) return rc;
     const size_t nc = (size_t)kt->nbin * kt->ng, nodes = (size_t)nt_new * np_new;
-    if (kt->ip) { rc = kt_free(kt, kt->ip); kt->ip = nullptr; kt->ip_nodes = 0; if (rc) return rc; }
-    rc = hx_alloc(ctx, nodes * nc * 8, (void**)&kt->ip);
+    rc = hx_owned_free(ctx, kt->owned, kt->ip);      // a refused plan leaves the last result; a failure from here on leaves none
+    kt->ip = nullptr; kt->ip_nodes = 0;
+    if (!rc) rc = hx_owned_alloc(ctx, kt->owned, nodes * nc * 8, &kt->ip);
+    if (!rc) rc = hx_internal_regrid(ctx, __func__, &plan, kt->out, kt->ip, nc, &kt->timing[2]);
     if (rc) return rc;
-    const size_t ni = (size_t)2 * (nt_new + np_new), nd = (size_t)nt_old + np_old + nt_new + np_new;
-    int* d_i = nullptr;
-    double* d_d = nullptr;
-    std::vector<int> hi;
-    std::vector<double> hd;
-    hi.insert(hi.end(), t_left, t_left + nt_new); hi.insert(hi.end(), t_reduced, t_reduced + nt_new);
-    hi.insert(hi.end(), p_left, p_left + np_new); hi.insert(hi.end(), p_reduced, p_reduced + np_new);
-    hd.insert(hd.end(), temp_old, temp_old + nt_old); hd.insert(hd.end(), logp_old, logp_old + np_old);
-    hd.insert(hd.end(), temp_new, temp_new + nt_new); hd.insert(hd.end(), logp_new, logp_new + np_new);
-    rc = hx_alloc(ctx, ni * 4, (void**)&d_i);
-    if (!rc) rc = hx_alloc(ctx, nd * 8, (void**)&d_d);
-    if (!rc) rc = hx_h2d(ctx, d_i, hi.data(), ni * 4);
-    if (!rc) rc = hx_h2d(ctx, d_d, hd.data(), nd * 8);
-    double ms = 0.0;
-    if (!rc) {
-        KtRegrid R;
-        R.k_old = kt->out; R.k_new = kt->ip;
-        R.t_left = d_i; R.t_red = d_i + nt_new; R.p_left = d_i + 2 * nt_new; R.p_red = d_i + 2 * nt_new + np_new;
-        R.T = d_d; R.lp = d_d + nt_old; R.Tn = d_d + nt_old + np_old; R.lpn = d_d + nt_old + np_old + nt_new;
-        R.nc = (int)nc; R.np_old = np_old; R.np_new = np_new; R.total = nodes * nc;
-        const int grid = (int)std::min<size_t>((R.total + 255) / 256, 65536);
-        rc = hx_timer_start(ctx);
-        if (!rc) {
-            k_ktable_regrid<<<grid, 256, 0, ctx->stream>>>(R);
-            rc = hipGetLastError() == hipSuccess ? 0 : hx_fail(ctx, HX_E_ARG, "k_ktable_regrid launch failed");
-        }
-        if (!rc) rc = hx_timer_stop_ms(ctx, &ms);
-    }
-    (void)hx_free(ctx, d_i);
-    (void)hx_free(ctx, d_d);
-    if (rc) return rc;
-    kt->timing[2] += ms;
     kt->ip_nodes = nodes;
     return 0;
 }
@@ -488,25 +497,15 @@ int hx_ktable_put(hx_ktable* kt, const double* kpoints) {
 
 int hx_ktable_get(hx_ktable* kt, const char* name, void* out, size_t out_bytes) {
     if (!kt || !name || !out) return HX_E_ARG;
-    hx_context* ctx = kt->ctx;
     int rc = kt_settle(kt);
     if (rc) return rc;
-    const std::string n(name);
     const size_t nc = (size_t)kt->nbin * kt->ng;
-    if (n == "timing_ms") {
-        if (out_bytes != sizeof kt->timing) return hx_fail(ctx, HX_E_ARG, "hx_ktable_get(timing_ms): 32 bytes expected");
-        memcpy(out, kt->timing, sizeof kt->timing);
-        return 0;
-    }
-    const double* src = nullptr;
-    size_t bytes = 0;
-    if (n == "kpoints") { src = kt->out; bytes = (size_t)kt->ntp * nc * 8; }
-    else if (n == "kpoints_ip") {
-        HX_REQUIRE(ctx, kt->ip, HX_E_STATE, "re-grid first");
-        src = kt->ip; bytes = kt->ip_nodes * nc * 8;
-    } else return hx_fail(ctx, HX_E_ARG, "hx_ktable_get: unknown name '%s'", name);
-    if (bytes != out_bytes) return hx_fail(ctx, HX_E_ARG, "hx_ktable_get(%s): %zu bytes expected, got %zu", name, bytes, out_bytes);
-    return hx_d2h(ctx, out, src, bytes);
+    const hx_result rows[] = {
+        {"timing_ms", kt->timing, sizeof kt->timing, false, nullptr},
+        {"kpoints", kt->out, (size_t)kt->ntp * nc * 8, true, nullptr},
+        {"kpoints_ip", kt->ip, kt->ip_nodes * nc * 8, true, kt->ip ? nullptr : "re-grid first"},
+    };
+    return hx_get_result(kt->ctx, __func__, rows, 3, name, out, out_bytes);
 }
 
 }  // extern "C"

@@ -12,15 +12,14 @@
 //                   The node is uniform per workgroup: the species' mass mixing ratios arrive by scalar loads.  Up to KM_G
 //                   species per launch, their tables as pointers in the argument struct; more are further launches that start
 //                   from the accumulator.  Traffic: (absorbers + 1) tables per chemistry, no atomics.
-//   k_ktmix_regrid  a native table onto the final grid into its slot: k_ktable_regrid's branches and term order (csrc/ktable.hip)
+//   k_ktable_regrid a native table onto the final grid into its slot: the k-table stage's own kernel (hx_internal_regrid, ktable.hip)
 //   k_ktmix_scat    a thread owns one bin of one node; the water vapour's cross-section is stage 2's own formula (not the run-time
 //                   h2o_rayleigh_cross of two_stream.h): no min(1, density), lambda <= 2.5 micron, the Lorentz-Lorenz factor is A
 #include <algorithm>
 #include <new>
-#include <string>
 #include <vector>
 
-#include "hx_common.h"
+#include "hx_tool.h"
 
 namespace {
 
@@ -76,41 +75,6 @@ __global__ void __launch_bounds__(KM_THREADS) k_ktmix_sum(KmSum A) {
         double a = A.from_acc ? out[e] : 0.0;
         for (int g = 0; g < A.n; g++) a = a + A.m[g][node] * A.k[g][row + e];
         out[e] = a;
-    }
-}
-
-struct KmRegrid {
-    const double* k_old; double* k_new;
-    const int *t_left, *t_red, *p_left, *p_red;
-    const double *T, *lp, *Tn, *lpn;
-    int nc, np_old, np_new;
-    size_t total;
-};
-
-__global__ void k_ktmix_regrid(KmRegrid R) {
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < R.total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int e = (int)(idx % R.nc);
-        const size_t node = idx / R.nc;
-        const int j = (int)(node % R.np_new), i = (int)(node / R.np_new);
-        const int t0 = R.t_left[i], p0 = R.p_left[j];
-        const bool rt = R.t_red[i] != 0, rp = R.p_red[j] != 0;
-        auto K = [&](int t, int p) { return R.k_old[((size_t)t * R.np_old + p) * R.nc + e]; };
-        double v;
-        if (rt && rp) {
-            v = K(t0, p0);
-        } else if (rt) {
-            const double c = R.lpn[j] - R.lp[p0], d = R.lp[p0 + 1] - R.lpn[j];
-            v = (K(t0, p0 + 1) * c + K(t0, p0) * d) / (R.lp[p0 + 1] - R.lp[p0]);
-        } else if (rp) {
-            const double a = R.Tn[i] - R.T[t0], b = R.T[t0 + 1] - R.Tn[i];
-            v = (K(t0 + 1, p0) * a + K(t0, p0) * b) / (R.T[t0 + 1] - R.T[t0]);
-        } else {
-            const double a = R.Tn[i] - R.T[t0], b = R.T[t0 + 1] - R.Tn[i];
-            const double c = R.lpn[j] - R.lp[p0], d = R.lp[p0 + 1] - R.lpn[j];
-            v = (K(t0 + 1, p0 + 1) * a * c + K(t0 + 1, p0) * a * d + K(t0, p0 + 1) * b * c + K(t0, p0) * b * d) /
-                ((R.T[t0 + 1] - R.T[t0]) * (R.lp[p0 + 1] - R.lp[p0]));
-        }
-        R.k_new[idx] = v;
     }
 }
 
@@ -174,18 +138,20 @@ struct hx_ktmix {
     int* kind;
     std::vector<double*> slot;
     std::vector<int> hkind;
+    hx_owned owned;
     bool have_grid, ran;
-    double timing[4];               // ms in k_ktmix_sum and in k_ktmix_scat of the last run, ms in k_ktmix_regrid so far, runs
+    double timing[4];               // ms in k_ktmix_sum and in k_ktmix_scat of the last run, ms in k_ktable_regrid so far, runs
 };
 
 // refuses what the device's free memory cannot hold, before asking for it
-static int km_alloc(hx_ktmix* km, size_t bytes, void** p, const char* what) {
+template <class T>
+static int km_alloc(hx_ktmix* km, size_t bytes, T** p, const char* what) {
     size_t free_b = 0, total_b = 0;
     int rc = hx_mem_info(km->ctx, &free_b, &total_b);
     if (rc) return rc;
     if (bytes > free_b)
         return hx_fail(km->ctx, HX_E_ARG, "hx_ktmix: %s needs %zu bytes, the device has %zu free", what, bytes, free_b);
-    rc = hx_alloc(km->ctx, bytes, p);
+    rc = hx_owned_alloc(km->ctx, km->owned, bytes, p);
     if (rc) return hx_fail(km->ctx, rc, "hx_ktmix: the allocation of %zu bytes for %s failed", bytes, what);
     if (((uintptr_t)*p & 15) != 0) return hx_fail(km->ctx, HX_E_STATE, "hx_ktmix: %s is not 16-byte aligned", what);
     return 0;
@@ -212,9 +178,7 @@ extern "C" {
 int hx_ktmix_destroy(hx_ktmix* km) {
     if (!km) return HX_E_ARG;
     (void)hx_sync(km->ctx);
-    void* all[] = {km->wave, km->temp, km->press, km->kpoints, km->scat, km->sigma, km->mmr, km->vmr, km->kind};
-    for (void* p : all) (void)hx_free(km->ctx, p);
-    for (double* p : km->slot) (void)hx_free(km->ctx, p);
+    hx_owned_free_all(km->ctx, km->owned);
     delete km;
     return 0;
 }
@@ -233,15 +197,15 @@ int hx_ktmix_create(hx_context* ctx, int nbin, int ny, int nt, int np, int nspec
     km->slot.assign(nspecies, nullptr);
     km->hkind.assign(nspecies, 0);
     // one row more than the tables hold: the guard rows behind them, which no kernel may touch
-    int rc = km_alloc(km, (km->nodes + 1) * km->nc * 8, (void**)&km->kpoints, "kpoints");
-    if (!rc) rc = km_alloc(km, (km->nodes + 1) * nbin * 8, (void**)&km->scat, "the Rayleigh table");
-    if (!rc) rc = km_alloc(km, (size_t)nspecies * km->nodes * 8, (void**)&km->mmr, "the mass mixing ratios");
-    if (!rc) rc = km_alloc(km, (size_t)nspecies * km->nodes * 8, (void**)&km->vmr, "the mixing ratios");
-    if (!rc) rc = km_alloc(km, (size_t)nspecies * nbin * 8, (void**)&km->sigma, "the cross-sections");
-    if (!rc) rc = km_alloc(km, (size_t)nspecies * 4, (void**)&km->kind, "the species' kinds");
-    if (!rc) rc = km_alloc(km, (size_t)nbin * 8, (void**)&km->wave, "the wavelengths");
-    if (!rc) rc = km_alloc(km, (size_t)nt * 8, (void**)&km->temp, "the temperatures");
-    if (!rc) rc = km_alloc(km, (size_t)np * 8, (void**)&km->press, "the pressures");
+    int rc = km_alloc(km, (km->nodes + 1) * km->nc * 8, &km->kpoints, "kpoints");
+    if (!rc) rc = km_alloc(km, (km->nodes + 1) * nbin * 8, &km->scat, "the Rayleigh table");
+    if (!rc) rc = km_alloc(km, (size_t)nspecies * km->nodes * 8, &km->mmr, "the mass mixing ratios");
+    if (!rc) rc = km_alloc(km, (size_t)nspecies * km->nodes * 8, &km->vmr, "the mixing ratios");
+    if (!rc) rc = km_alloc(km, (size_t)nspecies * nbin * 8, &km->sigma, "the cross-sections");
+    if (!rc) rc = km_alloc(km, (size_t)nspecies * 4, &km->kind, "the species' kinds");
+    if (!rc) rc = km_alloc(km, (size_t)nbin * 8, &km->wave, "the wavelengths");
+    if (!rc) rc = km_alloc(km, (size_t)nt * 8, &km->temp, "the temperatures");
+    if (!rc) rc = km_alloc(km, (size_t)np * 8, &km->press, "the pressures");
     if (!rc) rc = hx_memset0(ctx, km->sigma, (size_t)nspecies * nbin * 8);
     if (!rc) rc = hx_memset0(ctx, km->kind, (size_t)nspecies * 4);
     if (!rc) {
@@ -277,12 +241,12 @@ int hx_ktmix_set_species(hx_ktmix* km, int s, const double* k_on_final_grid) {
     int rc = km_slot_index(km, s, "hx_ktmix_set_species");
     if (rc) return rc;
     if (!k_on_final_grid) {                 // not absorbing
-        rc = hx_free(km->ctx, km->slot[s]);
+        rc = hx_owned_free(km->ctx, km->owned, km->slot[s]);
         km->slot[s] = nullptr;
         return rc;
     }
     if (!km->slot[s]) {
-        rc = km_alloc(km, km->nodes * km->nc * 8, (void**)&km->slot[s], "a species table");
+        rc = km_alloc(km, km->nodes * km->nc * 8, &km->slot[s], "a species table");
         if (rc) { km->slot[s] = nullptr; return rc; }
     }
     return km_upload(km, km->slot[s], k_on_final_grid, km->nodes * km->nc);
@@ -296,56 +260,22 @@ int hx_ktmix_set_species_native(hx_ktmix* km, int s, const double* k_native, int
     int rc = km_slot_index(km, s, "hx_ktmix_set_species_native");
     if (rc) return rc;
     HX_REQUIRE(ctx, nt_old >= 1 && np_old >= 1 && (long long)nt_old * np_old <= (1LL << 30), HX_E_ARG, "an empty native grid");
-    HX_REQUIRE(ctx, k_native && t_left && t_reduced && p_left && p_reduced && temp_old && logp_old && temp_new && logp_new,
-               HX_E_ARG, "null array");
-    const int nt_new = km->nt, np_new = km->np;
-    // a node that is not clamped reads its left neighbour and the one after it
-    for (int i = 0; i < nt_new; i++)
-        HX_REQUIRE(ctx, t_left[i] >= 0 && t_left[i] + (t_reduced[i] ? 0 : 1) < nt_old, HX_E_ARG, "temperature plan out of range");
-    for (int j = 0; j < np_new; j++)
-        HX_REQUIRE(ctx, p_left[j] >= 0 && p_left[j] + (p_reduced[j] ? 0 : 1) < np_old, HX_E_ARG, "pressure plan out of range");
+    HX_REQUIRE(ctx, k_native, HX_E_ARG, "null array");
+    const hx_regrid_plan plan = {nt_old, np_old, km->nt, km->np, t_left, t_reduced, p_left, p_reduced,
+                                 temp_old, logp_old, temp_new, logp_new};
+    rc = hx_internal_regrid_check(ctx, __func__, &plan);
+    if (rc) return rc;
     if (!km->slot[s]) {
-        rc = km_alloc(km, km->nodes * km->nc * 8, (void**)&km->slot[s], "a species table");
+        rc = km_alloc(km, km->nodes * km->nc * 8, &km->slot[s], "a species table");
         if (rc) { km->slot[s] = nullptr; return rc; }
     }
     const size_t n_old = (size_t)nt_old * np_old * km->nc;
     double* d_old = nullptr;
-    int* d_i = nullptr;
-    double* d_d = nullptr;
-    const size_t ni = (size_t)2 * (nt_new + np_new), nd = (size_t)nt_old + np_old + nt_new + np_new;
-    std::vector<int> hi;
-    std::vector<double> hd;
-    hi.insert(hi.end(), t_left, t_left + nt_new); hi.insert(hi.end(), t_reduced, t_reduced + nt_new);
-    hi.insert(hi.end(), p_left, p_left + np_new); hi.insert(hi.end(), p_reduced, p_reduced + np_new);
-    hd.insert(hd.end(), temp_old, temp_old + nt_old); hd.insert(hd.end(), logp_old, logp_old + np_old);
-    hd.insert(hd.end(), temp_new, temp_new + nt_new); hd.insert(hd.end(), logp_new, logp_new + np_new);
-    rc = km_alloc(km, n_old * 8, (void**)&d_old, "a native species table");
-    if (!rc) rc = hx_alloc(ctx, ni * 4, (void**)&d_i);
-    if (!rc) rc = hx_alloc(ctx, nd * 8, (void**)&d_d);
+    rc = km_alloc(km, n_old * 8, &d_old, "a native species table");
     if (!rc) rc = km_upload(km, d_old, k_native, n_old);
-    if (!rc) rc = hx_h2d(ctx, d_i, hi.data(), ni * 4);
-    if (!rc) rc = hx_h2d(ctx, d_d, hd.data(), nd * 8);
-    double ms = 0.0;
-    if (!rc) {
-        KmRegrid R;
-        R.k_old = d_old; R.k_new = km->slot[s];
-        R.t_left = d_i; R.t_red = d_i + nt_new; R.p_left = d_i + 2 * nt_new; R.p_red = d_i + 2 * nt_new + np_new;
-        R.T = d_d; R.lp = d_d + nt_old; R.Tn = d_d + nt_old + np_old; R.lpn = d_d + nt_old + np_old + nt_new;
-        R.nc = (int)km->nc; R.np_old = np_old; R.np_new = np_new; R.total = km->nodes * km->nc;
-        const int grid = (int)std::min<size_t>((R.total + 255) / 256, 65536);
-        rc = hx_timer_start(ctx);
-        if (!rc) {
-            k_ktmix_regrid<<<grid, 256, 0, ctx->stream>>>(R);
-            rc = hipGetLastError() == hipSuccess ? 0 : hx_fail(ctx, HX_E_ARG, "k_ktmix_regrid launch failed");
-        }
-        if (!rc) rc = hx_timer_stop_ms(ctx, &ms);
-    }
-    (void)hx_free(ctx, d_old);
-    (void)hx_free(ctx, d_i);
-    (void)hx_free(ctx, d_d);
-    if (rc) return rc;
-    km->timing[2] += ms;
-    return 0;
+    if (!rc) rc = hx_internal_regrid(ctx, __func__, &plan, d_old, km->slot[s], km->nc, &km->timing[2]);
+    (void)hx_owned_free(ctx, km->owned, d_old);
+    return rc;
 }
 
 int hx_ktmix_set_rayleigh(hx_ktmix* km, int s, const double* sigma, int is_h2o) {
@@ -421,33 +351,24 @@ int hx_ktmix_run(hx_ktmix* km, const double* mmr, const double* vmr_scat) {
 int hx_ktmix_get(hx_ktmix* km, const char* name, void* out, size_t out_bytes) {
     if (!km || !name || !out) return HX_E_ARG;
     hx_context* ctx = km->ctx;
-    const std::string n(name);
-    if (n == "timing_ms") {
-        if (out_bytes != sizeof km->timing) return hx_fail(ctx, HX_E_ARG, "hx_ktmix_get(timing_ms): 32 bytes expected");
-        memcpy(out, km->timing, sizeof km->timing);
-        return 0;
-    }
-    const double* src = nullptr;
-    size_t bytes = 0;
-    if (n == "kpoints" || n == "scat_cross") {
-        HX_REQUIRE(ctx, km->ran, HX_E_STATE, "run first");
-        src = n == "kpoints" ? km->kpoints : km->scat;
-        bytes = km->nodes * (n == "kpoints" ? km->nc : (size_t)km->nbin) * 8;
-    } else if (n == "kpoints_guard") {
-        src = km->kpoints + km->nodes * km->nc; bytes = km->nc * 8;
-    } else if (n == "scat_cross_guard") {
-        src = km->scat + km->nodes * km->nbin; bytes = (size_t)km->nbin * 8;
-    } else if (n.rfind("species_", 0) == 0) {
-        char* end = nullptr;
-        const long s = strtol(name + 8, &end, 10);
-        if (end == name + 8 || *end) return hx_fail(ctx, HX_E_ARG, "hx_ktmix_get: unknown name '%s'", name);
+    char* end = nullptr;
+    const long s = strncmp(name, "species_", 8) == 0 ? strtol(name + 8, &end, 10) : 0;
+    if (end && end != name + 8 && !*end) {
         if (s < 0 || s >= km->ns)
             return hx_fail(ctx, HX_E_ARG, "hx_ktmix_get: species slot %ld out of range, the object has %d", s, km->ns);
         if (!km->slot[s]) return hx_fail(ctx, HX_E_STATE, "hx_ktmix_get: species slot %ld holds no table", s);
-        src = km->slot[s]; bytes = km->nodes * km->nc * 8;
-    } else return hx_fail(ctx, HX_E_ARG, "hx_ktmix_get: unknown name '%s'", name);
-    if (bytes != out_bytes) return hx_fail(ctx, HX_E_ARG, "hx_ktmix_get(%s): %zu bytes expected, got %zu", name, bytes, out_bytes);
-    return hx_d2h(ctx, out, src, bytes);
+        const hx_result row = {name, km->slot[s], km->nodes * km->nc * 8, true, nullptr};
+        return hx_get_result(ctx, __func__, &row, 1, name, out, out_bytes);
+    }
+    const char* run_first = km->ran ? nullptr : "run first";
+    const hx_result rows[] = {
+        {"timing_ms", km->timing, sizeof km->timing, false, nullptr},
+        {"kpoints", km->kpoints, km->nodes * km->nc * 8, true, run_first},
+        {"scat_cross", km->scat, km->nodes * km->nbin * 8, true, run_first},
+        {"kpoints_guard", km->kpoints + km->nodes * km->nc, km->nc * 8, true, nullptr},
+        {"scat_cross_guard", km->scat + km->nodes * km->nbin, (size_t)km->nbin * 8, true, nullptr},
+    };
+    return hx_get_result(ctx, __func__, rows, 5, name, out, out_bytes);
 }
 
 }  // extern "C"

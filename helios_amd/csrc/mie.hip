@@ -9,11 +9,10 @@
 //           wavefront that would not fit with 64 lanes gets fewer.
 //
 // All arithmetic is fp64 without contraction, complex division is written out, and no function of the complex m x is taken.
-#include "hx_common.h"
+#include "hx_tool.h"
 
 #include <cmath>
 #include <new>
-#include <string>
 #include <vector>
 
 namespace {
@@ -157,7 +156,8 @@ struct hx_mie {
     int *nterms, *cap, *order;
     double2* dbuf;                     // cap_entries + 1
     MieWave* waves;                    // nmax: a wavefront holds at least one pair
-    hipEvent_t ev[2];
+    hx_owned owned;
+    hx_stream_timer timer;
     double timing[2];                  // ms in k_mie and launches, of the last run
 };
 
@@ -175,18 +175,18 @@ int hx_mie_create(hx_context* ctx, int n_pairs_max, size_t scratch_bytes, hx_mie
     h->nmax = n_pairs_max;
     h->cap_entries = scratch_bytes / sizeof(double2);
     const size_t n = (size_t)n_pairs_max;
-    int rc = hx_alloc(ctx, n * 8, (void**)&h->x);
-    if (!rc) rc = hx_alloc(ctx, n * 8, (void**)&h->m_re);
-    if (!rc) rc = hx_alloc(ctx, n * 8, (void**)&h->m_im);
-    if (!rc) rc = hx_alloc(ctx, (n + 1) * 8, (void**)&h->q_ext);
-    if (!rc) rc = hx_alloc(ctx, (n + 1) * 8, (void**)&h->q_sca);
-    if (!rc) rc = hx_alloc(ctx, (n + 1) * 8, (void**)&h->g);
-    if (!rc) rc = hx_alloc(ctx, n * 4, (void**)&h->nterms);
-    if (!rc) rc = hx_alloc(ctx, n * 4, (void**)&h->cap);
-    if (!rc) rc = hx_alloc(ctx, n * 4, (void**)&h->order);
-    if (!rc) rc = hx_alloc(ctx, n * sizeof(MieWave), (void**)&h->waves);
+    int rc = hx_owned_alloc(ctx, h->owned, n * 8, &h->x);
+    if (!rc) rc = hx_owned_alloc(ctx, h->owned, n * 8, &h->m_re);
+    if (!rc) rc = hx_owned_alloc(ctx, h->owned, n * 8, &h->m_im);
+    if (!rc) rc = hx_owned_alloc(ctx, h->owned, (n + 1) * 8, &h->q_ext);
+    if (!rc) rc = hx_owned_alloc(ctx, h->owned, (n + 1) * 8, &h->q_sca);
+    if (!rc) rc = hx_owned_alloc(ctx, h->owned, (n + 1) * 8, &h->g);
+    if (!rc) rc = hx_owned_alloc(ctx, h->owned, n * 4, &h->nterms);
+    if (!rc) rc = hx_owned_alloc(ctx, h->owned, n * 4, &h->cap);
+    if (!rc) rc = hx_owned_alloc(ctx, h->owned, n * 4, &h->order);
+    if (!rc) rc = hx_owned_alloc(ctx, h->owned, n * sizeof(MieWave), &h->waves);
     if (!rc) {
-        rc = hx_alloc(ctx, (h->cap_entries + 1) * sizeof(double2), (void**)&h->dbuf);
+        rc = hx_owned_alloc(ctx, h->owned, (h->cap_entries + 1) * sizeof(double2), &h->dbuf);
         if (rc) rc = hx_fail(ctx, rc, "hx_mie_create: no device memory for a D buffer of %zu bytes", scratch_bytes);
     }
     if (!rc) rc = hx_memset0(ctx, h->q_ext, n * 8);
@@ -199,8 +199,7 @@ int hx_mie_create(hx_context* ctx, int n_pairs_max, size_t scratch_bytes, hx_mie
         if (!rc) rc = hx_h2d(ctx, h->g + n, gd, 8);
         if (!rc) rc = hx_h2d(ctx, h->dbuf + h->cap_entries, gd, 16);
     }
-    for (int k = 0; k < 2 && !rc; k++)
-        rc = hipEventCreate(&h->ev[k]) == hipSuccess ? 0 : hx_fail(ctx, HX_E_ARG, "hipEventCreate failed");
+    if (!rc) rc = hx_stream_timer_create(ctx, h->timer);
     if (rc) {
         hx_mie_destroy(h);
         return rc;
@@ -212,11 +211,8 @@ int hx_mie_create(hx_context* ctx, int n_pairs_max, size_t scratch_bytes, hx_mie
 int hx_mie_destroy(hx_mie* h) {
     if (!h) return HX_E_ARG;
     (void)hx_sync(h->ctx);
-    void* all[] = {h->x, h->m_re, h->m_im, h->q_ext, h->q_sca, h->g, h->nterms, h->cap, h->order, h->waves, h->dbuf};
-    for (void* p : all)
-        if (p) (void)hx_free(h->ctx, p);
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
+    hx_owned_free_all(h->ctx, h->owned);
+    hx_stream_timer_destroy(h->timer);
     delete h;
     return 0;
 }
@@ -289,8 +285,8 @@ int hx_mie_run(hx_mie* h, int n_pairs, const double* x, const double* m_re, cons
     if (!rc) rc = hx_h2d(ctx, h->cap, cap.data(), (size_t)n_pairs * 4);
     if (!rc) rc = hx_h2d(ctx, h->order, order, (size_t)n_pairs * 4);
     if (!rc) rc = hx_h2d(ctx, h->waves, waves.data(), waves.size() * sizeof(MieWave));
+    if (!rc) rc = hx_stream_timer_start(ctx, h->timer);
     if (rc) return rc;
-    HX_HIP(ctx, hipEventRecord(h->ev[0], ctx->stream));
     const int launches = (int)launch_first.size() - 1;
     for (int l = 0; l < launches; l++) {
         const int w0 = launch_first[l], nw = launch_first[l + 1] - w0;
@@ -298,25 +294,17 @@ int hx_mie_run(hx_mie* h, int n_pairs, const double* x, const double* m_re, cons
                                                  h->q_ext, h->q_sca, h->g);
         HX_LAUNCH_CHECK(ctx);
     }
-    HX_HIP(ctx, hipEventRecord(h->ev[1], ctx->stream));
-    HX_HIP(ctx, hipEventSynchronize(h->ev[1]));
-    float ms = 0;
-    HX_HIP(ctx, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    h->timing[0] = ms;
+    h->timing[0] = 0.0;                 // of this run alone, and it has ended when the call returns
     h->timing[1] = launches;
-    return 0;
+    rc = hx_stream_timer_stop(ctx, h->timer);
+    if (!rc) rc = hx_stream_timer_settle(ctx, h->timer, &h->timing[0]);
+    return rc;
 }
 
 int hx_mie_get(hx_mie* h, const char* name, void* out, size_t out_bytes) {
     if (!h || !name || !out) return HX_E_ARG;
     hx_context* ctx = h->ctx;
-    const std::string n(name);
-    if (n == "timing_ms") {
-        if (out_bytes != sizeof h->timing) return hx_fail(ctx, HX_E_ARG, "hx_mie_get(timing_ms): 16 bytes expected");
-        memcpy(out, h->timing, sizeof h->timing);
-        return 0;
-    }
-    if (n == "guard") {                 // behind q_ext, q_sca, g, and the two doubles behind the D buffer
+    if (!strcmp(name, "guard")) {       // behind q_ext, q_sca, g, and the two doubles behind the D buffer
         if (out_bytes != 40) return hx_fail(ctx, HX_E_ARG, "hx_mie_get(guard): 40 bytes expected");
         int rc = hx_d2h(ctx, out, h->q_ext + h->nmax, 8);
         if (!rc) rc = hx_d2h(ctx, (char*)out + 8, h->q_sca + h->nmax, 8);
@@ -324,11 +312,14 @@ int hx_mie_get(hx_mie* h, const char* name, void* out, size_t out_bytes) {
         if (!rc) rc = hx_d2h(ctx, (char*)out + 24, h->dbuf + h->cap_entries, 16);
         return rc;
     }
-    const double* src = n == "q_ext" ? h->q_ext : n == "q_sca" ? h->q_sca : n == "g" ? h->g : nullptr;
-    if (!src) return hx_fail(ctx, HX_E_ARG, "hx_mie_get: unknown name '%s'", name);
-    if (out_bytes == 0 || out_bytes % 8 || out_bytes > (size_t)h->nmax * 8)
-        return hx_fail(ctx, HX_E_ARG, "hx_mie_get(%s): 8 ... %zu bytes expected, got %zu", name, (size_t)h->nmax * 8, out_bytes);
-    return hx_d2h(ctx, out, src, out_bytes);
+    const double* src = !strcmp(name, "q_ext") ? h->q_ext : !strcmp(name, "q_sca") ? h->q_sca : !strcmp(name, "g") ? h->g : nullptr;
+    if (src) {                          // the first out_bytes: a run may hold fewer pairs than the handle
+        if (out_bytes == 0 || out_bytes % 8 || out_bytes > (size_t)h->nmax * 8)
+            return hx_fail(ctx, HX_E_ARG, "hx_mie_get(%s): 8 ... %zu bytes expected, got %zu", name, (size_t)h->nmax * 8, out_bytes);
+        return hx_d2h(ctx, out, src, out_bytes);
+    }
+    const hx_result row = {"timing_ms", h->timing, sizeof h->timing, false, nullptr};
+    return hx_get_result(ctx, __func__, &row, 1, name, out, out_bytes);
 }
 
 }  // extern "C"

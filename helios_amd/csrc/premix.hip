@@ -21,10 +21,10 @@
 // the existing kernel's code object was to stay as it is, and both sides call the same vmr_from_table and locate_tp.
 #define HX_SPECIES_DECLARATIONS_ONLY
 #include "rt_species.h"
+#include "hx_tool.h"
 
 #include <algorithm>
 #include <cmath>
-#include <string>
 #include <vector>
 
 using namespace hx;
@@ -46,7 +46,7 @@ struct hx_premix {
     std::vector<double> h_ktemp, h_kpress, outT, outP, cenT, cenP;  // output nodes and cell centres along each axis
     std::vector<double> kpoints, scat, mmm, err_max, err_mean;      // results (host)
     double timing[4] = {0, 0, 0, 0};
-    std::vector<void*> owned;  // device allocations of the object
+    hx_owned owned;
 };
 
 namespace {
@@ -169,22 +169,9 @@ __global__ void __launch_bounds__(256) k_premix_table_outer(double* __restrict__
         out[k] = kxy[k % nc] * ftp[k / nc];
 }
 
-int pm_alloc(hx_premix* pm, size_t bytes, void** out) {
-    int rc = hx_alloc(pm->ctx, bytes, out);
-    if (!rc) pm->owned.push_back(*out);
-    return rc;
-}
-
-int pm_free(hx_premix* pm, void* p) {
-    if (!p) return 0;
-    auto it = std::find(pm->owned.begin(), pm->owned.end(), p);
-    if (it != pm->owned.end()) pm->owned.erase(it);
-    return hx_free(pm->ctx, p);
-}
-
 #define PM_ALLOC(ptr, count)                                                 \
     do {                                                                     \
-        int rc_ = pm_alloc(pm, (size_t)(count) * sizeof(*(ptr)), (void**)&(ptr)); \
+        int rc_ = hx_owned_alloc(pm->ctx, pm->owned, (size_t)(count) * sizeof(*(ptr)), &(ptr)); \
         if (rc_) return rc_;                                                 \
     } while (0)
 
@@ -247,7 +234,7 @@ int hx_premix_create(hx_context* ctx, int nbin, int ny, int ntemp, int npress, i
 int hx_premix_destroy(hx_premix* pm) {
     if (!pm) return 0;
     (void)hx_sync(pm->ctx);
-    for (void* p : pm->owned) (void)hipFree(p);
+    hx_owned_free_all(pm->ctx, pm->owned);
     delete pm;
     return 0;
 }
@@ -303,7 +290,7 @@ int hx_premix_set_species_vmr(hx_premix* pm, int s, const double* vmr_table, dou
         int rc = hx_h2d(pm->ctx, sp.vmr_tab, vmr_table, ntp * 8);
         if (rc) return rc;
     } else if (sp.vmr_tab) {
-        int rc = pm_free(pm, sp.vmr_tab);
+        int rc = hx_owned_free(pm->ctx, pm->owned, sp.vmr_tab);
         if (rc) return rc;
         sp.vmr_tab = nullptr;
     }
@@ -541,28 +528,22 @@ int hx_premix_run(hx_premix* pm, int cell_error) {
 int hx_premix_get(hx_premix* pm, const char* name, void* out, size_t out_bytes) {
     if (!pm || !name || !out) return HX_E_ARG;
     hx_context* ctx = pm->ctx;
-    const std::string n(name);
-    const void* src = nullptr;
-    size_t bytes = 0;
-    bool found = true;
-    int32_t dims[2] = {pm->NT, pm->NP};
-    if (n == "dims") { src = dims; bytes = sizeof dims; }
-    else if (n == "timing_ms") { src = pm->timing; bytes = sizeof pm->timing; }
-    else if (n == "temperatures") { src = pm->outT.data(); bytes = pm->outT.size() * 8; }
-    else if (n == "pressures") { src = pm->outP.data(); bytes = pm->outP.size() * 8; }
-    else if (n == "kpoints") { src = pm->kpoints.data(); bytes = pm->kpoints.size() * 8; }
-    else if (n == "scat_cross") { src = pm->scat.data(); bytes = pm->scat.size() * 8; }
-    else if (n == "meanmolmass") { src = pm->mmm.data(); bytes = pm->mmm.size() * 8; }
-    else if (n == "cell_error_max") { src = pm->err_max.data(); bytes = pm->err_max.size() * 8; }
-    else if (n == "cell_error_mean") { src = pm->err_mean.data(); bytes = pm->err_mean.size() * 8; }
-    else found = false;
-    if (!found) return hx_fail(ctx, HX_E_ARG, "hx_premix_get: unknown name '%s'", name);
-    const bool grid_only = n == "dims" || n == "timing_ms" || n == "temperatures" || n == "pressures";
-    HX_REQUIRE(ctx, grid_only ? pm->have_grid || n == "dims" : pm->ran, HX_E_STATE, "set the grid and run the premix first");
-    HX_REQUIRE(ctx, n.rfind("cell_error", 0) != 0 || pm->ran_error, HX_E_STATE, "the last run did not build the cell-error map");
-    if (bytes != out_bytes) return hx_fail(ctx, HX_E_ARG, "hx_premix_get(%s): %zu bytes expected, got %zu", name, bytes, out_bytes);
-    if (bytes) memcpy(out, src, bytes);
-    return 0;
+    const int32_t dims[2] = {pm->NT, pm->NP};
+    const char* first = "set the grid and run the premix first";
+    const char *no_grid = pm->have_grid ? nullptr : first, *no_run = pm->ran ? nullptr : first;
+    const char* no_error = no_run ? no_run : pm->ran_error ? nullptr : "the last run did not build the cell-error map";
+    const hx_result rows[] = {
+        {"dims", dims, sizeof dims, false, nullptr},
+        {"timing_ms", pm->timing, sizeof pm->timing, false, no_grid},
+        {"temperatures", pm->outT.data(), pm->outT.size() * 8, false, no_grid},
+        {"pressures", pm->outP.data(), pm->outP.size() * 8, false, no_grid},
+        {"kpoints", pm->kpoints.data(), pm->kpoints.size() * 8, false, no_run},
+        {"scat_cross", pm->scat.data(), pm->scat.size() * 8, false, no_run},
+        {"meanmolmass", pm->mmm.data(), pm->mmm.size() * 8, false, no_run},
+        {"cell_error_max", pm->err_max.data(), pm->err_max.size() * 8, false, no_error},
+        {"cell_error_mean", pm->err_mean.data(), pm->err_mean.size() * 8, false, no_error},
+    };
+    return hx_get_result(ctx, __func__, rows, sizeof rows / sizeof rows[0], name, out, out_bytes);
 }
 
 }  // extern "C"

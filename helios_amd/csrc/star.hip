@@ -8,11 +8,10 @@
 //   k_star_rebin_*      interface interpolants and the trapezoids of the points inside a bin: bins of up to ST_NARROW points one
 //                       thread each in the reference's own order, longer ones one workgroup each in chunks staged through LDS and
 //                       summed by a tree whose shape the chunk length fixes
-#include "hx_common.h"
+#include "hx_tool.h"
 
 #include <algorithm>
 #include <new>
-#include <string>
 #include <vector>
 
 namespace {
@@ -192,24 +191,16 @@ struct hx_star {
     StStar* stars;
     std::vector<StStar> h_stars;
     std::vector<char> have_corner, have_star;
-    bool have_grid, pending;
-    hipEvent_t ev[6];
-    bool timed[3];
+    bool have_grid;
+    hx_owned owned;
+    hx_stream_timer timer[3];          // around the blend, the Planck values and the re-binning of the last run
     double timing[4];      // ms in k_star_blend, in k_star_planck_bins, in the re-binning kernels; runs
 };
 
 static int st_settle(hx_star* st) {
-    if (!st->pending) return 0;
-    hx_context* ctx = st->ctx;
-    HX_HIP(ctx, hipEventSynchronize(st->ev[5]));
-    for (int k = 0; k < 3; k++) {
-        if (!st->timed[k]) continue;
-        float ms = 0;
-        HX_HIP(ctx, hipEventElapsedTime(&ms, st->ev[2 * k], st->ev[2 * k + 1]));
-        st->timing[k] += ms;
-    }
-    st->pending = false;
-    return 0;
+    int rc = 0;
+    for (int k = 0; k < 3 && !rc; k++) rc = hx_stream_timer_settle(st->ctx, st->timer[k], &st->timing[k]);
+    return rc;
 }
 
 extern "C" {
@@ -230,23 +221,22 @@ int hx_star_create(hx_context* ctx, int n_points, int n_corners, int n_stars, in
     st->have_corner.assign(n_corners, 0);
     st->have_star.assign(n_stars, 0);
     const size_t nb = (size_t)n_bins, ns = (size_t)n_stars;
-    int rc = hx_alloc(ctx, st->npad * 8, (void**)&st->lam);
-    if (!rc && n_corners) rc = hx_alloc(ctx, (size_t)n_corners * st->npad * 4, (void**)&st->corners);
+    int rc = hx_owned_alloc(ctx, st->owned, st->npad * 8, &st->lam);
+    if (!rc && n_corners) rc = hx_owned_alloc(ctx, st->owned, (size_t)n_corners * st->npad * 4, &st->corners);
     if (!rc && n_corners) rc = hx_memset0(ctx, st->corners, (size_t)n_corners * st->npad * 4);
-    if (!rc) rc = hx_alloc(ctx, ns * st->npad * 8, (void**)&st->flux);
+    if (!rc) rc = hx_owned_alloc(ctx, st->owned, ns * st->npad * 8, &st->flux);
     if (!rc) rc = hx_memset0(ctx, st->flux, ns * st->npad * 8);
-    if (!rc) rc = hx_alloc(ctx, (nb + 1) * 8, (void**)&st->inter);
-    if (!rc) rc = hx_alloc(ctx, (nb + 1) * 4, (void**)&st->pbot);
-    if (!rc) rc = hx_alloc(ctx, (nb + 1) * 4, (void**)&st->state);
-    if (!rc) rc = hx_alloc(ctx, nb * 4, (void**)&st->wide);
-    if (!rc) rc = hx_alloc(ctx, ns * nb * 8, (void**)&st->planck);
+    if (!rc) rc = hx_owned_alloc(ctx, st->owned, (nb + 1) * 8, &st->inter);
+    if (!rc) rc = hx_owned_alloc(ctx, st->owned, (nb + 1) * 4, &st->pbot);
+    if (!rc) rc = hx_owned_alloc(ctx, st->owned, (nb + 1) * 4, &st->state);
+    if (!rc) rc = hx_owned_alloc(ctx, st->owned, nb * 4, &st->wide);
+    if (!rc) rc = hx_owned_alloc(ctx, st->owned, ns * nb * 8, &st->planck);
     if (!rc) rc = hx_memset0(ctx, st->planck, ns * nb * 8);
-    if (!rc) rc = hx_alloc(ctx, ns * nb * 8, (void**)&st->out);
+    if (!rc) rc = hx_owned_alloc(ctx, st->owned, ns * nb * 8, &st->out);
     if (!rc) rc = hx_memset0(ctx, st->out, ns * nb * 8);
-    if (!rc) rc = hx_alloc(ctx, ns * 16, (void**)&st->temp_d);
-    if (!rc) rc = hx_alloc(ctx, ns * sizeof(StStar), (void**)&st->stars);
-    for (int k = 0; k < 6 && !rc; k++)
-        rc = hipEventCreate(&st->ev[k]) == hipSuccess ? 0 : hx_fail(ctx, HX_E_ARG, "hipEventCreate failed");
+    if (!rc) rc = hx_owned_alloc(ctx, st->owned, ns * 16, &st->temp_d);
+    if (!rc) rc = hx_owned_alloc(ctx, st->owned, ns * sizeof(StStar), &st->stars);
+    for (int k = 0; k < 3 && !rc; k++) rc = hx_stream_timer_create(ctx, st->timer[k]);
     if (rc) {
         hx_star_destroy(st);
         return rc;
@@ -258,12 +248,8 @@ int hx_star_create(hx_context* ctx, int n_points, int n_corners, int n_stars, in
 int hx_star_destroy(hx_star* st) {
     if (!st) return HX_E_ARG;
     (void)hx_sync(st->ctx);
-    void* all[] = {st->lam, st->corners, st->flux, st->inter, st->pbot, st->state, st->wide, st->planck, st->out, st->temp_d,
-                   st->stars};
-    for (void* p : all)
-        if (p) (void)hx_free(st->ctx, p);
-    for (hipEvent_t e : st->ev)
-        if (e) (void)hipEventDestroy(e);
+    hx_owned_free_all(st->ctx, st->owned);
+    for (hx_stream_timer& t : st->timer) hx_stream_timer_destroy(t);
     delete st;
     return 0;
 }
@@ -355,34 +341,34 @@ int hx_star_run(hx_star* st, int n_stars, const double* bb_temp, const double* b
     }
     int rc = st_settle(st);
     if (rc) return rc;
-    st->timed[0] = st->timed[1] = st->timed[2] = false;
     if (stages & 1) {
         rc = hx_h2d(ctx, st->stars, st->h_stars.data(), (size_t)n_stars * sizeof(StStar));
+        if (!rc) rc = hx_stream_timer_start(ctx, st->timer[0]);
         if (rc) return rc;
-        HX_HIP(ctx, hipEventRecord(st->ev[0], ctx->stream));
         const dim3 grid(hx_cdiv((long long)(st->npad / ST_PER_THREAD), ST_THREADS), n_stars);
         k_star_blend<<<grid, ST_THREADS, 0, ctx->stream>>>(st->corners, st->stars, st->flux, st->npad);
         HX_LAUNCH_CHECK(ctx);
-        HX_HIP(ctx, hipEventRecord(st->ev[1], ctx->stream));
-        st->timed[0] = true;
+        rc = hx_stream_timer_stop(ctx, st->timer[0]);
+        if (rc) return rc;
     }
     if (stages & 2) {
         std::vector<double> td(2 * (size_t)n_stars);
         for (int s = 0; s < n_stars; s++) { td[2 * s] = bb_temp[s]; td[2 * s + 1] = bb_prefactor[s]; }
         rc = hx_h2d(ctx, st->temp_d, td.data(), td.size() * 8);
+        if (!rc) rc = hx_stream_timer_start(ctx, st->timer[1]);
         if (rc) return rc;
-        HX_HIP(ctx, hipEventRecord(st->ev[2], ctx->stream));
         k_star_planck_bins<<<dim3(hx_cdiv(st->nbin, ST_THREADS), n_stars), ST_THREADS, 0, ctx->stream>>>(
             st->inter, st->temp_d, st->planck, st->nbin, hc, kb);
         HX_LAUNCH_CHECK(ctx);
-        HX_HIP(ctx, hipEventRecord(st->ev[3], ctx->stream));
-        st->timed[1] = true;
+        rc = hx_stream_timer_stop(ctx, st->timer[1]);
+        if (rc) return rc;
     }
     if (stages & 4) {
         StGrid G;
         G.lam = st->lam; G.inter = st->inter; G.pbot = st->pbot; G.state = st->state; G.flux = st->flux; G.planck = st->planck;
         G.out = st->out; G.npad = st->npad; G.N = st->N; G.nbin = st->nbin;
-        HX_HIP(ctx, hipEventRecord(st->ev[4], ctx->stream));
+        rc = hx_stream_timer_start(ctx, st->timer[2]);
+        if (rc) return rc;
         // bins with an interface outside the table or of few points; the kernel leaves the long ones alone
         k_star_rebin_narrow<<<dim3(hx_cdiv(st->nbin, ST_THREADS), n_stars), ST_THREADS, 0, ctx->stream>>>(G);
         HX_LAUNCH_CHECK(ctx);
@@ -391,12 +377,9 @@ int hx_star_run(hx_star* st, int n_stars, const double* bb_temp, const double* b
             k_star_rebin_wide<<<dim3(st->nwide, n_stars), ST_THREADS, lds, ctx->stream>>>(G, st->wide, st->chunk);
             HX_LAUNCH_CHECK(ctx);
         }
-        st->timed[2] = true;
-    } else {
-        HX_HIP(ctx, hipEventRecord(st->ev[4], ctx->stream));
+        rc = hx_stream_timer_stop(ctx, st->timer[2]);
+        if (rc) return rc;
     }
-    HX_HIP(ctx, hipEventRecord(st->ev[5], ctx->stream));
-    st->pending = true;
     st->timing[3] += 1.0;
     return 0;
 }
@@ -406,24 +389,19 @@ int hx_star_get(hx_star* st, const char* name, void* out, size_t out_bytes) {
     hx_context* ctx = st->ctx;
     int rc = st_settle(st);
     if (rc) return rc;
-    const std::string n(name);
-    if (n == "timing_ms") {
-        if (out_bytes != sizeof st->timing) return hx_fail(ctx, HX_E_ARG, "hx_star_get(timing_ms): 32 bytes expected");
-        memcpy(out, st->timing, sizeof st->timing);
-        return 0;
-    }
     const size_t ns = (size_t)st->nstar;
-    if (n == "flux") {                 // [s][n_points], without the padding of the device rows
+    if (!strcmp(name, "flux")) {       // [s][n_points], without the padding of the device rows
         if (out_bytes != ns * st->N * 8) return hx_fail(ctx, HX_E_ARG, "hx_star_get(flux): %zu bytes expected", ns * st->N * 8);
         for (size_t s = 0; s < ns && !rc; s++)
             rc = hx_d2h(ctx, (char*)out + s * st->N * 8, st->flux + s * st->npad, (size_t)st->N * 8);
         return rc;
     }
-    const double* src = n == "converted" ? st->out : n == "planck" ? st->planck : nullptr;
-    if (!src) return hx_fail(ctx, HX_E_ARG, "hx_star_get: unknown name '%s'", name);
-    const size_t bytes = ns * st->nbin * 8;
-    if (bytes != out_bytes) return hx_fail(ctx, HX_E_ARG, "hx_star_get(%s): %zu bytes expected, got %zu", name, bytes, out_bytes);
-    return hx_d2h(ctx, out, src, bytes);
+    const hx_result rows[] = {
+        {"timing_ms", st->timing, sizeof st->timing, false, nullptr},
+        {"converted", st->out, ns * st->nbin * 8, true, nullptr},
+        {"planck", st->planck, ns * st->nbin * 8, true, nullptr},
+    };
+    return hx_get_result(ctx, __func__, rows, 3, name, out, out_bytes);
 }
 
 }  // extern "C"

@@ -12,12 +12,13 @@ comparisons); the sort, the scan and the interpolation run in k_ktable_bins, or 
 checker of the device path and what a machine without a GPU gets when it asks for it.
 """
 import argparse
-import ctypes
 import os
 import time
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
+
+from ._tool import DeviceObject, dp, ip, vp
 
 
 K_FLOOR = 1e-15
@@ -291,64 +292,48 @@ def target_grid(temperature_grid=None, pressure_grid=None):
 
 
 # ---- device -------------------------------------------------------------------------------------------------------------
-def _dp(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+def regrid_args(temp_old, press_old, temp_new, press_new):
+    """the plan of a re-gridding as hx_ktable_regrid and hx_ktmix_set_species_native take it: t_left, t_reduced, p_left,
+    p_reduced, temp_old, logp_old, temp_new, logp_new.  The pointers hold their arrays: keep the list until the call is over."""
+    plan = regrid_plan(temp_old, temp_new) + regrid_plan(press_old, press_new)
+    nodes = [np.ascontiguousarray(v, np.float64) for v in (temp_old, np.log10(np.asarray(press_old, np.float64)), temp_new,
+                                                           np.log10(np.asarray(press_new, np.float64)))]
+    return [ip(a) for a in plan] + [dp(a) for a in nodes]
 
 
-def _ip(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-
-
-class KTableBuilder(object):
+class KTableBuilder(DeviceObject):
     """one species' spectral axis and bins on the device; (T, P) slabs go through in batches"""
 
+    PREFIX = "hx_ktable"
+
     def __init__(self, ctx, n_points, n_bins, n_gauss, n_tp, max_tp_per_launch=4, lds_points=LDS_POINTS):
-        from . import _lib
-        self.ctx, self._l = ctx, _lib.lib()
         self.n_points, self.n_bins, self.n_gauss, self.n_tp = int(n_points), int(n_bins), int(n_gauss), int(n_tp)
         self.max_tp = max(1, min(int(max_tp_per_launch), self.n_tp))
         self.ip_nodes = 0
-        h = ctypes.c_void_p()
-        ctx.check(self._l.hx_ktable_create(ctx.handle, self.n_points, self.n_bins, self.n_gauss, self.n_tp, self.max_tp,
-                                           int(lds_points), ctypes.byref(h)), "hx_ktable_create")
-        self.handle = h
+        self._create(ctx, self.n_points, self.n_bins, self.n_gauss, self.n_tp, self.max_tp, int(lds_points))
 
     def set_grid(self, lam, start, end, inter, yg):
         a = [np.ascontiguousarray(lam, np.float64), np.ascontiguousarray(start, np.int32), np.ascontiguousarray(end, np.int32),
              np.ascontiguousarray(inter, np.float64), np.ascontiguousarray(yg, np.float64)]
         assert len(a[0]) == self.n_points and len(a[1]) == len(a[2]) == self.n_bins
         assert len(a[3]) == self.n_bins + 1 and len(a[4]) == self.n_gauss
-        self.ctx.check(self._l.hx_ktable_set_grid(self.handle, _dp(a[0]), _ip(a[1]), _ip(a[2]), _dp(a[3]), _dp(a[4])),
-                       "hx_ktable_set_grid")
+        self._call("set_grid", dp(a[0]), ip(a[1]), ip(a[2]), dp(a[3]), dp(a[4]))
 
     def run(self, slabs, first):
         """`slabs`: fp32 [n][n_points] as the files hold them, n <= max_tp_per_launch; fills nodes first .. first + n - 1.
         Returns once the slabs are on the device; the kernel may still be running."""
         s = np.ascontiguousarray(slabs, np.float32).reshape(-1, self.n_points)
-        self.ctx.check(self._l.hx_ktable_run(self.handle, s.ctypes.data_as(ctypes.c_void_p), int(s.shape[0]), int(first)),
-                       "hx_ktable_run")
+        self._call("run", vp(s), int(s.shape[0]), int(first))
 
     def regrid(self, temp_old, press_old, temp_new, press_new):
         assert len(temp_old) * len(press_old) == self.n_tp
-        tl, tr = regrid_plan(temp_old, temp_new)
-        pl, pr = regrid_plan(press_old, press_new)
-        a = [np.ascontiguousarray(v, np.float64) for v in (temp_old, np.log10(np.asarray(press_old, np.float64)), temp_new,
-                                                           np.log10(np.asarray(press_new, np.float64)))]
-        self.ctx.check(self._l.hx_ktable_regrid(self.handle, len(temp_old), len(press_old), len(temp_new), len(press_new),
-                                                _ip(tl), _ip(tr), _ip(pl), _ip(pr), *[_dp(v) for v in a]), "hx_ktable_regrid")
+        plan = regrid_args(temp_old, press_old, temp_new, press_new)
+        self._call("regrid", len(temp_old), len(press_old), len(temp_new), len(press_new), *plan)
         self.ip_nodes = len(temp_new) * len(press_new)
 
-    def get(self, name):
-        n = {"kpoints": self.n_tp, "kpoints_ip": self.ip_nodes}.get(name)
-        out = np.zeros(4 if name == "timing_ms" else n * self.n_bins * self.n_gauss, np.float64)
-        self.ctx.check(self._l.hx_ktable_get(self.handle, name.encode(), out.ctypes.data_as(ctypes.c_void_p), out.nbytes),
-                       "hx_ktable_get(%s)" % name)
-        return out
-
-    def close(self):
-        if self.handle:
-            self._l.hx_ktable_destroy(self.handle)
-            self.handle = None
+    def _results(self):
+        nc = self.n_bins * self.n_gauss
+        return {"kpoints": self.n_tp * nc, "kpoints_ip": self.ip_nodes * nc, "timing_ms": 4}
 
 
 # ---- one species ----------------------------------------------------------------------------------------------------------

@@ -41,7 +41,6 @@ fails later with a TypeError); `temperatures` is written as doubles.
 Two backends: numpy (the checker, and what a machine without a GPU gets) and hip -- the tables stay on the device in a
 `Mixer`, and every further chemistry of a sweep is one upload of mixing ratios and one kernel pass.
 """
-import ctypes
 import os
 import time
 
@@ -50,7 +49,8 @@ import numpy as np
 from . import continuum
 from . import continuum_data as cd
 from . import phys_const as pc
-from .ktable import numpy_regrid, regrid_plan, target_grid, write_table
+from ._tool import DeviceObject, dp
+from .ktable import numpy_regrid, regrid_args, target_grid, write_table
 from .species_data import species_lib
 
 CONTINUUM = ("H-_bf", "H-_ff", "He-")
@@ -268,32 +268,21 @@ def numpy_scat(sigmas, x, wave, temp, press):
 
 
 # ---- the device ----------------------------------------------------------------------------------------------------------
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-
-
-def _ip(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-
-
-class Mixer(object):
+class Mixer(DeviceObject):
     """the species' tables on the final grid, resident on the device; `run` is one chemistry"""
 
+    PREFIX = "hx_ktmix"
+
     def __init__(self, ctx, nbin, ny, nt, npress, nspecies):
-        from . import _lib
-        self.ctx, self._l = ctx, _lib.lib()
         self.nbin, self.ny, self.nt, self.np, self.ns = int(nbin), int(ny), int(nt), int(npress), int(nspecies)
         self.nc, self.nodes = self.nbin * self.ny, self.nt * self.np
-        h = ctypes.c_void_p()
-        ctx.check(self._l.hx_ktmix_create(ctx.handle, self.nbin, self.ny, self.nt, self.np, self.ns, ctypes.byref(h)),
-                  "hx_ktmix_create")
-        self.handle = h
+        self._create(ctx, self.nbin, self.ny, self.nt, self.np, self.ns)
         self.temp = self.press = None
 
     def set_grid(self, wave, temp, press):
         a = [np.ascontiguousarray(v, np.float64) for v in (wave, temp, press)]
         assert len(a[0]) == self.nbin and len(a[1]) == self.nt and len(a[2]) == self.np
-        self.ctx.check(self._l.hx_ktmix_set_grid(self.handle, *[_dp(v) for v in a]), "hx_ktmix_set_grid")
+        self._call("set_grid", *[dp(v) for v in a])
         self.temp, self.press = a[1], a[2]
 
     def set_species(self, s, table):
@@ -302,49 +291,31 @@ class Mixer(object):
             t = np.ascontiguousarray(table, np.float64).reshape(-1)
             if t.size != self.nodes * self.nc:
                 raise IOError("ktable: a table of %d entries for a grid of %d" % (t.size, self.nodes * self.nc))
-        self.ctx.check(self._l.hx_ktmix_set_species(self.handle, int(s), _dp(t)), "hx_ktmix_set_species")
+        self._call("set_species", int(s), dp(t))
 
     def set_species_native(self, s, table, temp_old, press_old):
         assert self.temp is not None, "set the grid first"
         t = np.ascontiguousarray(table, np.float64).reshape(-1)
         if t.size != len(temp_old) * len(press_old) * self.nc:
             raise IOError("ktable: a native table of %d entries for %d x %d nodes" % (t.size, len(temp_old), len(press_old)))
-        tl, tr = regrid_plan(temp_old, self.temp)
-        pl, pr = regrid_plan(press_old, self.press)
-        a = [np.ascontiguousarray(v, np.float64) for v in (temp_old, np.log10(np.asarray(press_old, np.float64)), self.temp,
-                                                           np.log10(self.press))]
-        self.ctx.check(self._l.hx_ktmix_set_species_native(self.handle, int(s), _dp(t), len(temp_old), len(press_old), _ip(tl),
-                                                           _ip(tr), _ip(pl), _ip(pr), *[_dp(v) for v in a]),
-                       "hx_ktmix_set_species_native")
+        plan = regrid_args(temp_old, press_old, self.temp, self.press)
+        self._call("set_species_native", int(s), dp(t), len(temp_old), len(press_old), *plan)
 
     def set_rayleigh(self, s, sigma, is_h2o=False):
         g = None if sigma is None else np.ascontiguousarray(sigma, np.float64)
         assert g is None or len(g) == self.nbin
-        self.ctx.check(self._l.hx_ktmix_set_rayleigh(self.handle, int(s), _dp(g), 1 if is_h2o else 0), "hx_ktmix_set_rayleigh")
+        self._call("set_rayleigh", int(s), dp(g), 1 if is_h2o else 0)
 
     def run(self, mmr, vmr_scat):
         m, v = [np.ascontiguousarray(a, np.float64).reshape(-1) for a in (mmr, vmr_scat)]
         assert m.size == v.size == self.ns * self.nodes
-        self.ctx.check(self._l.hx_ktmix_run(self.handle, _dp(m), _dp(v)), "hx_ktmix_run")
+        self._call("run", dp(m), dp(v))
 
-    def get(self, name):
-        if name == "timing_ms":
-            n = 4
-        elif name in ("scat_cross", "scat_cross_guard"):
-            n = self.nbin * (self.nodes if name == "scat_cross" else 1)
-        elif name == "kpoints_guard":
-            n = self.nc
-        else:
-            n = self.nodes * self.nc
-        out = np.zeros(n, np.float64)
-        self.ctx.check(self._l.hx_ktmix_get(self.handle, name.encode(), out.ctypes.data_as(ctypes.c_void_p), out.nbytes),
-                       "hx_ktmix_get(%s)" % name)
-        return out
-
-    def close(self):
-        if self.handle:
-            self._l.hx_ktmix_destroy(self.handle)
-            self.handle = None
+    def _results(self):
+        table = {"timing_ms": 4, "kpoints": self.nodes * self.nc, "kpoints_guard": self.nc, "scat_cross": self.nodes * self.nbin,
+                 "scat_cross_guard": self.nbin}
+        table.update(("species_%d" % s, self.nodes * self.nc) for s in range(self.ns))
+        return table
 
 
 # ---- containers ------------------------------------------------------------------------------------------------------------

@@ -36,12 +36,12 @@ refused with its radius, wavelength and byte count before anything is launched. 
 vectorised over the pairs in fp64: the checker of the device path, and what a machine without a GPU gets when it asks for it.
 """
 import argparse
-import ctypes
 import os
 import time
 
 import numpy as np
 
+from ._tool import DeviceObject, dp, ip
 from .clouds import R_VALUES
 
 X_SMALL = 0.5
@@ -196,24 +196,17 @@ def numpy_series(x, m_re, m_im):
 
 
 # ---- device ---------------------------------------------------------------------------------------------------------------
-def _dp(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-
-
-class MieSeries(object):
+class MieSeries(DeviceObject):
     """hx_mie: up to n_pairs_max pairs per run through a D buffer of scratch_bytes"""
 
+    PREFIX = "hx_mie"
     GUARD = 0x7ff8dead0badbeef
 
     def __init__(self, ctx, n_pairs_max, scratch_bytes=None):
-        from . import _lib
-        self.ctx, self._l = ctx, _lib.lib()
         self.n_pairs_max = int(n_pairs_max)
         self.scratch_bytes = SCRATCH_BYTES if scratch_bytes is None else int(scratch_bytes)
         self.n_pairs = 0
-        h = ctypes.c_void_p()
-        ctx.check(self._l.hx_mie_create(ctx.handle, self.n_pairs_max, self.scratch_bytes, ctypes.byref(h)), "hx_mie_create")
-        self.handle = h
+        self._create(ctx, self.n_pairs_max, self.scratch_bytes)
 
     def run(self, x, m_re, m_im, order=None):
         """`order`: the sequence in which the pairs are dealt to lanes; None: by N, descending"""
@@ -224,29 +217,14 @@ class MieSeries(object):
                 order = np.argsort(-n_terms(np.where(x > 0, x, 1.0)), kind="stable")
         order = np.ascontiguousarray(order, np.int32)
         assert len(order) == len(x)
-        self.ctx.check(self._l.hx_mie_run(self.handle, len(x), _dp(x), _dp(m_re), _dp(m_im),
-                                          order.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), "hx_mie_run")
+        self._call("run", len(x), dp(x), dp(m_re), dp(m_im), ip(order))
         self.n_pairs = len(x)
 
-    def get(self, name):
-        if name == "guard":
-            out = np.zeros(5, np.uint64)
-        elif name == "timing_ms":
-            out = np.zeros(2, np.float64)
-        else:
-            out = np.zeros(self.n_pairs, np.float64)
-        self.ctx.check(self._l.hx_mie_get(self.handle, name.encode(), out.ctypes.data_as(ctypes.c_void_p), out.nbytes),
-                       "hx_mie_get(%s)" % name)
-        return out
+    def _results(self):
+        return {"guard": (5, np.uint64), "timing_ms": 2, "q_ext": self.n_pairs, "q_sca": self.n_pairs, "g": self.n_pairs}
 
     def guards_intact(self):
         return bool(np.all(self.get("guard") == np.uint64(self.GUARD)))
-
-    def close(self):
-        if self.handle:
-            self._l.hx_mie_destroy(self.handle)
-            self.handle = None
-
 
 def device_series(x, m_re, m_im, ctx=None, scratch_bytes=None, order=None, timing=None):
     """(Q_ext, Q_sca, g) per pair from k_mie"""

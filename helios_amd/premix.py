@@ -8,15 +8,14 @@ refresh's species loop (random overlap or correlated-k), `write_premixed_table` 
 map says how far the premixed look-up's bilinear value is from the on-the-fly mix at the centre of every table cell.
 """
 import argparse
-import ctypes
 import os
 import time
 
 import numpy as np
 
-from . import _lib
 from . import hdf5_lite
 from . import host_functions as hsfunc
+from ._tool import DeviceObject, dp
 
 RO_NY = 20          # Gauss points of the random-overlap kernel (csrc/random_overlap.h, ro::NY)
 UNIFORM_RTOL = 1e-9
@@ -116,66 +115,46 @@ def species_mixing_ratios(quant, reader):
 
 
 # ---- device -----------------------------------------------------------------------------------------------------------
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-
-
-class Premixer(object):
+class Premixer(DeviceObject):
     """the species tables on the device (uploaded once) and the runs over them"""
 
+    PREFIX = "hx_premix"
+
     def __init__(self, ctx, nbin, ny, ntemp, npress, nspecies, refine=(1, 1), correlated_k=False):
-        self.ctx, self._l = ctx, _lib.lib()
         self.nbin, self.ny, self.nspecies = int(nbin), int(ny), int(nspecies)
         self.nT, self.nP = output_grid_size(ntemp, npress, refine)
-        h = ctypes.c_void_p()
-        ctx.check(self._l.hx_premix_create(ctx.handle, int(nbin), int(ny), int(ntemp), int(npress), int(nspecies),
-                                           int(refine[0]), int(refine[1]), 1 if correlated_k else 0, ctypes.byref(h)),
-                  "hx_premix_create")
-        self.handle = h
-
-    def _ck(self, rc, what):
-        self.ctx.check(rc, what)
+        self._create(ctx, int(nbin), int(ny), int(ntemp), int(npress), int(nspecies), int(refine[0]), int(refine[1]),
+                     1 if correlated_k else 0)
 
     def set_grid(self, wave, gauss_y, gauss_w, ktemp, kpress):
         a = [np.ascontiguousarray(v, np.float64) for v in (wave, gauss_y, gauss_w, ktemp, kpress)]
-        self._ck(self._l.hx_premix_set_grid(self.handle, *[_dp(v) for v in a]), "hx_premix_set_grid")
+        self._call("set_grid", *[dp(v) for v in a])
 
     def set_species(self, s, pretab, scat_cross, vmr_table, vmr_const, weight, absorbing, scattering, is_h2o=0, is_cia=0,
                     in_mu=1):
         a = [None if v is None else np.ascontiguousarray(v, np.float64) for v in (pretab, scat_cross, vmr_table)]
-        self._ck(self._l.hx_premix_set_species(self.handle, int(s), _dp(a[0]), _dp(a[1]), _dp(a[2]), float(vmr_const),
-                                               float(weight), int(absorbing), int(scattering), int(is_h2o), int(is_cia),
-                                               int(in_mu)), "hx_premix_set_species")
+        self._call("set_species", int(s), dp(a[0]), dp(a[1]), dp(a[2]), float(vmr_const), float(weight), int(absorbing),
+                   int(scattering), int(is_h2o), int(is_cia), int(in_mu))
 
     def set_species_separable(self, s, kxy, ftp):
         a, b = np.ascontiguousarray(kxy, np.float64), np.ascontiguousarray(ftp, np.float64)
-        self._ck(self._l.hx_premix_set_species_separable(self.handle, int(s), _dp(a), _dp(b)),
-                 "hx_premix_set_species_separable")
+        self._call("set_species_separable", int(s), dp(a), dp(b))
 
     def set_species_vmr(self, s, vmr_table, vmr_const=0.0):
         t = None if vmr_table is None else np.ascontiguousarray(vmr_table, np.float64)
-        self._ck(self._l.hx_premix_set_species_vmr(self.handle, int(s), _dp(t), float(vmr_const)), "hx_premix_set_species_vmr")
+        self._call("set_species_vmr", int(s), dp(t), float(vmr_const))
 
     def set_slab_rows(self, rows):
-        self._ck(self._l.hx_premix_set_slab_rows(self.handle, int(rows)), "hx_premix_set_slab_rows")
+        self._call("set_slab_rows", int(rows))
 
     def run(self, cell_error=True):
-        self._ck(self._l.hx_premix_run(self.handle, 1 if cell_error else 0), "hx_premix_run")
+        self._call("run", 1 if cell_error else 0)
 
-    def get(self, name):
+    def _results(self):
         nT, nP, nc = self.nT, self.nP, self.nbin * self.ny
-        n = {"temperatures": nT, "pressures": nP, "kpoints": nT * nP * nc, "scat_cross": nT * nP * self.nbin,
-             "meanmolmass": nT * nP, "cell_error_max": (nT - 1) * (nP - 1), "cell_error_mean": (nT - 1) * (nP - 1),
-             "timing_ms": 4}[name]
-        out = np.zeros(n, np.float64)
-        self._ck(self._l.hx_premix_get(self.handle, name.encode(), out.ctypes.data_as(ctypes.c_void_p), out.nbytes),
-                 "hx_premix_get(%s)" % name)
-        return out
-
-    def close(self):
-        if self.handle:
-            self._l.hx_premix_destroy(self.handle)
-            self.handle = None
+        return {"temperatures": nT, "pressures": nP, "kpoints": nT * nP * nc, "scat_cross": nT * nP * self.nbin,
+                "meanmolmass": nT * nP, "cell_error_max": (nT - 1) * (nP - 1), "cell_error_mean": (nT - 1) * (nP - 1),
+                "timing_ms": 4}
 
 
 def _settings(quant, refine, cell_error):

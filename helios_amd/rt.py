@@ -10,6 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._tool import dp as _dp
 
 
 class RtDims(ctypes.Structure):
@@ -49,10 +50,6 @@ def _check_struct_sizes(l):
     if got != (a.value, b.value, c.value):
         raise _lib.HeliosHipError("hx_rt_* struct layout mismatch: python %r, library %r"
                                   % (got, (a.value, b.value, c.value)))
-
-
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
 def _f64(a):

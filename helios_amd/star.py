@@ -13,7 +13,6 @@ path and what a machine without a GPU gets when it asks for it.  Nothing is ever
 error that names it.
 """
 import argparse
-import ctypes
 import os
 import time
 
@@ -22,6 +21,7 @@ import numpy as np
 from . import fits_lite
 from . import hdf5_lite
 from . import phys_const as pc
+from ._tool import DeviceObject, dp, ip, vp
 
 PARSEC = 3.0856775814913674e18        # cm: 648000 / pi astronomical units
 PHOENIX_WAVE_FILE = "WAVE_PHOENIX-ACES-AGSS-COND-2011.fits"
@@ -348,68 +348,47 @@ def fit_bb_temperature(inter, index, bin_flux, start_temp):
 
 
 # ---- device -------------------------------------------------------------------------------------------------------------
-def _dp(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-
-
-def _ip(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
-
-
-class StarBuilder(object):
+class StarBuilder(DeviceObject):
     """stars that share their tabulated wavelengths and the grid, on the device"""
 
+    PREFIX = "hx_star"
     BLEND, PLANCK, REBIN = 1, 2, 4
 
     def __init__(self, ctx, n_points, n_corners, n_stars, n_bins, chunk=CHUNK):
-        from . import _lib
-        self.ctx, self._l = ctx, _lib.lib()
         self.n_points, self.n_corners, self.n_stars, self.n_bins = int(n_points), int(n_corners), int(n_stars), int(n_bins)
-        h = ctypes.c_void_p()
-        ctx.check(self._l.hx_star_create(ctx.handle, self.n_points, self.n_corners, self.n_stars, self.n_bins, int(chunk),
-                                         ctypes.byref(h)), "hx_star_create")
-        self.handle = h
+        self._create(ctx, self.n_points, self.n_corners, self.n_stars, self.n_bins, int(chunk))
 
     def add_corner(self, slot, flux32):
         f = np.ascontiguousarray(flux32, np.float32)
         assert f.shape == (self.n_points,)
-        self.ctx.check(self._l.hx_star_add_corner(self.handle, int(slot), f.ctypes.data_as(ctypes.c_void_p)), "hx_star_add_corner")
+        self._call("add_corner", int(slot), vp(f))
 
     def set_grid(self, lam, inter, pbot, state):
         a = [np.ascontiguousarray(lam, np.float64), np.ascontiguousarray(inter, np.float64),
              np.ascontiguousarray(pbot, np.int32), np.ascontiguousarray(state, np.int32)]
         assert len(a[0]) == self.n_points and len(a[1]) == len(a[2]) == len(a[3]) == self.n_bins + 1
-        self.ctx.check(self._l.hx_star_set_grid(self.handle, _dp(a[0]), _dp(a[1]), _ip(a[2]), _ip(a[3])), "hx_star_set_grid")
+        self._call("set_grid", dp(a[0]), dp(a[1]), ip(a[2]), ip(a[3]))
 
     def set_star(self, s, slots, weights, div):
         sl, w = np.ascontiguousarray(slots, np.int32), np.ascontiguousarray(weights, np.float64).reshape(-1)
         assert len(w) == 3 * len(sl)
-        self.ctx.check(self._l.hx_star_set_star(self.handle, int(s), len(sl), _ip(sl), _dp(w), float(div)), "hx_star_set_star")
+        self._call("set_star", int(s), len(sl), ip(sl), dp(w), float(div))
 
     def put_flux(self, s, flux):
         f = np.ascontiguousarray(flux, np.float64)
         assert f.shape == (self.n_points,)
-        self.ctx.check(self._l.hx_star_put_flux(self.handle, int(s), _dp(f)), "hx_star_put_flux")
+        self._call("put_flux", int(s), dp(f))
 
     def run(self, stages, bb_temps=None, n_stars=None):
         n = self.n_stars if n_stars is None else int(n_stars)
         t = np.zeros(n, np.float64) if bb_temps is None else np.ascontiguousarray(bb_temps, np.float64)
         assert len(t) == n
         d = np.array([planck_prefactor(float(v)) for v in t], np.float64)
-        self.ctx.check(self._l.hx_star_run(self.handle, n, _dp(t), _dp(d), pc.H * pc.C, pc.K_B, int(stages)), "hx_star_run")
+        self._call("run", n, dp(t), dp(d), pc.H * pc.C, pc.K_B, int(stages))
 
-    def get(self, name):
-        shape = {"flux": (self.n_stars, self.n_points), "converted": (self.n_stars, self.n_bins),
-                 "planck": (self.n_stars, self.n_bins), "timing_ms": (4,)}[name]
-        out = np.zeros(shape, np.float64)
-        self.ctx.check(self._l.hx_star_get(self.handle, name.encode(), out.ctypes.data_as(ctypes.c_void_p), out.nbytes),
-                       "hx_star_get(%s)" % name)
-        return out
-
-    def close(self):
-        if self.handle:
-            self._l.hx_star_destroy(self.handle)
-            self.handle = None
+    def _results(self):
+        return {"flux": (self.n_stars, self.n_points), "converted": (self.n_stars, self.n_bins),
+                "planck": (self.n_stars, self.n_bins), "timing_ms": 4}
 
 
 # ---- stars onto one grid --------------------------------------------------------------------------------------------------

@@ -637,8 +637,8 @@ int hx_star_get(hx_star* st, const char* name, void* out, size_t out_bytes);
  *   hx_ktmix_set_grid            wave[nbin] bin centres (cm), temp[nt] (K), press[np] (dyne cm^-2), all > 0
  *   hx_ktmix_set_species         a table [nt][np][nbin][ny] on the final grid into slot s, uploaded in pieces of 64 MiB; NULL: the
  *                                species does not absorb (its slot is freed)
- *   hx_ktmix_set_species_native  a table on its own nt_old x np_old nodes: uploaded, re-gridded into the slot by k_ktmix_regrid
- *                                (hx_ktable_regrid's plan arrays, branches and term order), the native copy freed
+ *   hx_ktmix_set_species_native  a table on its own nt_old x np_old nodes: uploaded, re-gridded into the slot by k_ktable_regrid
+ *                                (hx_ktable_regrid's plan arrays and its kernel), the native copy freed
  *   hx_ktmix_set_rayleigh        sigma[nbin] of slot s; is_h2o = 1 (with sigma NULL): water vapour, evaluated per node and bin
  *                                by stage 2's own formula; NULL and 0: the species contributes nothing
  *   hx_ktmix_run                 one chemistry: mmr[nspecies][nt * np] (the mass mixing ratios, read for the absorbing slots)
@@ -646,7 +646,7 @@ int hx_star_get(hx_star* st, const char* name, void* out, size_t out_bytes);
  *   hx_ktmix_get                 "kpoints", "scat_cross", "species_<s>" (the slot), "kpoints_guard" [nbin * ny] and
  *                                "scat_cross_guard" [nbin] (the guard rows: every double the bit pattern 0x7ff8dead0badbeef),
  *                                "timing_ms" (double[4]: ms in k_ktmix_sum and in k_ktmix_scat of the last run, ms in
- *                                k_ktmix_regrid so far, runs)
+ *                                k_ktable_regrid so far, runs)
  */
 typedef struct hx_ktmix hx_ktmix;
 int hx_ktmix_create(hx_context* ctx, int nbin, int ny, int nt, int np, int nspecies, hx_ktmix** out_km);

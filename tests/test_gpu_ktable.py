@@ -9,6 +9,7 @@ import pytest
 
 import ktable_cases as kc
 from helios_amd import ktable
+from helios_amd._tool import dp
 
 pytestmark = pytest.mark.gpu
 
@@ -54,7 +55,7 @@ def test_regridding_on_the_device(ctx):
     nx = len(g["center wavelengths"])
     b = ktable.KTableBuilder(ctx, 2000, nx, 20, 4)
     try:
-        ctx.check(b._l.hx_ktable_put(b.handle, ktable._dp(np.ascontiguousarray(g["kpoints"], np.float64))), "hx_ktable_put")
+        ctx.check(b._l.hx_ktable_put(b.handle, dp(np.ascontiguousarray(g["kpoints"], np.float64))), "hx_ktable_put")
         b.regrid(g["temperatures"], g["pressures"], g["regrid_temperatures"], g["regrid_pressures"])
         got = b.get("kpoints_ip")
         np.testing.assert_array_equal(b.get("kpoints"), g["kpoints"])

@@ -21,6 +21,7 @@ import pytest
 import ktable_reference as kr
 from helios_amd import ktable
 from helios_amd._lib import HeliosHipError
+from helios_amd._tool import dp, ip
 
 pytestmark = pytest.mark.gpu
 
@@ -144,7 +145,7 @@ def device_regrid(ctx, temps, press, k, nx, ny, targets):
     """kpoints_ip per (temp_new, press_new) of `targets`, one after the other on the same builder"""
     b = ktable.KTableBuilder(ctx, 8, nx, ny, len(temps) * len(press))
     try:
-        ctx.check(b._l.hx_ktable_put(b.handle, ktable._dp(np.ascontiguousarray(k, np.float64))), "hx_ktable_put")
+        ctx.check(b._l.hx_ktable_put(b.handle, dp(np.ascontiguousarray(k, np.float64))), "hx_ktable_put")
         out = []
         for temp_new, press_new in targets:
             b.regrid(temps, press, temp_new, press_new)
@@ -259,9 +260,9 @@ def test_refusals(ctx):
 
         def regrid(nt_old, np_old, t_left, t_red, p_left, p_red):
             t_old, p_old = (one, five) if nt_old == 1 else (five, one)
-            ctx.check(b._l.hx_ktable_regrid(b.handle, nt_old, np_old, 1, 1, ktable._ip(t_left), ktable._ip(t_red),
-                                            ktable._ip(p_left), ktable._ip(p_red), ktable._dp(t_old), ktable._dp(p_old),
-                                            ktable._dp(new), ktable._dp(new)), "hx_ktable_regrid")
+            ctx.check(b._l.hx_ktable_regrid(b.handle, nt_old, np_old, 1, 1, ip(t_left), ip(t_red),
+                                            ip(p_left), ip(p_red), dp(t_old), dp(p_old),
+                                            dp(new), dp(new)), "hx_ktable_regrid")
 
         clamped = np.ones(1, np.int32)
         with pytest.raises(HeliosHipError, match="not the table's number"):

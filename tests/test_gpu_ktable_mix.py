@@ -1,5 +1,5 @@
 """The kernels of the mixing stage (csrc/ktable_mix.hip) at the smallest shapes that reach every path: k_ktmix_sum bit for bit
-against the numpy backend (the same two roundings per term, in the same order), k_ktmix_regrid and the water part of
+against the numpy backend (the same two roundings per term, in the same order), the re-gridding into a slot and the water part of
 k_ktmix_scat under the rule of tests/test_gpu_ktable_edges.py -- within max(1e-13, 8 eps64) of the long-double restatement,
 eps64 the numpy backend's own deviation there -- the error paths by message, the two backends on the whole tool call of golden
 case a, and the chain this stage closes: a premixed helios.py run from a file this tool wrote on the hard-coded grid, where
@@ -10,10 +10,12 @@ import numpy as np
 import pytest
 
 import ktable_mix_reference as kr
+import ktable_reference as ktr
 from ktable_reference import LD, reference_regrid
 from test_ktable_mix import case_inputs, final, grid, held, lines, load, restated, tool          # noqa: F401 -- fixtures
 from helios_amd import ktable, ktable_mix
 from helios_amd._lib import HeliosHipError
+from helios_amd._tool import dp, ip
 
 pytestmark = pytest.mark.gpu
 
@@ -106,7 +108,7 @@ def test_no_absorber_gives_zeros(ctx):
         m.close()
 
 
-# ---- k_ktmix_regrid ------------------------------------------------------------------------------------------------------------
+# ---- the re-gridding into a slot (k_ktable_regrid) -------------------------------------------------------------------------------
 REGRID_T = [100.0, 200.0, 201.0, 450.0, 700.0, 900.0, 2500.0]              # below, on, between and above the nodes
 REGRID_P = [1e-2, 1e1, 50.0, 1e3, 1e5, 3e6, 1e8, 1e10]
 
@@ -133,6 +135,36 @@ def test_regrid_against_the_restatement(ctx, source, nc):
     dev = np.abs((got.astype(LD) - exact) / exact).astype(np.float64)
     print("regrid %s, nc %d: device %.3e, numpy %.3e" % (source, nc, dev.max(), eps64.max()))
     assert np.all(dev <= np.maximum(1e-13, 8 * eps64)) and np.all(np.isfinite(ex64))
+
+
+@pytest.mark.parametrize("nbin,ny", [(1, 3), (7, 5), (3, 20)])
+@pytest.mark.parametrize("temps,press", ktr.REGRID_SOURCES, ids=["1x1", "1x3", "3x1", "3x4"])
+def test_the_mixer_regrids_bit_for_bit_as_the_builder(ctx, temps, press, nbin, ny):
+    """one re-gridding behind both objects: what Mixer.set_species_native leaves in its slot is KTableBuilder.regrid's kpoints_ip
+    of the same source, and both are numpy_regrid's, to the bit.  Sources with a single temperature or pressure; the 3 x 4 one
+    clamps 4 of the 7 temperatures and 4 of the 9 pressures, so every branch of the kernel runs; rows of 3, 35 and 60 entries"""
+    nc = nbin * ny
+    k = ktr.regrid_source(temps, press, nc)
+    host = ktable.numpy_regrid(press, temps, k, ktr.REGRID_T, ktr.REGRID_P, nbin, ny)
+    assert np.all(np.isfinite(host))
+    if len(temps) * len(press) == 12:
+        assert ktable.regrid_plan(temps, ktr.REGRID_T)[1].sum() == 4 and ktable.regrid_plan(press, ktr.REGRID_P)[1].sum() == 4
+    b = ktable.KTableBuilder(ctx, 8, nbin, ny, len(temps) * len(press))
+    try:
+        ctx.check(b._l.hx_ktable_put(b.handle, dp(np.ascontiguousarray(k, np.float64))), "hx_ktable_put")
+        b.regrid(temps, press, ktr.REGRID_T, ktr.REGRID_P)
+        built = b.get("kpoints_ip")
+    finally:
+        b.close()
+    m = ktable_mix.Mixer(ctx, nbin, ny, len(ktr.REGRID_T), len(ktr.REGRID_P), 2)
+    try:
+        m.set_grid(np.linspace(1e-4, 2e-4, nbin), ktr.REGRID_T, ktr.REGRID_P)
+        m.set_species_native(1, k, temps, press)
+        mixed = m.get("species_1")
+    finally:
+        m.close()
+    np.testing.assert_array_equal(mixed, built)
+    np.testing.assert_array_equal(built, host)
 
 
 # ---- k_ktmix_scat ----------------------------------------------------------------------------------------------------------------
@@ -212,9 +244,9 @@ def test_error_paths_by_message(ctx):
             bad = np.array([5, 5], np.int32)
             ok = np.zeros(2, np.int32)
             a = np.array([100.0, 200.0])
-            m.ctx.check(m._l.hx_ktmix_set_species_native(m.handle, 0, ktable_mix._dp(np.ones(48)), 2, 2, ktable_mix._ip(bad),
-                                                         ktable_mix._ip(ok), ktable_mix._ip(ok), ktable_mix._ip(ok),
-                                                         *[ktable_mix._dp(a)] * 4), "hx_ktmix_set_species_native")
+            m.ctx.check(m._l.hx_ktmix_set_species_native(m.handle, 0, dp(np.ones(48)), 2, 2, ip(bad),
+                                                         ip(ok), ip(ok), ip(ok),
+                                                         *[dp(a)] * 4), "hx_ktmix_set_species_native")
     finally:
         m.close()
 
