@@ -1,6 +1,7 @@
 // What the objects of the off-line tools (hx_ktable, hx_ktmix, hx_premix, hx_star, hx_mie) share around their kernels: the list
 // of an object's device allocations, an event pair that times a stretch of the stream and is read later, the tail of hx_*_get,
-// and the re-gridding of a table onto another (T, P) grid.  The kernels and the state of the objects stay with the objects.
+// the rows of the batch object's (hx_rt) named arrays, and the re-gridding of a table onto another (T, P) grid.  The kernels and the
+// state of the objects stay with the objects.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -97,6 +98,28 @@ inline int hx_get_result(hx_context* ctx, const char* fn, const hx_result* rows,
         return 0;
     }
     return hx_fail(ctx, HX_E_ARG, "%s: unknown name '%s'", fn, name);
+}
+
+// ---- the same for an object that holds a stretch of memory per column (hx_rt) and serves a name through up to three calls:
+// a row per name; hx_find_array looks a name up among the rows that serve `call` ---------------------------------------------
+enum : unsigned { HX_GET = 1, HX_SET = 2, HX_PTR = 4, HX_ANY_COL = 8 };   // (HX_ANY_COL: one value for the batch, no column is looked at)
+struct hx_column_array {
+    const char* name;
+    const void* base;           // column 0's first element
+    size_t stride, count;       // elements from one column to the next (0: one array for all columns), elements served
+    size_t elem;                // bytes per element
+    unsigned serves;
+    bool on_device;
+    const char* not_ready;      // null, or why the object's state does not hold the array yet (HX_E_STATE)
+
+    size_t bytes() const { return count * elem; }
+    void* at(int col) const { return (char*)base + (size_t)col * stride * elem; }
+};
+
+inline const hx_column_array* hx_find_array(const std::vector<hx_column_array>& rows, const char* name, unsigned call) {
+    for (const hx_column_array& r : rows)
+        if ((r.serves & call) && strcmp(r.name, name) == 0) return &r;
+    return nullptr;
 }
 
 // ---- re-gridding (k_ktable_regrid, ktable.hip): a table [nt_old][np_old][nc] onto nt_new x np_new nodes.  The plan names per

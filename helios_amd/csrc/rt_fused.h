@@ -71,7 +71,6 @@ struct hx_rt {
     double *T_lay_ref = nullptr, *T_int_ref = nullptr;  // temperatures of the last refresh
     int nchunk;  // x-chunks of the totals reduction
     int coef_tpb = 4;  // k_rt_coef: tiles (wavefronts) per workgroup
-    hipError_t shmem_rc = hipSuccess;
     bool cloud_lds = true;       // k_rt_coef stages the clouds' half-layer terms in LDS when they fit (HELIOS_RT_CLOUD_LDS)
     bool serpentine = false;     // k_rt_flux walks its grid back and forth from launch to launch (HELIOS_RT_SERPENTINE)
     unsigned flux_launches = 0;

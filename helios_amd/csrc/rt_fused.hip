@@ -4,7 +4,8 @@
 // Replaces the body of Compute.radiation_loop (reference source/computation.py:851-984):
 //   refresh  = :860-879  (opacities, mean molecular mass, [species mixing], transmission, dz, beam)
 //   step     = :856-857 + :880-888 + :926-932 (T_int, Planck, 3*scat+1 sweeps, integrate, T step)
-#include "rt_kernels.h"
+#include "hx_tool.h"
+#include "rt_select.h"
 #include "rt_species.h"
 
 #include <algorithm>
@@ -66,7 +67,7 @@ void choose_workgroup(int Y, int X, int max_threads, TileGeom& g) {
 // (round 6, rt_kernels.h flux_one_wave) -- chosen only where no other lane count avoids them
 bool flux_variant_spills(int rows, int k) { return rows >= 15 || (rows == 14 && k != 16); }
 
-bool choose_geometry(int H, int Y, int X, int C, int dir_beam, int scat_corr, TileGeom& g, int matrix = 0) {
+bool choose_geometry(int H, int Y, int X, int C, int dir_beam, int scat_corr, TileGeom& g) {
     // lanes per spectral point: the fewest padded nodes, with the kernels whose scans are written for a compile-time
     // lane count (k = 16, 32, 64) preferred -- measured at 10 000 bins: 50 layers 0.172 ms (k = 16, 12 % padding) against
     // 0.210 ms (k = 8, 4 %), 60 layers 0.194 against 0.256 ms
@@ -99,7 +100,6 @@ bool choose_geometry(int H, int Y, int X, int C, int dir_beam, int scat_corr, Ti
             // without: same-box A/B of round 5, k_rt_flux per launch: 10 000 x 100 with beam 0.465 ms (k = 32, 7 rows) ->
             // 0.434 ms (k = 16, 13 rows); 30 000 x 200 with beam and I2S 3.12-3.40 ms (k = 64, 7 rows) against 3.08-3.13 ms
             // (k = 32, 13 rows), its coefficient kernel 6.4 -> 5.85 ms.  profiles/r05_flux_tilings_beam.txt.)
-            (void)dir_beam;
             if (cost < best_cost) {
                 best_cost = cost;
                 best_k = k;
@@ -138,7 +138,6 @@ bool choose_geometry(int H, int Y, int X, int C, int dir_beam, int scat_corr, Ti
     g.pl_vp = 3;
     g.pl_dd = 3 + g.has_vp;
     g.nplane = 3 + g.has_vp + (dir_beam ? 2 : 0);
-    (void)matrix;   // (the matrix method's direct solve reads the sweeps' planes, nothing more)
     g.tile_rows = g.ROWS;
     g.coef_elems_per_col = (size_t)g.nblk * g.NW * g.nplane * g.ROWS * 64;
     g.flux_elems_per_col = (size_t)g.nblk * g.NW * g.ROWS * 64;
@@ -228,71 +227,6 @@ struct ProfScope {
     }
 };
 
-size_t flux_shmem_bytes(hx_rt* rt) {
-    const TileGeom& g = rt->g;
-    return ((size_t)g.nxb * (rt->H + 3) + (size_t)g.nxb * 2 * rt->I + (size_t)g.ypb * g.nxb * 2 * rt->I) *
-           sizeof(double);
-}
-
-#define DISPATCH_ROWS(fn, rt, a)                  \
-    switch ((rt)->g.ROWS) {                       \
-        case 1: fn<1>(rt, a); break;              \
-        case 2: fn<2>(rt, a); break;              \
-        case 3: fn<3>(rt, a); break;              \
-        case 4: fn<4>(rt, a); break;              \
-        case 5: fn<5>(rt, a); break;              \
-        case 6: fn<6>(rt, a); break;              \
-        case 7: fn<7>(rt, a); break;              \
-        case 8: fn<8>(rt, a); break;              \
-        case 9: fn<9>(rt, a); break;              \
-        case 10: fn<10>(rt, a); break;            \
-        case 11: fn<11>(rt, a); break;            \
-        case 12: fn<12>(rt, a); break;            \
-        case 13: fn<13>(rt, a); break;            \
-        case 14: fn<14>(rt, a); break;            \
-        case 15: fn<15>(rt, a); break;            \
-        case 20: fn<20>(rt, a); break;            \
-        case 24: fn<24>(rt, a); break;            \
-        case 28: fn<28>(rt, a); break;            \
-        case 32: fn<32>(rt, a); break;            \
-        default: fn<16>(rt, a); break;            \
-    }
-
-// The k_rt_flux instantiation this batch runs (rt_fused_f32.hip's flux_kernel / flux_method on fp64 planes): launched with
-// `f`, or -- f == nullptr -- its dynamic-LDS limit raised to the batch's demand, the outcome in rt->shmem_rc
-template <int ROWS, int K, bool MATRIX>
-void flux_kernel(hx_rt* rt, const FluxArgs* f) {
-    const size_t shmem = flux_shmem_bytes(rt);
-    if (!f) {
-        rt->shmem_rc = hipFuncSetAttribute((const void*)k_rt_flux<ROWS, K, MATRIX>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)shmem);
-        return;
-    }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rt_flux<ROWS, K, MATRIX>), dim3(rt->g.nblk_x, rt->C), dim3(rt->g.threads), shmem,
-                       rt->ctx->stream, *f);
-}
-
-template <int ROWS, bool MATRIX>
-void flux_method(hx_rt* rt, const FluxArgs* f) {
-    const int k = rt->g.k;
-    const bool generic = rt->generic_scans;
-    if constexpr (ROWS > 16) {   // (only on 64 lanes: choose_geometry)
-        (void)k; (void)generic;
-        flux_kernel<ROWS, 64, MATRIX>(rt, f);
-    } else {
-        if (k == 16 && !generic) flux_kernel<ROWS, 16, MATRIX>(rt, f);
-        else if (k == 32 && !generic) flux_kernel<ROWS, 32, MATRIX>(rt, f);
-        else if (k == 64 && !generic) flux_kernel<ROWS, 64, MATRIX>(rt, f);
-        else flux_kernel<ROWS, 0, MATRIX>(rt, f);
-    }
-}
-
-template <int ROWS>
-void flux_rows(hx_rt* rt, const FluxArgs* f) {
-    if (rt->matrix) flux_method<ROWS, true>(rt, f);
-    else flux_method<ROWS, false>(rt, f);
-}
-
 void launch_flux(hx_rt* rt, const KArgs& a) {
     const TileGeom& g = rt->g;
     FluxArgs f;
@@ -330,66 +264,29 @@ void launch_flux(hx_rt* rt, const KArgs& a) {
         f.reverse = 0;
         f.cache_state_from = INT_MAX;
     }
-    if (rt->coef32) {   // `precision = single`: the same kernel on fp32 planes (rt_fused_f32.hip)
-        launch_flux_f32(rt, f, dim3(g.nblk_x, rt->C), flux_shmem_bytes(rt));
-        return;
-    }
-    DISPATCH_ROWS(flux_rows, rt, &f);
+    // (`precision = single`: the same kernel on fp32 planes, rt_fused_f32.hip)
+    (void)(rt->coef32 ? select_flux_f32(rt, &f) : select_flux<double>(rt, &f));
 }
 
-template <int ROWS, int TPB>
-void launch_coef_tpb(hx_rt* rt, KArgs a) {
+void launch_coef(hx_rt* rt, KArgs a) {
     const TileGeom& g = rt->g;
-    const int ntiles = g.nblk_x * g.nparts * g.NW;
-    const int TS = TPB * g.S, TSP = TS;
-    const int NBX = g.nxb * ((TPB - 1) / (g.NW * g.nparts) + 2);
-    a.coef_nbx = NBX;
-    size_t shmem = ((size_t)(rt->L + rt->I) * TSP + (size_t)rt->H * (NBX + 2)) * sizeof(double) + 2 * TS * sizeof(int);
-    const size_t cloud_image = 3 * (size_t)rt->H * NBX * sizeof(double);
+    const int ntiles = g.nblk_x * g.nparts * g.NW, tpb = rt->coef_tpb;
+    a.coef_nbx = coef_nbx(rt, tpb);
+    size_t shmem = coef_shmem_bytes(rt, tpb);
+    const size_t cloud_image = 3 * (size_t)rt->H * a.coef_nbx * sizeof(double);
     a.cloud_lds = a.clouds == 1 && rt->cloud_lds && shmem + cloud_image <= 80 * 1024;  // keep two workgroups per CU
     if (a.cloud_lds) shmem += cloud_image;
-    if (rt->coef32) {   // `precision = single` (rt_fused_f32.hip)
-        launch_coef_f32(rt, a, TPB, dim3((ntiles + TPB - 1) / TPB, rt->C), shmem);
-        return;
-    }
-    if (shmem > 64 * 1024 && !rt->coef_shmem_raised) {
-        (void)hipFuncSetAttribute((const void*)k_rt_coef<ROWS, TPB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)shmem);
-        rt->coef_shmem_raised = true;
-    }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rt_coef<ROWS, TPB>), dim3((ntiles + TPB - 1) / TPB, rt->C), dim3(64 * TPB),
-                       shmem, rt->ctx->stream, a);
-}
-template <int ROWS>
-void launch_coef(hx_rt* rt, const KArgs& a) {
-    switch (rt->coef_tpb) {
-        case 1: launch_coef_tpb<ROWS, 1>(rt, a); break;
-        case 2: launch_coef_tpb<ROWS, 2>(rt, a); break;
-        case 8:
-            if constexpr (ROWS <= 16) { launch_coef_tpb<ROWS, 8>(rt, a); break; }   // (big columns: at most four tiles fit the LDS)
-            [[fallthrough]];
-        default: launch_coef_tpb<ROWS, 4>(rt, a); break;
-    }
-}
-
-// LDS demand of k_rt_coef with `tpb` tiles per workgroup (launch_coef_tpb's formula, without the optional cloud image)
-size_t coef_shmem_bytes(const hx_rt* rt, int tpb) {
-    const TileGeom& g = rt->g;
-    const int TS = tpb * g.S;
-    const int NBX = g.nxb * ((tpb - 1) / (g.NW * g.nparts) + 2);
-    return ((size_t)(rt->L + rt->I) * TS + (size_t)rt->H * (NBX + 2)) * sizeof(double) + 2 * TS * sizeof(int);
+    const dim3 grid((ntiles + tpb - 1) / tpb, rt->C);
+    if (rt->coef32) select_coef_f32(rt, a, grid, shmem);   // `precision = single` (rt_fused_f32.hip)
+    else select_coef<double>(rt, a, grid, shmem);
 }
 
 int set_flux_shmem_limits(hx_rt* rt) {
     const size_t shmem = flux_shmem_bytes(rt);
     if (shmem > 160 * 1024) return rt_fail(rt, HX_E_UNSUPPORTED, "workgroup LDS demand exceeds 160 KiB");
     if (shmem <= 64 * 1024) return 0;
-    if (rt->coef_bytes == 4) {   // (the batch's fp32 kernel: rt_create_into chose the width before this call)
-        HX_HIP(rt->ctx, raise_flux_shmem_f32(rt, (int)shmem));
-        return 0;
-    }
-    DISPATCH_ROWS(flux_rows, rt, nullptr);
-    HX_HIP(rt->ctx, rt->shmem_rc);
+    // (the batch's own kernel: rt_create_into chose the planes' width before this call)
+    HX_HIP(rt->ctx, rt->coef_bytes == 4 ? select_flux_f32(rt, nullptr) : select_flux<double>(rt, nullptr));
     return 0;
 }
 
@@ -451,7 +348,7 @@ static int rt_create_into(hx_rt* rt, hx_context* ctx, const hx_rt_dims* dims, co
         return hx_fail(ctx, HX_E_ARG, "HELIOS_RT_MATRIX=%s: the knob is retired (the matrix method has one solver); unset it", e);
     rt->matrix = flags->matrix != 0;
     rt->matrix_keep_state = rt->matrix && flags->debug == 1;   // count_negative_fluxes reads the up-flux tiles
-    if (!choose_geometry(rt->H, rt->Y, rt->X, rt->C, flags->dir_beam, flags->scat_corr, rt->g, rt->matrix ? 1 : 0))
+    if (!choose_geometry(rt->H, rt->Y, rt->X, rt->C, flags->dir_beam, flags->scat_corr, rt->g))
         return hx_fail(ctx, HX_E_UNSUPPORTED, "fused path supports nlayer <= 1024 (2048 isothermal layers); use the per-stage API");
     // bin chunks of the totals reduction: k_rt_totals_a wants many, _b few.  nbin/48 measured best at 10 000 bins;
     // a small grid keeps at least 32 chunks (of >= 8 bins) so that the first level still spreads over the chip
@@ -467,7 +364,7 @@ static int rt_create_into(hx_rt* rt, hx_context* ctx, const hx_rt_dims* dims, co
     // at k = 16, 8 at k = 32 (config 5, same box: 2 tiles 6.4 ms, 4 tiles 4.5 ms, 8 tiles 3.4 ms per refresh)
     rt->coef_tpb = std::max(1, std::min(8, 16 / std::max(1, rt->g.S)));    // (16 tiles per workgroup at k = 64: measured, no faster)
     if (const char* e = getenv("HELIOS_RT_COEF_TPB")) rt->coef_tpb = atoi(e);   // tuning knobs
-    // launch_coef has kernels of 1, 2, 4 and 8 tiles (8 up to 16 rows) and runs any other value as 4: the LDS limits below
+    // select_coef has kernels of 1, 2, 4 and 8 tiles (8 up to 16 rows) and runs any other value as 4: the LDS limits below
     // and "flux_tiling" are those of the kernel that runs
     if (rt->coef_tpb != 1 && rt->coef_tpb != 2 && !(rt->coef_tpb == 8 && rt->g.ROWS <= 16)) rt->coef_tpb = 4;
     while (rt->coef_tpb > 1 && coef_shmem_bytes(rt, rt->coef_tpb) > 150 * 1024) rt->coef_tpb /= 2;   // (deep columns: the staged layers of fewer tiles)
@@ -631,23 +528,29 @@ static int new_table_set(hx_rt* rt) {
     return rt->tables.size() == 1 ? upload_coltab(rt, 0, rt->C) : 0;
 }
 
+static int fill_outer(hx_rt* rt, double* table, const double* kxy, const double* ftp);
+
+// Table set `n` from the host, created first where n is one past the batch's last set.  The k-table is `opac_k`, or -- null --
+// the product of its two factors, formed on the device.  Set 0 is the one a batch needs before its first refresh.
+static int fill_table_set(hx_rt* rt, size_t n, const double* opac_k, const double* kxy, const double* ftp,
+                          const double* opac_scat_cross, const double* opac_meanmass) {
+    if (n == rt->tables.size())
+        if (const int rc = new_table_set(rt)) return rc;
+    const size_t ntp = (size_t)rt->d.ntemp * rt->d.npress;
+    const TableSet& t = rt->tables[n];
+    int rc = opac_k ? h2d(rt, (void*)t.k, opac_k, ntp * rt->X * rt->Y * 8) : fill_outer(rt, (double*)t.k, kxy, ftp);
+    rc |= h2d(rt, (void*)t.scat_cross, opac_scat_cross, ntp * rt->X * 8);
+    rc |= h2d(rt, (void*)t.meanmass, opac_meanmass, ntp * 8);
+    if (n == 0) rt->have_tables = rc == 0;
+    return rc;
+}
+
 int hx_rt_set_premixed_tables(hx_rt* rt, const double* opac_k, const double* opac_scat_cross,
                               const double* opac_meanmass) {
     if (!rt) return HX_E_ARG;  // e.g. a call after hx_rt_destroy
     rt_touch(rt);            // a captured iteration graph holds the arguments of before this call
     HX_REQUIRE(rt->ctx, rt->d.nspecies == 0, HX_E_STATE, "object was created for on-the-fly mixing");
-    const size_t ntp = (size_t)rt->d.ntemp * rt->d.npress;
-    if (rt->tables.empty()) {
-        int rc0 = new_table_set(rt);
-        if (rc0) return rc0;
-    }
-    const TableSet& t = rt->tables[0];
-    int rc = 0;
-    rc |= h2d(rt, (void*)t.k, opac_k, ntp * rt->X * rt->Y * 8);
-    rc |= h2d(rt, (void*)t.scat_cross, opac_scat_cross, ntp * rt->X * 8);
-    rc |= h2d(rt, (void*)t.meanmass, opac_meanmass, ntp * 8);
-    rt->have_tables = rc == 0;
-    return rc;
+    return fill_table_set(rt, 0, opac_k, nullptr, nullptr, opac_scat_cross, opac_meanmass);
 }
 
 int hx_rt_add_premixed_tables(hx_rt* rt, const double* opac_k, const double* opac_scat_cross, const double* opac_meanmass,
@@ -662,15 +565,8 @@ int hx_rt_add_premixed_tables(hx_rt* rt, const double* opac_k, const double* opa
                        "keeps its %d set(s)", ntab, ntab);
     HX_REQUIRE(rt->ctx, opac_k && opac_scat_cross && opac_meanmass && out_index, HX_E_ARG, "null table");
     rt_touch(rt);
-    int rc = new_table_set(rt);
-    if (rc) return rc;
-    const size_t ntp = (size_t)rt->d.ntemp * rt->d.npress;
-    const TableSet& t = rt->tables[ntab];
-    rc |= h2d(rt, (void*)t.k, opac_k, ntp * rt->X * rt->Y * 8);
-    rc |= h2d(rt, (void*)t.scat_cross, opac_scat_cross, ntp * rt->X * 8);
-    rc |= h2d(rt, (void*)t.meanmass, opac_meanmass, ntp * 8);
-    if (ntab == 0) rt->have_tables = rc == 0;
-    *out_index = ntab;
+    const int rc = fill_table_set(rt, ntab, opac_k, nullptr, nullptr, opac_scat_cross, opac_meanmass);
+    if ((int)rt->tables.size() > ntab) *out_index = ntab;
     return rc;
 }
 
@@ -763,20 +659,10 @@ int hx_rt_set_species_separable(hx_rt* rt, int s, const double* kxy, const doubl
 int hx_rt_set_premixed_separable(hx_rt* rt, const double* kxy, const double* ftp, const double* opac_scat_cross,
                                  const double* opac_meanmass) {
     if (!rt) return HX_E_ARG;
-    rt_touch(rt);         
+    rt_touch(rt);
     HX_REQUIRE(rt->ctx, rt->d.nspecies == 0, HX_E_STATE, "object was created for on-the-fly mixing");
     HX_REQUIRE(rt->ctx, kxy && ftp && opac_scat_cross && opac_meanmass, HX_E_ARG, "null table");
-    const size_t ntp = (size_t)rt->d.ntemp * rt->d.npress;
-    if (rt->tables.empty()) {
-        int rc0 = new_table_set(rt);
-        if (rc0) return rc0;
-    }
-    const TableSet& t = rt->tables[0];
-    int rc = fill_outer(rt, (double*)t.k, kxy, ftp);
-    if (!rc) rc = h2d(rt, (void*)t.scat_cross, opac_scat_cross, ntp * rt->X * 8);
-    if (!rc) rc = h2d(rt, (void*)t.meanmass, opac_meanmass, ntp * 8);
-    rt->have_tables = rc == 0;
-    return rc;
+    return fill_table_set(rt, 0, nullptr, kxy, ftp, opac_scat_cross, opac_meanmass);
 }
 
 // calculate_vmr_for_all_species on the device (host_functions.py:874-910): a species whose mixing ratio is tabulated on the
@@ -1043,6 +929,15 @@ static int refresh_species(hx_rt* rt) {
     return 0;
 }
 
+// interface temperatures and node Planck values of the CURRENT layer temperatures; moves the device's iteration counter on
+static int launch_nodes(hx_rt* rt, const KArgs& a) {
+    ProfScope ps(rt, "rt_nodes");
+    dim3 grid(hx_cdiv(rt->X, 32), hx_cdiv(rt->H + 3, 32), rt->C);
+    k_rt_nodes<<<grid, 256, 0, rt->ctx->stream>>>(a);
+    HX_LAUNCH_CHECK(rt->ctx);
+    return 0;
+}
+
 int hx_rt_refresh(hx_rt* rt) {
     if (!rt) return HX_E_ARG;  // e.g. a call after hx_rt_destroy
     RT_NEED_LOOP(rt);
@@ -1061,18 +956,12 @@ int hx_rt_refresh(hx_rt* rt) {
         if (Y != ro::NY && Y != 1 && any_ro)  // ny == 1 mixes correlated-k in the reference too (kernels.cu:3302)
             return hx_fail(ctx, HX_E_RO_NY, "random-overlap mixing needs ny == 20 or 1 (got %d)", Y);
         HX_REQUIRE(ctx, Y <= ro::NY, HX_E_UNSUPPORTED, "on-the-fly mixing in the fused path holds at most 20 Gauss points");
-        int nabs = 0;
-        for (const Species& sp : rt->species) nabs += sp.absorbing ? 1 : 0;
-        (void)nabs;   // (any number: the species loop takes them in blocks of MIX_MAX_ABSORBERS, refresh_species)
+        // (any number of absorbers: the species loop takes them in blocks of MIX_MAX_ABSORBERS, refresh_species)
     }
     KArgs a = make_args(rt);
     rt->iter_dev_expected = -1;   // k_rt_nodes below moves the device's iteration counter on (hx_rt_step sets it right again)
-    {   // interface temperatures (and node Planck values) of the CURRENT layer temperatures
-        ProfScope ps(rt, "rt_nodes");
-        dim3 grid(hx_cdiv(X, 32), hx_cdiv(rt->H + 3, 32), C);
-        k_rt_nodes<<<grid, 256, 0, ctx->stream>>>(a);
-        HX_LAUNCH_CHECK(ctx);
-    }
+    rc = launch_nodes(rt, a);
+    if (rc) return rc;
     ProfScope ps_all(rt, "refresh_total");
     // Every launch below covers all columns; a column whose loop has ended (done[c], set on the device) is skipped
     // inside the kernels and keeps the state of its last real refresh.  No host round trip.
@@ -1130,7 +1019,7 @@ int hx_rt_refresh(hx_rt* rt) {
         k_rt_half_bands<<<dim3(hx_cdiv(X, 32), hx_cdiv(rt->H, 32), C), 256, 0, ctx->stream>>>(a);
         HX_LAUNCH_CHECK(ctx);
         a.from_table = fused_lookup ? 1 : 0;
-        DISPATCH_ROWS(launch_coef, rt, a);
+        launch_coef(rt, a);
         HX_LAUNCH_CHECK(ctx);
     }
     rt->refreshed = true;
@@ -1158,33 +1047,35 @@ static int spectral_fluxes(hx_rt* rt, const KArgs& a) {
     return rt->f.debug == 1 ? count_negative_fluxes(rt) : 0;   // (debug = 1 keeps the solve's stores on: rt_create_into)
 }
 
+// The head of an iteration, radiative or convective: the nodes (unless the refresh of this iteration evaluated them), the
+// spectral fluxes and the first level of the wavelength sum.
+// (The two levels of the sum stay two launches: merged into one -- the workgroup that draws a column's last ticket
+// going on with the second level and the temperature step -- measured slower with device-scope fences and not bit-identical
+// without them, profiles/r06_ab_totals_merged.txt)
+static int iteration_head(hx_rt* rt, const KArgs& a, bool nodes_done) {
+    int rc = nodes_done ? 0 : launch_nodes(rt, a);
+    if (!rc) rc = spectral_fluxes(rt, a);
+    if (rc) return rc;
+    ProfScope ps(rt, "rt_totals_a");
+    k_rt_totals_a<<<dim3(rt->nchunk, rt->C), 256, 0, rt->ctx->stream>>>(a);
+    HX_LAUNCH_CHECK(rt->ctx);
+    return 0;
+}
+
+// any column of the batch with a physical time step: each column's own physical_tstep decides, as it does in rad_temp_step
+static bool any_time_stepped(const hx_rt* rt) {
+    return std::any_of(rt->cols.begin(), rt->cols.end(), [](const hx_rt_column& c) { return c.physical_tstep != 0; });
+}
+
 static int rt_step_kernels(hx_rt* rt, int itervalue, int step_temperature, bool nodes_done) {
     hx_context* ctx = rt->ctx;
     rt->solve_serial++;
     KArgs a = make_args(rt);
-    if (!nodes_done) {
-        ProfScope ps(rt, "rt_nodes");
-        dim3 grid(hx_cdiv(rt->X, 32), hx_cdiv(rt->H + 3, 32), rt->C);
-        k_rt_nodes<<<grid, 256, 0, ctx->stream>>>(a);
-        HX_LAUNCH_CHECK(ctx);
-    }
-    {
-        int rc = spectral_fluxes(rt, a);
-        if (rc) return rc;
-    }
-    // (the two levels of the wavelength sum stay two launches: merged into one -- the workgroup that draws a column's last ticket
-    // going on with the second level and the temperature step -- measured slower with device-scope fences and not bit-identical
-    // without them, profiles/r06_ab_totals_merged.txt)
-    {
-        ProfScope ps(rt, "rt_totals_a");
-        k_rt_totals_a<<<dim3(rt->nchunk, rt->C), 256, 0, ctx->stream>>>(a);
-        HX_LAUNCH_CHECK(ctx);
-    }
-    if (rt->entr_kappa && itervalue % 10 == 0) {   // computation.py:921-923, for the columns that are time-stepped: each column's
-        bool time_stepped = false;                 // own physical_tstep decides, as it does in rad_temp_step (graph_wanted likewise)
-        for (const auto& c : rt->cols) time_stepped = time_stepped || c.physical_tstep != 0;
+    int rc = iteration_head(rt, a, nodes_done);
+    if (rc) return rc;
+    if (rt->entr_kappa && itervalue % 10 == 0 && any_time_stepped(rt)) {   // computation.py:921-923, for the time-stepped columns
         // (reads temperatures and pressures, not the fluxes: before or behind the first level alike)
-        int rc = time_stepped ? kappa_cp_from_table(rt, false, true) : 0;
+        rc = kappa_cp_from_table(rt, false, true);
         if (rc) return rc;
     }
     {
@@ -1385,20 +1276,9 @@ int hx_rt_conv_advance(hx_rt* rt, int itervalue) {
     KArgs a = make_args(rt);
     rt->solve_serial++;
     rt->iter_dev_expected = -1;   // (the convection loop passes its own iteration index; k_rt_nodes still counts)
-    if (!nodes_done) {
-        ProfScope ps(rt, "rt_nodes");
-        dim3 grid(hx_cdiv(rt->X, 32), hx_cdiv(rt->H + 3, 32), rt->C);
-        k_rt_nodes<<<grid, 256, 0, ctx->stream>>>(a);
-        HX_LAUNCH_CHECK(ctx);
-    }
     {
-        int rc = spectral_fluxes(rt, a);
+        int rc = iteration_head(rt, a, nodes_done);
         if (rc) return rc;
-    }
-    {
-        ProfScope ps(rt, "rt_totals_a");
-        k_rt_totals_a<<<dim3(rt->nchunk, rt->C), 256, 0, ctx->stream>>>(a);
-        HX_LAUNCH_CHECK(ctx);
     }
     if (rt->entr_kappa) {   // computation.py:1088: once more for the adjusted profile, before the layers are marked
         int rc = kappa_cp_from_table(rt, false);
@@ -1458,10 +1338,8 @@ static bool graph_wanted(hx_rt* rt) {
     }
     // not while the event profiler brackets every launch, not with the per-iteration host decisions of the time-stepped
     // kappa refresh (computation.py:921-923)
-    bool time_stepped = false;   // any column of the batch
-    for (const auto& c : rt->cols) time_stepped = time_stepped || c.physical_tstep != 0;
     // (the matrix method's direct solve replays like the sweeps)
-    return rt->use_graph == 1 && !rt->profiling && !(rt->entr_kappa && time_stepped);
+    return rt->use_graph == 1 && !rt->profiling && !(rt->entr_kappa && any_time_stepped(rt));
 }
 
 // `with_refresh`: the whole decade -- the opacity refresh with the iteration that carries it, then the nine refresh-free
@@ -1544,12 +1422,6 @@ int hx_rt_converged_layers(hx_rt* rt, int* out_counts) {
 
 // ---- read-back in the reference's layouts ------------------------------------------------------
 namespace {
-
-int get_plain(hx_rt* rt, const void* dptr, size_t bytes, void* out, size_t out_bytes) {
-    if (bytes != out_bytes)
-        return hx_fail(rt->ctx, HX_E_ARG, "hx_rt_get: buffer is %zu bytes, array has %zu", out_bytes, bytes);
-    return hx_d2h(rt->ctx, out, dptr, bytes);
-}
 
 // internal band layout [x][i] -> reference [x + X*i]
 int get_band(hx_rt* rt, const double* dptr, void* out, size_t out_bytes) {
@@ -1635,131 +1507,117 @@ static int materialize_opac(hx_rt* rt) {
     return 0;
 }
 
+// ---- the batch's named arrays: one row per name that is one stretch of memory per column (or one for the batch), with the
+// calls that serve it.  hx_rt_get, hx_rt_set_state and hx_rt_device_ptr look a name up here; what is converted, gathered or
+// allocated on demand stays with them.  Built per call from the batch's dimensions: `host` holds the host-side values.
+namespace {
+
+struct HostValues {
+    int32_t coef_bytes, nchunk, ntables, nmie, tiling[14];
+    double policy[2], replays[3], builds[2];
+};
+
+extern "C++" std::vector<hx_column_array> rt_arrays(hx_rt* rt, HostValues& host) {
+    const size_t X = rt->X, Y = rt->Y, L = rt->L, I = rt->I, XI = X * I, wg = X * Y * I, S = std::max(rt->d.nspecies, 0);
+    const TileGeom& g = rt->g;
+    host = {rt->coef_bytes, rt->nchunk, (int32_t)rt->tables.size(), (int32_t)rt->mie.size(),
+            {g.k, g.ROWS, g.threads, g.nparts, g.nxb, g.ypb, g.NW, g.nplane, g.has_vp, g.pl_vp, g.pl_dd, rt->coef_tpb, rt->coef_bytes,
+             rt->generic_scans ? 1 : 0},
+            // {launch order back and forth (0/1), MiB of up-flux state kept cached}
+            {rt->serpentine ? 1.0 : 0.0, rt->serpentine ? rt->state_cache_mb : 0.0},
+            // {replays of the nine refresh-free iterations, replays of a whole decade, graphs in use (0/1)}
+            {(double)rt->iter_graph_replays, (double)rt->decade_graph_replays, rt->use_graph == 1 ? 1.0 : 0.0},
+            // {captures of the nine-iteration graph, captures of the decade graph}
+            {(double)rt->iter_graph_builds, (double)rt->decade_graph_builds}};
+    const unsigned G = HX_GET, GS = HX_GET | HX_SET, GP = HX_GET | HX_PTR, P = HX_PTR, ANY = HX_GET | HX_ANY_COL;
+    const char* no_clouds = rt->f.clouds == 1 ? nullptr : "object was created with clouds = 0";
+    const char* no_decks = rt->cloud_ndecks > 0 ? nullptr : "no cloud decks have been set (hx_rt_set_column_cloud_decks)";
+    const size_t deck = (size_t)rt->cloud_ndecks * 3 * X, grid = (size_t)(rt->d.plancktable_dim + 1) * X;
+    const void* planes = rt->coef32 ? (const void*)rt->coef32 : (const void*)rt->coef;
+    // (name, column 0, elements per column, elements served, calls[, why not yet]); `dev`: device memory, `here`: host memory
+    auto dev = [](const char* name, const auto* p, size_t stride, size_t count, unsigned serves, const char* not_ready = nullptr) {
+        return hx_column_array{name, p, stride, count, sizeof(*p), serves, true, not_ready};
+    };
+    auto here = [](const char* name, const auto* p, size_t stride, size_t count, unsigned serves) {
+        return hx_column_array{name, p, stride, count, sizeof(*p), serves, false, nullptr};
+    };
+    std::vector<hx_column_array> rows = {
+        // host-side, any column (-1): the planes' element width, the tiling and kernels this batch runs, the bin chunks of the
+        // wavelength totals, the table sets and Mie tables the batch holds
+        here("coef_plane_bytes", &host.coef_bytes, 0, 1, ANY), here("flux_tiling", host.tiling, 0, 14, ANY),
+        here("totals_chunks", &host.nchunk, 0, 1, ANY), here("premixed_table_count", &host.ntables, 0, 1, ANY),
+        here("mie_table_count", &host.nmie, 0, 1, ANY),
+        // host-side: the index of the column's table set; the launch policy and the graph counters
+        here("premixed_table", rt->col_table.data(), 1, 1, G), here("flux_launch_policy", host.policy, 0, 2, G),
+        here("graph_replays", host.replays, 0, 3, G), here("graph_builds", host.builds, 0, 2, G),
+        // the column's coefficient planes as k_rt_coef wrote them (after a refresh)
+        {"coef_planes", planes, g.coef_elems_per_col, g.coef_elems_per_col, (size_t)rt->coef_bytes, G, true, nullptr},
+        dev("T_lay", rt->T_lay, L + 1, L + 1, GS | P), dev("T_int", rt->T_int, I, I, GP),
+        dev("p_lay", rt->p_lay, L, L, P), dev("p_int", rt->p_int, I, I, P),
+        dev("delta_col_upper", rt->dcol_u, L, L, P), dev("delta_col_lower", rt->dcol_l, L, L, P),
+        dev("F_up_tot", rt->F_up_tot, I, I, GP), dev("F_down_tot", rt->F_down_tot, I, I, GP), dev("F_net", rt->F_net, I, I, GP),
+        dev("F_net_diff", rt->F_net_diff, L, L, G), dev("abort", rt->abort_flags, L + 1, L + 1, G),
+        dev("delta_t_prefactor", rt->prefactor, L + 1, L + 1, GS), dev("T_store", rt->T_store, L + 1, L + 1, GS),
+        dev("delta_z_lay", rt->delta_z, L, L, G), dev("z_lay", rt->z_lay, L, L, G),
+        // (the layer arrays of the refresh are strided like the interface ones)
+        dev("meanmolmass_lay", rt->mmm_lay, I, L, GP), dev("meanmolmass_int", rt->mmm_int, I, I, GP),
+        dev("opac_wg_lay", rt->opac_wg_lay, wg, X * Y * L, GP), dev("opac_wg_int", rt->opac_wg_int, wg, wg, GP),
+        dev("scat_cross_lay", rt->scat_cross_lay, XI, X * L, GP), dev("scat_cross_int", rt->scat_cross_int, XI, XI, GP),
+        // the cloud planes, whichever of hx_rt_set_column_clouds and hx_rt_set_column_cloud_decks filled them last
+        dev("abs_cross_all_clouds_lay", rt->cl_abs_lay, XI, X * L, GP), dev("abs_cross_all_clouds_int", rt->cl_abs_int, XI, XI, G),
+        dev("scat_cross_all_clouds_lay", rt->cl_sc_lay, XI, X * L, G), dev("scat_cross_all_clouds_int", rt->cl_sc_int, XI, XI, G),
+        dev("g_0_all_clouds_lay", rt->cl_g0_lay, XI, X * L, G, no_clouds), dev("g_0_all_clouds_int", rt->cl_g0_int, XI, XI, G, no_clouds),
+        // [ndecks][3][nbin] of the column's last hx_rt_set_column_cloud_decks
+        dev("cloud_deck_spectra", rt->cloud_spec, deck, deck, G, no_decks),
+        dev("g_0_tot_lay", rt->g0_tot_lay, XI, X * L, G), dev("g_0_tot_int", rt->g0_tot_int, XI, XI, G),
+        dev("iters_done", rt->iters_done, 1, 1, G), dev("done", rt->done, 1, 1, GS), dev("dampara", rt->dampara, 1, 1, HX_SET),
+        dev("conv_layer", rt->conv_layer, L + 1, L + 1, GS), dev("conv_unstable", rt->conv_unstable, L + 1, L + 1, GS),
+        dev("marked_red", rt->marked_red, L + 1, L + 1, G), dev("F_smooth_sum", rt->F_smooth_sum, L, L, G),
+        dev("kappa_lay", rt->kappa_lay, L, L, GS), dev("kappa_int", rt->kappa_int, I, I, GS), dev("c_p_lay", rt->c_p_lay, L, L, GS),
+        dev("F_add_heat_lay", rt->F_add_heat_lay, L, L, G), dev("F_add_heat_sum", rt->F_add_heat_sum, L, L, G),
+        // band fluxes in the internal layout [bin][interface] (hx_rt_get returns the reference's [interface][bin])
+        dev("F_up_band_n", rt->F_up_band_n, XI, XI, P), dev("F_down_band_n", rt->F_down_band_n, XI, XI, P),
+        // shared by all columns (hx_rt_set_state writes the Planck table by its own code: the stellar rows follow it)
+        dev("planck_grid", rt->planck_grid, 0, grid, GP), dev("gauss_weight", rt->gauss_w, 0, Y, P), dev("gauss_y", rt->gauss_y, 0, Y, P),
+        dev("opac_deltawave", rt->deltawave, 0, X, P), dev("opac_interwave", rt->interwave, 0, X + 1, P)};
+    if (S > 0) {   // mixing-ratio profiles as the last refresh used them, [nspecies][ninterface] (layer rows: the first nlayer entries)
+        rows.push_back(dev("vmr_lay", rt->vmr_lay, S * I, S * I, G));
+        rows.push_back(dev("vmr_int", rt->vmr_int, S * I, S * I, G));
+    }
+    if (rt->f.dir_beam) {   // (without the beam hx_rt_get answers zeros and there is no memory to point to)
+        rows.push_back(dev("F_dir_wg", rt->F_dir_wg, wg, wg, GP));
+        rows.push_back(dev("Fc_dir_wg", rt->Fc_dir_wg, wg, wg, GP));
+    }
+    return rows;
+}
+
+}  // namespace
+
 int hx_rt_get(hx_rt* rt, int col, const char* name, void* out, size_t out_bytes) {
     if (!rt) return HX_E_ARG;  // e.g. a call after hx_rt_destroy
-    if (strcmp(name, "coef_plane_bytes") == 0) {   // host-side, any column (-1): int32, 4 (fp32 planes) or 8
-        HX_REQUIRE(rt->ctx, out_bytes == sizeof(int32_t), HX_E_ARG, "coef_plane_bytes is one int32");
-        const int32_t v = rt->coef_bytes;
-        memcpy(out, &v, sizeof(v));
-        return 0;
-    }
-    if (strcmp(name, "flux_tiling") == 0) {   // host-side, any column (-1): the tiling and kernels this batch runs
-        const TileGeom& g = rt->g;
-        const int32_t v[14] = {g.k, g.ROWS, g.threads, g.nparts, g.nxb, g.ypb, g.NW, g.nplane, g.has_vp, g.pl_vp, g.pl_dd,
-                               rt->coef_tpb, rt->coef_bytes, rt->generic_scans ? 1 : 0};
-        HX_REQUIRE(rt->ctx, out_bytes == sizeof(v), HX_E_ARG, "flux_tiling is 14 int32");
-        memcpy(out, v, sizeof(v));
-        return 0;
-    }
-    if (strcmp(name, "totals_chunks") == 0) {   // host-side, any column (-1): int32, the bin chunks of the wavelength totals
-        HX_REQUIRE(rt->ctx, out_bytes == sizeof(int32_t), HX_E_ARG, "totals_chunks is one int32");
-        const int32_t v = rt->nchunk;
-        memcpy(out, &v, sizeof(v));
-        return 0;
-    }
-    if (strcmp(name, "premixed_table_count") == 0) {   // host-side, any column (-1): int32, the table sets the batch holds
-        HX_REQUIRE(rt->ctx, out_bytes == sizeof(int32_t), HX_E_ARG, "premixed_table_count is one int32");
-        const int32_t v = (int32_t)rt->tables.size();
-        memcpy(out, &v, sizeof(v));
-        return 0;
-    }
-    if (strcmp(name, "mie_table_count") == 0) {   // host-side, any column (-1): int32, the Mie tables the batch holds
-        HX_REQUIRE(rt->ctx, out_bytes == sizeof(int32_t), HX_E_ARG, "mie_table_count is one int32");
-        const int32_t v = (int32_t)rt->mie.size();
-        memcpy(out, &v, sizeof(v));
-        return 0;
-    }
-    HX_REQUIRE(rt->ctx, col >= 0 && col < rt->C, HX_E_ARG, "column index out of range");
-    if (strcmp(name, "premixed_table") == 0) {   // host-side: int32, the index of the column's table set
-        HX_REQUIRE(rt->ctx, out_bytes == sizeof(int32_t), HX_E_ARG, "premixed_table is one int32");
-        const int32_t v = rt->col_table[col];
-        memcpy(out, &v, sizeof(v));
-        return 0;
-    }
-    if (strcmp(name, "coef_planes") == 0) {   // the column's coefficient planes as k_rt_coef wrote them (after a refresh)
-        const void* planes = rt->coef32 ? (const void*)rt->coef32 : (const void*)rt->coef;
-        const size_t bytes = rt->g.coef_elems_per_col * rt->coef_bytes;
-        return get_plain(rt, (const char*)planes + (size_t)col * bytes, bytes, out, out_bytes);
-    }
+    HostValues host;
+    const std::vector<hx_column_array> rows = rt_arrays(rt, host);
+    const hx_column_array* r = hx_find_array(rows, name, HX_GET);
+    if (!r || !(r->serves & HX_ANY_COL)) HX_REQUIRE(rt->ctx, col >= 0 && col < rt->C, HX_E_ARG, "column index out of range");
     if (strncmp(name, "opac_wg_", 8) == 0) {
         int rc = materialize_opac(rt);
         if (rc) return rc;
     }
+    if (r) {
+        if (r->not_ready) return hx_fail(rt->ctx, HX_E_STATE, "hx_rt_get: %s", r->not_ready);
+        if (r->bytes() != out_bytes)
+            return hx_fail(rt->ctx, HX_E_ARG, "hx_rt_get: buffer is %zu bytes, array has %zu", out_bytes, r->bytes());
+        if (r->on_device) return hx_d2h(rt->ctx, out, r->at(col), out_bytes);
+        memcpy(out, r->at(col), out_bytes);
+        return 0;
+    }
+    // what is gathered or converted on the way: band fluxes and node Planck values into the reference's layouts, the spectral
+    // fluxes from their tiles
     const size_t X = rt->X, Y = rt->Y, L = rt->L, I = rt->I, nc = X * Y, c = col;
     const std::string n(name);
-    if (n == "T_lay") return get_plain(rt, rt->T_lay + c * (L + 1), (L + 1) * 8, out, out_bytes);
-    if (n == "T_int") return get_plain(rt, rt->T_int + c * I, I * 8, out, out_bytes);
     if (n == "F_up_band") return get_band(rt, rt->F_up_band_n + c * X * I, out, out_bytes);
     if (n == "F_down_band") return get_band(rt, rt->F_down_band_n + c * X * I, out, out_bytes);
     if (n == "F_dir_band") return get_band(rt, rt->F_dir_band_n + c * X * I, out, out_bytes);
-    if (n == "F_up_tot") return get_plain(rt, rt->F_up_tot + c * I, I * 8, out, out_bytes);
-    if (n == "F_down_tot") return get_plain(rt, rt->F_down_tot + c * I, I * 8, out, out_bytes);
-    if (n == "F_net") return get_plain(rt, rt->F_net + c * I, I * 8, out, out_bytes);
-    if (n == "F_net_diff") return get_plain(rt, rt->F_net_diff + c * L, L * 8, out, out_bytes);
-    if (n == "abort") return get_plain(rt, rt->abort_flags + c * (L + 1), (L + 1) * 4, out, out_bytes);
-    if (n == "delta_t_prefactor") return get_plain(rt, rt->prefactor + c * (L + 1), (L + 1) * 8, out, out_bytes);
-    if (n == "T_store") return get_plain(rt, rt->T_store + c * (L + 1), (L + 1) * 8, out, out_bytes);
-    if (n == "delta_z_lay") return get_plain(rt, rt->delta_z + c * L, L * 8, out, out_bytes);
-    if (n == "z_lay") return get_plain(rt, rt->z_lay + c * L, L * 8, out, out_bytes);
-    if (n == "meanmolmass_lay") return get_plain(rt, rt->mmm_lay + c * I, L * 8, out, out_bytes);
-    if (n == "meanmolmass_int") return get_plain(rt, rt->mmm_int + c * I, I * 8, out, out_bytes);
-    if (n == "opac_wg_lay") return get_plain(rt, rt->opac_wg_lay + c * nc * I, nc * L * 8, out, out_bytes);
-    if (n == "opac_wg_int") return get_plain(rt, rt->opac_wg_int + c * nc * I, nc * I * 8, out, out_bytes);
-    if (n == "scat_cross_lay") return get_plain(rt, rt->scat_cross_lay + c * X * I, X * L * 8, out, out_bytes);
-    if (n == "scat_cross_int") return get_plain(rt, rt->scat_cross_int + c * X * I, X * I * 8, out, out_bytes);
-    // the cloud planes, whichever of hx_rt_set_column_clouds and hx_rt_set_column_cloud_decks filled them last
-    if (n == "abs_cross_all_clouds_lay") return get_plain(rt, rt->cl_abs_lay + c * X * I, X * L * 8, out, out_bytes);
-    if (n == "abs_cross_all_clouds_int") return get_plain(rt, rt->cl_abs_int + c * X * I, X * I * 8, out, out_bytes);
-    if (n == "scat_cross_all_clouds_lay") return get_plain(rt, rt->cl_sc_lay + c * X * I, X * L * 8, out, out_bytes);
-    if (n == "scat_cross_all_clouds_int") return get_plain(rt, rt->cl_sc_int + c * X * I, X * I * 8, out, out_bytes);
-    if (n == "g_0_all_clouds_lay" || n == "g_0_all_clouds_int") {
-        HX_REQUIRE(rt->ctx, rt->f.clouds == 1, HX_E_STATE, "object was created with clouds = 0");
-        return n == "g_0_all_clouds_lay" ? get_plain(rt, rt->cl_g0_lay + c * X * I, X * L * 8, out, out_bytes)
-                                         : get_plain(rt, rt->cl_g0_int + c * X * I, X * I * 8, out, out_bytes);
-    }
-    if (n == "cloud_deck_spectra") {   // [ndecks][3][nbin] of the column's last hx_rt_set_column_cloud_decks
-        HX_REQUIRE(rt->ctx, rt->cloud_ndecks > 0, HX_E_STATE, "no cloud decks have been set (hx_rt_set_column_cloud_decks)");
-        const size_t per = (size_t)rt->cloud_ndecks * 3 * X;
-        return get_plain(rt, rt->cloud_spec + c * per, per * 8, out, out_bytes);
-    }
-    if (n == "g_0_tot_lay") return get_plain(rt, rt->g0_tot_lay + c * X * I, X * L * 8, out, out_bytes);
-    if (n == "g_0_tot_int") return get_plain(rt, rt->g0_tot_int + c * X * I, X * I * 8, out, out_bytes);
-    // mixing-ratio profiles as the last refresh used them, [nspecies][ninterface] (layer rows: the first nlayer entries)
-    if ((n == "vmr_lay" || n == "vmr_int") && rt->d.nspecies > 0) {
-        const size_t S = rt->d.nspecies;
-        return get_plain(rt, (n == "vmr_lay" ? rt->vmr_lay : rt->vmr_int) + c * S * I, S * I * 8, out, out_bytes);
-    }
-    if (n == "iters_done") return get_plain(rt, rt->iters_done + c, 4, out, out_bytes);
-    if (n == "flux_launch_policy") {   // host-side: {launch order back and forth (0/1), MiB of up-flux state kept cached}
-        HX_REQUIRE(rt->ctx, out_bytes == 2 * sizeof(double), HX_E_ARG, "flux_launch_policy is two doubles");
-        const double v[2] = {rt->serpentine ? 1.0 : 0.0, rt->serpentine ? rt->state_cache_mb : 0.0};
-        memcpy(out, v, sizeof(v));
-        return 0;
-    }
-    if (n == "graph_replays") {   // host-side: {replays of the nine refresh-free iterations, replays of a whole decade, graphs in use (0/1)}
-        HX_REQUIRE(rt->ctx, out_bytes == 3 * sizeof(double), HX_E_ARG, "graph_replays is three doubles");
-        const double v[3] = {(double)rt->iter_graph_replays, (double)rt->decade_graph_replays, rt->use_graph == 1 ? 1.0 : 0.0};
-        memcpy(out, v, sizeof(v));
-        return 0;
-    }
-    if (n == "graph_builds") {   // host-side: {captures of the nine-iteration graph, captures of the decade graph}
-        HX_REQUIRE(rt->ctx, out_bytes == 2 * sizeof(double), HX_E_ARG, "graph_builds is two doubles");
-        const double v[2] = {(double)rt->iter_graph_builds, (double)rt->decade_graph_builds};
-        memcpy(out, v, sizeof(v));
-        return 0;
-    }
-    if (n == "planck_grid")
-        return get_plain(rt, rt->planck_grid, (size_t)(rt->d.plancktable_dim + 1) * X * 8, out, out_bytes);
-    if (n == "done") return get_plain(rt, rt->done + c, 4, out, out_bytes);
-    if (n == "conv_layer") return get_plain(rt, rt->conv_layer + c * (L + 1), (L + 1) * 4, out, out_bytes);
-    if (n == "conv_unstable") return get_plain(rt, rt->conv_unstable + c * (L + 1), (L + 1) * 4, out, out_bytes);
-    if (n == "marked_red") return get_plain(rt, rt->marked_red + c * (L + 1), (L + 1) * 4, out, out_bytes);
-    if (n == "F_smooth_sum") return get_plain(rt, rt->F_smooth_sum + c * L, L * 8, out, out_bytes);
-    if (n == "kappa_lay") return get_plain(rt, rt->kappa_lay + c * L, L * 8, out, out_bytes);
-    if (n == "kappa_int") return get_plain(rt, rt->kappa_int + c * (L + 1), (L + 1) * 8, out, out_bytes);
-    if (n == "c_p_lay") return get_plain(rt, rt->c_p_lay + c * L, L * 8, out, out_bytes);
-    if (n == "F_add_heat_lay") return get_plain(rt, rt->F_add_heat_lay + c * L, L * 8, out, out_bytes);
-    if (n == "F_add_heat_sum") return get_plain(rt, rt->F_add_heat_sum + c * L, L * 8, out, out_bytes);
     if (n == "planckband_lay" || n == "planckband_int") {
         // from the node array Bn[x][H+3]: layers = odd nodes, then star, surface; interfaces = even
         const bool lay = n == "planckband_lay";
@@ -1823,14 +1681,10 @@ int hx_rt_get(hx_rt* rt, int col, const char* name, void* out, size_t out_bytes)
                 o[y + Y * x + nc * L] = (1.0 - rt->f.dir_beam) * cp.f_factor * (rs * rs) * HX_PI * bs[x];
         return 0;
     }
-    if (n == "F_dir_wg" || n == "Fc_dir_wg") {
-        if (!rt->f.dir_beam) {
-            if (out_bytes != nc * I * 8) return hx_fail(rt->ctx, HX_E_ARG, "hx_rt_get: wrong buffer size");
-            memset(out, 0, out_bytes);
-            return 0;
-        }
-        return get_plain(rt, (n == "F_dir_wg" ? rt->F_dir_wg : rt->Fc_dir_wg) + c * nc * I, nc * I * 8, out,
-                         out_bytes);
+    if ((n == "F_dir_wg" || n == "Fc_dir_wg") && !rt->f.dir_beam) {
+        if (out_bytes != nc * I * 8) return hx_fail(rt->ctx, HX_E_ARG, "hx_rt_get: wrong buffer size");
+        memset(out, 0, out_bytes);
+        return 0;
     }
     return hx_fail(rt->ctx, HX_E_ARG, "hx_rt_get: unknown array name '%s'", name);
 }
@@ -1875,78 +1729,35 @@ int hx_rt_set_state(hx_rt* rt, int col, const char* name, const void* in, size_t
     }
     int c0, c1, rc = for_cols(rt, col, &c0, &c1);
     if (rc) return rc;
-    const size_t L = rt->L;
-    for (int c = c0; c < c1; c++) {
-        if (n == "T_lay") {
-            if (in_bytes != (L + 1) * 8) return hx_fail(rt->ctx, HX_E_ARG, "wrong size for T_lay");
-            rc |= h2d(rt, rt->T_lay + c * (L + 1), in, in_bytes);
-        } else if (n == "c_p_lay") {
-            if (in_bytes != L * 8) return hx_fail(rt->ctx, HX_E_ARG, "wrong size for c_p_lay");
-            rc |= h2d(rt, rt->c_p_lay + c * L, in, in_bytes);
-        } else if (n == "delta_t_prefactor" || n == "T_store") {
-            if (in_bytes != (L + 1) * 8) return hx_fail(rt->ctx, HX_E_ARG, "wrong size");
-            rc |= h2d(rt, (n == "T_store" ? rt->T_store : rt->prefactor) + c * (L + 1), in, in_bytes);
-        } else if (n == "done") {
-            if (in_bytes != 4) return hx_fail(rt->ctx, HX_E_ARG, "done expects one int32");
-            rc |= h2d(rt, rt->done + c, in, 4);
-        } else if (n == "kappa_lay") {
-            if (in_bytes != L * 8) return hx_fail(rt->ctx, HX_E_ARG, "wrong size for kappa_lay");
-            rc |= h2d(rt, rt->kappa_lay + c * L, in, in_bytes);
-        } else if (n == "kappa_int") {
-            if (in_bytes != (L + 1) * 8) return hx_fail(rt->ctx, HX_E_ARG, "wrong size for kappa_int");
-            rc |= h2d(rt, rt->kappa_int + c * (L + 1), in, in_bytes);
-        } else if (n == "conv_layer" || n == "conv_unstable") {
-            if (in_bytes != (L + 1) * 4) return hx_fail(rt->ctx, HX_E_ARG, "wrong size for %s", name);
-            rc |= h2d(rt, (n == "conv_layer" ? rt->conv_layer : rt->conv_unstable) + c * (L + 1), in, in_bytes);
-        } else if (n == "add_heat_dens") {
-            if (in_bytes != L * 8) return hx_fail(rt->ctx, HX_E_ARG, "wrong size for add_heat_dens");
-            if (!rt->add_heat_dens) RT_ALLOC(rt->add_heat_dens, (size_t)rt->C * L);
-            rc |= h2d(rt, rt->add_heat_dens + c * L, in, in_bytes);
-            rt->has_heating = true;
-        } else if (n == "dampara") {
-            if (in_bytes != 8) return hx_fail(rt->ctx, HX_E_ARG, "dampara expects one double (<= 0: automatic)");
-            rc |= h2d(rt, rt->dampara + c, in, 8);
-        } else {
-            return hx_fail(rt->ctx, HX_E_ARG, "hx_rt_set_state: unknown name '%s'", name);
-        }
+    if (n == "add_heat_dens") {   // allocated with its first values; from then on every refresh turns it into heating fluxes
+        const size_t L = rt->L;
+        if (in_bytes != L * 8) return hx_fail(rt->ctx, HX_E_ARG, "wrong size for add_heat_dens");
+        if (!rt->add_heat_dens) RT_ALLOC(rt->add_heat_dens, (size_t)rt->C * L);
+        for (int c = c0; c < c1; c++) rc |= h2d(rt, rt->add_heat_dens + c * L, in, in_bytes);
+        rt->has_heating = true;
+        return rc;
     }
+    HostValues host;
+    const std::vector<hx_column_array> rows = rt_arrays(rt, host);
+    const hx_column_array* r = hx_find_array(rows, name, HX_SET);
+    if (!r) return hx_fail(rt->ctx, HX_E_ARG, "hx_rt_set_state: unknown name '%s'", name);
+    if (in_bytes != r->bytes()) return hx_fail(rt->ctx, HX_E_ARG, "wrong size for %s: %zu bytes, the array has %zu", name, in_bytes, r->bytes());
+    for (int c = c0; c < c1; c++) rc |= h2d(rt, r->at(c), in, in_bytes);
     return rc;
 }
 
 int hx_rt_device_ptr(hx_rt* rt, int col, const char* name, void** out_dptr) {
     if (!rt) return HX_E_ARG;  // e.g. a call after hx_rt_destroy
     HX_REQUIRE(rt->ctx, col >= 0 && col < rt->C && out_dptr, HX_E_ARG, "bad arguments");
-    const size_t X = rt->X, Y = rt->Y, L = rt->L, I = rt->I, nc = X * Y, c = col;
-    const std::string n(name);
-    void* p = nullptr;
-    if (n == "T_lay") p = rt->T_lay + c * (L + 1);
-    else if (n == "T_int") p = rt->T_int + c * I;
-    else if (n == "p_lay") p = rt->p_lay + c * L;
-    else if (n == "p_int") p = rt->p_int + c * I;
-    else if (n == "opac_wg_lay") { int rc = materialize_opac(rt); if (rc) return rc; p = rt->opac_wg_lay + c * nc * I; }
-    else if (n == "opac_wg_int") { int rc = materialize_opac(rt); if (rc) return rc; p = rt->opac_wg_int + c * nc * I; }
-    else if (n == "F_dir_wg" && rt->f.dir_beam) p = rt->F_dir_wg + c * nc * I;
-    else if (n == "Fc_dir_wg" && rt->f.dir_beam) p = rt->Fc_dir_wg + c * nc * I;
-    else if (n == "scat_cross_lay") p = rt->scat_cross_lay + c * X * I;
-    else if (n == "scat_cross_int") p = rt->scat_cross_int + c * X * I;
-    else if (n == "meanmolmass_lay") p = rt->mmm_lay + c * I;
-    else if (n == "meanmolmass_int") p = rt->mmm_int + c * I;
-    else if (n == "planck_grid") p = rt->planck_grid;
-    // band fluxes in the internal layout [bin][interface] (hx_rt_get returns the reference's [interface][bin])
-    else if (n == "F_up_band_n") p = rt->F_up_band_n + c * X * I;
-    else if (n == "F_down_band_n") p = rt->F_down_band_n + c * X * I;
-    else if (n == "F_net") p = rt->F_net + c * I;
-    else if (n == "F_up_tot") p = rt->F_up_tot + c * I;
-    else if (n == "F_down_tot") p = rt->F_down_tot + c * I;
-    else if (n == "gauss_weight") p = rt->gauss_w;
-    else if (n == "gauss_y") p = rt->gauss_y;
-    else if (n == "opac_deltawave") p = rt->deltawave;
-    else if (n == "opac_interwave") p = rt->interwave;
-    else if (n == "abs_cross_all_clouds_lay") p = rt->cl_abs_lay + c * X * I;
-    else if (n == "delta_col_upper") p = rt->dcol_u + c * L;
-    else if (n == "delta_col_lower") p = rt->dcol_l + c * L;
-    else return hx_fail(rt->ctx, HX_E_ARG, "hx_rt_device_ptr: unknown name '%s'", name);
-    *out_dptr = p;
+    HostValues host;
+    const std::vector<hx_column_array> rows = rt_arrays(rt, host);
+    const hx_column_array* r = hx_find_array(rows, name, HX_PTR);
+    if (!r) return hx_fail(rt->ctx, HX_E_ARG, "hx_rt_device_ptr: unknown name '%s'", name);
+    if (strncmp(name, "opac_wg_", 8) == 0) {
+        int rc = materialize_opac(rt);
+        if (rc) return rc;
+    }
+    *out_dptr = r->at(col);
     return 0;
 }
 

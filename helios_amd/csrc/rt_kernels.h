@@ -1,4 +1,4 @@
-// Device kernels of the fused fast path.  Included by rt_fused.hip only.
+// Device kernels of the fused fast path.  Included through rt_select.h by rt_fused.hip and rt_fused_f32.hip.
 //
 // Unknowns of one spectral point (x,y) live on NODES n = 0..H (H = 2*nlayer): node 2i = interface i,
 // node 2i+1 = centre of layer i.  Half-layer h spans node h (bottom) .. h+1 (top).  With
@@ -1055,12 +1055,4 @@ __global__ void __launch_bounds__(256) k_rt_tile_rows(const double* __restrict__
 
 #endif  // HX_PLANE_KERNELS_ONLY
 
-// ---- fp32 coefficient planes (`precision = single`, hx_rt_flags.coef_fp32): rt_fused_f32.hip -----------------------------
-// The tilings with an fp32 instantiation: every tiling choose_geometry selects without scratch (columns of up to 416
-// layers, isothermal ones up to 512).  Other tilings run on fp64 planes.
-bool coef_fp32_tiling(int rows, int k, bool generic_scans);
-// the launches of launch_coef_tpb / launch_flux on rt->coef32 (ROWS, k and the method are the batch's: rt->g, rt->matrix)
-void launch_coef_f32(hx_rt* rt, const KArgs& a, int tpb, dim3 grid, size_t shmem);
-void launch_flux_f32(hx_rt* rt, const FluxArgs& f, dim3 grid, size_t shmem);
-hipError_t raise_flux_shmem_f32(hx_rt* rt, int shmem);
 }  // namespace hx

@@ -279,12 +279,14 @@ class RTBatch(object):
         }
         return table[name]
 
-    def get(self, name, col=0):
-        n, dt = self._shape(name)
-        out = np.zeros(n, dt)
+    def _get(self, name, col, n, dtype):
+        out = np.zeros(n, dtype)
         self._ck(self._l.hx_rt_get(self.handle, int(col), name.encode(), out.ctypes.data_as(ctypes.c_void_p),
                                    out.nbytes), "hx_rt_get(%s)" % name)
         return out
+
+    def get(self, name, col=0):
+        return self._get(name, col, *self._shape(name))
 
     def device_ptr(self, name, col=0):
         p = ctypes.c_void_p()
@@ -310,27 +312,18 @@ class RTBatch(object):
     def coef_plane_bytes(self):
         """bytes per coefficient-plane element the batch uses: 4 with `precision = single` where its tiling has fp32
         planes, else 8"""
-        out = np.zeros(1, np.int32)
-        self._ck(self._l.hx_rt_get(self.handle, -1, b"coef_plane_bytes", out.ctypes.data_as(ctypes.c_void_p), out.nbytes),
-                 "hx_rt_get(coef_plane_bytes)")
-        return int(out[0])
+        return int(self._get("coef_plane_bytes", -1, 1, np.int32)[0])
 
     def totals_chunks(self):
         """the number of bin chunks the wavelength totals are summed in (k_rt_totals_a's grid)"""
-        out = np.zeros(1, np.int32)
-        self._ck(self._l.hx_rt_get(self.handle, -1, b"totals_chunks", out.ctypes.data_as(ctypes.c_void_p), out.nbytes),
-                 "hx_rt_get(totals_chunks)")
-        return int(out[0])
+        return int(self._get("totals_chunks", -1, 1, np.int32)[0])
 
     _TILING = ("k", "ROWS", "threads", "nparts", "nxb", "ypb", "NW", "nplane", "has_vp", "pl_vp", "pl_dd", "coef_tpb",
                "coef_bytes", "generic_scans")
 
     def flux_tiling(self):
         """the batch's tiling and the coefficient kernel it runs (include/helios_hip.h, hx_rt_flags.coef_fp32)"""
-        out = np.zeros(len(self._TILING), np.int32)
-        self._ck(self._l.hx_rt_get(self.handle, -1, b"flux_tiling", out.ctypes.data_as(ctypes.c_void_p), out.nbytes),
-                 "hx_rt_get(flux_tiling)")
-        return dict(zip(self._TILING, (int(v) for v in out)))
+        return dict(zip(self._TILING, (int(v) for v in self._get("flux_tiling", -1, len(self._TILING), np.int32))))
 
     def coef_planes(self, col=0):
         """column `col`'s coefficient planes as the coefficient kernel wrote them at the last refresh, shaped
@@ -339,10 +332,7 @@ class RTBatch(object):
         dt = np.float32 if t["coef_bytes"] == 4 else np.float64
         per_tile = t["nplane"] * t["ROWS"] * 64
         ntiles = -(-self.nbin // t["nxb"]) * t["nparts"] * t["NW"]
-        out = np.zeros(ntiles * per_tile, dt)
-        self._ck(self._l.hx_rt_get(self.handle, int(col), b"coef_planes", out.ctypes.data_as(ctypes.c_void_p), out.nbytes),
-                 "hx_rt_get(coef_planes)")
-        return out.reshape(ntiles, t["nplane"], t["ROWS"], 64)
+        return self._get("coef_planes", col, ntiles * per_tile, dt).reshape(ntiles, t["nplane"], t["ROWS"], 64)
 
     def close(self):
         if self.handle:
