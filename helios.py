@@ -58,6 +58,8 @@ def run_helios(argv=None):
     computer.convection_loop(keeper, writer, reader, None)
 
     computer.integrate_optdepth_transmission(keeper)
+    if keeper.transit_depth_spectrum == 1:
+        computer.calculate_transit_depth(keeper)
     computer.calculate_contribution_function(keeper)
     if keeper.convection == 1:
         computer.interpolate_entropy(keeper)

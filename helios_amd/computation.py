@@ -334,6 +334,69 @@ class Compute(object):
                        q.dev_delta_tau_all_clouds_upper.d, q.dev_delta_tau_all_clouds_lower.d, _i(q.nbin),
                        _i(q.nlayer), _i(q.ny))
 
+    @staticmethod
+    def transit_shell_boundaries(quant, z_lay=None, delta_z_lay=None):
+        """ascending boundaries zb[0 .. S] of the transit shells of a column, fp64: the interfaces built upward from the
+        lowest one, interleaved with the layer centres unless the layers are isothermal (shell 2i = lower half of layer i,
+        shell 2i + 1 = its upper half).  A column whose boundaries do not ascend strictly is refused.  The altitudes are
+        the Store's host arrays unless given."""
+        L = _i(quant.nlayer)
+        z_lay = np.asarray(quant.z_lay if z_lay is None else z_lay, np.float64)[:L]
+        dz = np.asarray(quant.delta_z_lay if delta_z_lay is None else delta_z_lay, np.float64)[:L]
+        z_int = np.empty(L + 1)
+        z_int[0] = z_lay[0] - dz[0] / 2.0
+        for i in range(L):
+            z_int[i + 1] = z_int[i] + dz[i]
+        if quant.iso == 1:
+            zb = z_int
+        else:
+            zb = np.empty(2 * L + 1)
+            zb[0::2] = z_int
+            zb[1::2] = z_lay
+        bad = np.nonzero(~(np.diff(zb) > 0))[0]          # (a NaN does not ascend either)
+        if len(bad):
+            s = int(bad[0])
+            layer = s if quant.iso == 1 else s // 2
+            raise ValueError("transit depth: the shell boundaries do not ascend strictly at layer %d (z = %r -> %r cm); "
+                             "the column is refused" % (layer, float(zb[s]), float(zb[s + 1])))
+        return zb
+
+    def calculate_transit_depth(self, quant):
+        """transit radius, transit depth and the deepest chord's transmission per bin, from the optical depths and the
+        altitudes on the device, the ones the run itself used (hx_transit_depth; README, "Transit depth spectrum").  Fills
+        quant.transit_radius, transit_depth, transit_floor_transmission, and transit_area and transit_zb for whoever
+        checks them; no other host array of the Store is touched."""
+        q = quant
+        ctx = self._ctx_of(q)
+        X, Y = _i(q.nbin), _i(q.ny)
+        zb = self.transit_shell_boundaries(q, q.dev_z_lay.get(), q.dev_delta_z_lay.get())
+        S = len(zb) - 1
+        R0 = _f(q.R_planet)
+        work = ctx.empty(int(self._l.hx_transit_work_doubles(S, X)))
+        dev_zb = ctx.to_gpu(zb)
+        dev_A, dev_floor = ctx.empty(X), ctx.empty(X)
+        null = ctypes.POINTER(ctypes.c_double)()
+        if q.iso == 1:
+            halves = (q.dev_delta_tau_wg.d, null, q.dev_delta_tau_all_clouds.d, null)
+        else:
+            halves = (q.dev_delta_tau_wg_lower.d, q.dev_delta_tau_wg_upper.d, q.dev_delta_tau_all_clouds_lower.d,
+                      q.dev_delta_tau_all_clouds_upper.d)
+        self._call("hx_transit_depth", *halves, dev_zb.d, q.dev_gauss_weight.d, R0, X, Y, S, work.d, dev_A.d,
+                   dev_floor.d, null)
+        A = dev_A.get()
+        q.transit_floor_transmission = dev_floor.get()
+        q.transit_area = A
+        q.transit_radius = np.sqrt((R0 + zb[0]) * (R0 + zb[0]) + A)
+        ratio = q.transit_radius / _f(q.R_star)
+        q.transit_depth = ratio * ratio
+        q.transit_zb = zb
+        for d in (work, dev_zb, dev_A, dev_floor):
+            d.free()
+        worst = float(np.max(q.transit_floor_transmission))
+        if worst > 1e-3:
+            print("\nWARNING: the deepest transit chord transmits up to %.3g of the star light in a bin: the bottom of the "
+                  "model is not opaque there, and the transit radius of such a bin is a lower limit." % worst)
+
     def calculate_contribution_function(self, quant):
         q = quant
         if q.iso == 1:

@@ -68,6 +68,13 @@ class Store(object):
             setattr(self, n, [])
             setattr(self, "dev_" + n, None)
         self.abort = None
+        # the column seen in transit, per bin (Compute.calculate_transit_depth; None unless `transit depth spectrum = yes`)
+        self.transit_depth_spectrum = np.int32(0)
+        self.transit_radius = None
+        self.transit_depth = None
+        self.transit_floor_transmission = None
+        self.transit_area = None          # A_x [cm^2]: the occulting area above the lowest boundary, divided by pi
+        self.transit_zb = None            # the ascending shell boundaries the spectrum was integrated on [cm]
         self.rt = None          # helios_amd.rt.RTBatch of the fused path, created by Compute
 
     # ---------------------------------------------------------------------------------------------

@@ -108,6 +108,8 @@ _OPTIONS = [
     ("yes --> heating file format", "add_heating_file_format", None, "1 Pressure cgs Heating 1e7"),
     # extensions for synthetic inputs (not in the reference)
     ("synthetic --> bins layers-are-set-above ntemp npress seed", "synthetic_spec", "synthetic", "300 30 20 20241"),
+    # the same column seen in transit (not in the reference; README, "Transit depth spectrum")
+    ("transit depth spectrum", "transit_depth_spectrum", "transit_depth_spectrum", "no"),
 ]
 
 
@@ -353,6 +355,7 @@ class Read(object):
         quant.coupl_tp_write_interval = 0 if val["write_tp_during_run"] == "no" else int(val["write_tp_during_run"])
         quant.realtime_plot = i32(0)
         self.synthetic_spec = val["synthetic_spec"]
+        quant.transit_depth_spectrum = _yes_no(val["transit_depth_spectrum"])
 
         # ---- derived settings (read.py:884-985) ----
         # `single` stores the device-resident loop's coefficient planes in fp32 (hx_rt_flags.coef_fp32); every other

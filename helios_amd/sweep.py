@@ -328,6 +328,8 @@ def _finish_column(computer, q, reader, writer):
         q.dev_conv_layer.set(np.asarray(q.conv_layer, np.int32))
     q.dev_F_smooth_sum.set(q.rt.get("F_smooth_sum", q.rt_col))
     computer.integrate_optdepth_transmission(q)
+    if q.transit_depth_spectrum == 1:
+        computer.calculate_transit_depth(q)
     computer.calculate_contribution_function(q)
     if q.convection == 1:
         computer.interpolate_entropy(q)

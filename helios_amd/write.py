@@ -427,6 +427,25 @@ class Write(object):
                 else:
                     f.write("{:<12}\n".format("not_avail."))
 
+    @staticmethod
+    def write_transit_depth(quant, read):
+        """only with `transit depth spectrum = yes`: the column seen in transit (README, "Transit depth spectrum").  The
+        three result columns carry 17 significant digits: they are compared, not only plotted."""
+        if getattr(quant, "transit_depth_spectrum", 0) != 1 or quant.transit_depth is None:
+            return
+        worst = float(np.max(quant.transit_floor_transmission))
+        with open(Write._path(quant, read, "_transit_depth.dat"), "w") as f:
+            f.write("This file contains the transit radius [cm] and the transit depth (= (R_transit / R_star)^2) per wavelength, "
+                    "and the band transmission of the deepest chord."
+                    "\nLargest transmission of the deepest chord: {:g} (well above 0: the model's bottom is not opaque "
+                    "in that bin).".format(worst))
+            f.write("\n{:<8}{:<18}{:<26}{:<26}{:<26}".format(
+                "bin", "cent_lambda[um]", "transit_radius[cm]", "transit_depth", "floor_transmission"))
+            for x in range(int(quant.nbin)):
+                f.write("\n{:<8g}{:<18.9g}{:<26.17g}{:<26.17g}{:<26.17g}".format(
+                    x, quant.opac_wave[x] * 1e4, quant.transit_radius[x], quant.transit_depth[x],
+                    quant.transit_floor_transmission[x]))
+
     # ---- photochemical-kinetics coupling: the T-P profile handed to the chemistry code (write.py:717-771) ---------
     @staticmethod
     def _coupling_tp_path(quant, read, step, previous=False):
@@ -470,5 +489,5 @@ class Write(object):
                   Write.write_transmission, Write.write_opt_depth, Write.write_cloud_opt_depth,
                   Write.write_trans_weight_function, Write.write_contribution_function,
                   self.write_mean_extinction, Write.write_flux_ratio_only, Write.write_phase_state,
-                  Write.write_surface_albedo, Write.write_criterion_warning_file):
+                  Write.write_surface_albedo, Write.write_criterion_warning_file, Write.write_transit_depth):
             w(quant, read)

@@ -302,6 +302,23 @@ int hx_calc_h2o_scat(hx_context* ctx, const double* temp, const double* press, c
 /* add_to_mixed_scat, kernels.cu:3444 / computation.py:1425 */
 int hx_add_to_mixed_scat(hx_context* ctx, const double* vmr, const double* scat_cross_spec,
                          double* scat_cross, int nbin, int nlay_or_nint);
+/* Transit depth spectrum of a column (csrc/stage_transit.hip; not in the reference -- the contract is README, "Transit depth
+ * spectrum").  nshell homogeneous spherical shells with the ascending boundaries zb[0 .. nshell] (altitudes, z = 0 at radius R0);
+ * one chord per shell, through its centre.
+ *   isothermal layers:  nshell = nlayer, shell i = layer i; delta_tau_wg[c + ny*nbin*i] (c = y + ny*x), delta_tau_clouds[x + nbin*i],
+ *                       the two `_upper` pointers null
+ *   otherwise:          nshell = 2 nlayer, shell 2i = the lower half of layer i (delta_tau_wg, delta_tau_clouds: the `_lower`
+ *                       arrays of the run), shell 2i + 1 = its upper half (the `_upper` arrays); same layouts
+ * Out: A[nbin] the occulting area above zb[0] divided by pi, T_floor[nbin] the band transmission of the deepest chord and,
+ * unless null, T_band[x + nbin*j] that of every chord j.  `work` holds hx_transit_work_doubles(nshell, nbin) doubles (path
+ * lengths, thicknesses, T_band when it is not asked for).  A thread carries hx_transit_chord_block() chords in registers.
+ * Any number of shells (up to 2^31 - 1 workgroups); 1 <= ny <= 256.  All pointers are device pointers. */
+int hx_transit_chord_block(void);
+int64_t hx_transit_work_doubles(int nshell, int nbin);
+int hx_transit_depth(hx_context* ctx, const double* delta_tau_wg, const double* delta_tau_wg_upper,
+                     const double* delta_tau_clouds, const double* delta_tau_clouds_upper, const double* zb,
+                     const double* gauss_weight, double R0, int nbin, int ny, int nshell, double* work, double* A,
+                     double* T_floor, double* T_band);
 
 /* ---- (4) fused fast path --------------------------------------------------------------------
  * One hx_rt object = one batch of `ncol` independent atmosphere columns (planets / T-P profiles of
