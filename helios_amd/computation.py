@@ -283,7 +283,7 @@ class Compute(object):
         ro_method = 0 if (quant.kcoeff_mixing == "correlated-k" or "CIA" in quant.species_list[s].name) else 1
         for vmr, spec, mix, mmm, n in self._levels(quant, "dev_vmr_spec_{}", "dev_opac_spec_wg_{}",
                                                    "dev_opac_wg_{}", "dev_meanmolmass_{}"):
-            self._call("hx_add_to_mixed_opac", vmr.d, spec.d, mix.d, mmm.d, quant.dev_gauss_weight.d,
+            self._call("hx_add_to_mixed_opac_ny", vmr.d, spec.d, mix.d, mmm.d, quant.dev_gauss_weight.d,
                        quant.dev_gauss_y.d, mass, int(s), ro_method, _i(quant.ny), _i(quant.nbin), n)
 
     def calculate_H2O_Rayleigh_scattering(self, quant, s):

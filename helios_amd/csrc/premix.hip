@@ -378,7 +378,7 @@ int hx_premix_run(hx_premix* pm, int cell_error) {
         }
     }
     HX_REQUIRE(ctx, !abs.empty() && abs[0] == 0, HX_E_ARG, "the first species must absorb (it starts the mix)");
-    if (any_ro && Y != ro::NY) return hx_fail(ctx, HX_E_RO_NY, "random-overlap mixing needs ny == 20 or 1 (got %d)", Y);
+    if (any_ro && Y > ro::NY) return hx_fail(ctx, HX_E_RO_NY, "random-overlap mixing needs ny == 20 or 1 (got %d)", Y);
 
     // slabs: R cell rows = R + 1 rows of nodes, next to R rows of cell centres when the error map is asked for
     const size_t row_bytes = (size_t)NP * nc * 8, cen_row_bytes = cell_error ? (size_t)(NP - 1) * nc * 8 : 0;
@@ -478,7 +478,7 @@ int hx_premix_run(hx_premix* pm, int cell_error) {
         m.opac_wg_lay = out; m.opac_wg_int = out;
         m.done = d_done; m.diag = ctx->diag;
         Timer tm(ctx, t_mix);
-        return launch_mix_species(ctx, m, d_abs, (int)abs.size());
+        return launch_mix_species(ctx, m, d_abs, (int)abs.size(), any_ro);
     };
 
     for (int r0 = 0; r0 < NT - 1; r0 += R) {

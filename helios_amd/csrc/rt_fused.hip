@@ -874,9 +874,12 @@ static int upload_species_table(hx_rt* rt) {
 }
 
 // the species loop of a batch, a refresh or a premix (csrc/premix.hip): one launch per block of MIX_MAX_ABSORBERS absorbers
-extern "C++" int hx::launch_mix_species(hx_context* ctx, MixArgs m, const int* abs_list, int nabs_all) {
+extern "C++" int hx::launch_mix_species(hx_context* ctx, MixArgs m, const int* abs_list, int nabs_all, bool any_ro) {
     const long long npair = (long long)m.C * (m.L + m.I) * m.X;
     if (npair <= 0) return 0;
+    // random overlap at another number of Gauss points than ro::mix is built for: the species loop with the general mixer
+    // (the flags are the caller's host copy of what m.sp holds: SpeciesDev::ro is set for 2 <= Y <= 20 only)
+    const bool general = any_ro && m.Y != ro::NY;
     // short runs (about ten points, each folding in every absorber): a wavefront lives for a fraction of a
     // millisecond, so the last round of workgroups does not leave the chip half empty
     static const int waves = [] { const char* e = getenv("HELIOS_RT_MIX_WAVES"); return e ? atoi(e) : 256 * 16 * 48; }();
@@ -890,7 +893,8 @@ extern "C++" int hx::launch_mix_species(hx_context* ctx, MixArgs m, const int* a
         m.abs_list = abs_list + first;
         m.nabs = std::min(MIX_MAX_ABSORBERS, nabs_all - first);
         m.carry_on = first > 0 ? 1 : 0;
-        k_rt_mix_species<<<grid, 64, extra_lds, ctx->stream>>>(m);
+        if (general) k_rt_species_mix_ny<<<grid, 64, extra_lds, ctx->stream>>>(m);
+        else k_rt_mix_species<<<grid, 64, extra_lds, ctx->stream>>>(m);
         HX_LAUNCH_CHECK(ctx);
     }
     return 0;
@@ -918,7 +922,9 @@ static int refresh_species(hx_rt* rt) {
     HX_LAUNCH_CHECK(ctx);
     {
         ProfScope ps(rt, "add_to_mixed_opac");
-        rc = launch_mix_species(ctx, m, rt->abs_list, rt->nabs);
+        bool any_ro = false;
+        for (const Species& sp : rt->species) any_ro = any_ro || (sp.absorbing && rt->f.kcoeff_mixing_ro && !sp.is_cia && rt->Y != 1);
+        rc = launch_mix_species(ctx, m, rt->abs_list, rt->nabs, any_ro);
         if (rc) return rc;
     }
     {
@@ -950,10 +956,10 @@ int hx_rt_refresh(hx_rt* rt) {
     const int X = rt->X, Y = rt->Y, L = rt->L, I = rt->I, C = rt->C;
     const size_t nc = (size_t)X * Y;
     int rc = 0;
-    if (rt->d.nspecies > 0) {  // computation.py:1343: random overlap is written for 20 Gauss points
+    if (rt->d.nspecies > 0) {  // the reference's random overlap is written for 20 Gauss points; here: 2 ... 20 (random_overlap_ny.h)
         bool any_ro = false;
         for (const Species& sp : rt->species) any_ro = any_ro || (sp.absorbing && rt->f.kcoeff_mixing_ro && !sp.is_cia);
-        if (Y != ro::NY && Y != 1 && any_ro)  // ny == 1 mixes correlated-k in the reference too (kernels.cu:3302)
+        if (Y > ro::NY && any_ro)  // (ny == 1 mixes correlated-k in the reference too, kernels.cu:3302)
             return hx_fail(ctx, HX_E_RO_NY, "random-overlap mixing needs ny == 20 or 1 (got %d)", Y);
         HX_REQUIRE(ctx, Y <= ro::NY, HX_E_UNSUPPORTED, "on-the-fly mixing in the fused path holds at most 20 Gauss points");
         // (any number of absorbers: the species loop takes them in blocks of MIX_MAX_ABSORBERS, refresh_species)

@@ -1,7 +1,7 @@
 // Per-stage entry points, part 4: on-the-fly opacity mixing (correlated-k and random overlap),
 // H2O Rayleigh scattering, scattering-cross-section accumulation, total asymmetry parameter.
 #include "two_stream.h"
-#include "random_overlap.h"
+#include "random_overlap_ny.h"
 #include <cstdlib>
 #include <string>
 
@@ -223,6 +223,38 @@ k_add_to_mixed_opac_lean(const double* __restrict__ vmr, const double* __restric
     ro::flush(cnt, lane, diag);
 }
 
+// ---- random overlap for 2 <= ny <= 19 Gauss points: the same loop around the general mixer (random_overlap_ny.h)
+__global__ void __launch_bounds__(64) k_add_to_mixed_opac_ny(const double* __restrict__ vmr, const double* __restrict__ opac_spec,
+                       double* __restrict__ opac_wg, const double* __restrict__ meanmolmass,
+                       const double* __restrict__ gauss_weight, const double* __restrict__ gauss_y,
+                       double mass_spec, int ny, int nbin, int nlev, unsigned long long* __restrict__ diag) {
+    __shared__ ro::Shared sh;
+    const int lane = threadIdx.x;
+    ro::init_ny(sh, lane, ny, gauss_weight, gauss_y);
+    const long long npair = (long long)nbin * nlev;
+    const long long chunk = (npair + gridDim.x - 1) / gridDim.x;
+    const long long p0 = (long long)blockIdx.x * chunk, p1 = min(npair, p0 + chunk);
+    int i_cur = -1;
+    double fac = 0.0;
+    ro::Counters cnt;
+    for (long long pair = p0; pair < p1; pair++) {
+        const int i = (int)(pair / nbin);
+        if (i != i_cur) {
+            i_cur = i;
+            fac = vmr[i] * mass_spec / meanmolmass[i];  // (vmr * mass) / mu, then times kappa (:3293)
+        }
+        const size_t base = (size_t)ny * pair;  // = ny*x + ny*nbin*i
+        double my_mix = 0.0, my_add = 0.0;
+        if (lane < ny) {
+            my_mix = opac_wg[base + lane];
+            my_add = fac * opac_spec[base + lane];
+        }
+        const double out = ro::mix_ny(sh, ny, lane, my_mix, my_add, cnt);
+        if (lane < ny) opac_wg[base + lane] = out;
+    }
+    ro::flush(cnt, lane, diag);
+}
+
 __global__ void __launch_bounds__(256)
 k_add_correlated_k(const double* __restrict__ vmr, const double* __restrict__ opac_spec, double* __restrict__ opac_wg,
                    const double* __restrict__ meanmolmass, double mass_spec, int ny, int nbin, int nlev) {
@@ -299,6 +331,27 @@ int hx_add_to_mixed_opac(hx_context* ctx, const double* vmr, const double* opac_
     else
         k_add_to_mixed_opac_lean<<<grid, 64, 0, ctx->stream>>>(vmr, opac_spec, opac_wg, meanmolmass, gauss_weight,
                                                               gauss_y, mass_spec, nbin, nlay_or_nint, ctx->diag);
+    HX_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+int hx_add_to_mixed_opac_ny(hx_context* ctx, const double* vmr, const double* opac_spec, double* opac_wg,
+                            const double* meanmolmass, const double* gauss_weight, const double* gauss_y, double mass_spec,
+                            int s, int ro_method, int ny, int nbin, int nlay_or_nint) {
+    const bool ro_possible = ro_method != 0 && s != 0 && ny != 1;
+    if (!ro_possible || ny >= RO_NY)   // the kernel of 20 points, correlated-k for any ny, the refusal beyond 20
+        return hx_add_to_mixed_opac(ctx, vmr, opac_spec, opac_wg, meanmolmass, gauss_weight, gauss_y, mass_spec, s, ro_method,
+                                    ny, nbin, nlay_or_nint);
+    // HELIOS_RO_SORT chooses between the two kernels of 20 points; below 20 there is one kernel, and a value that asks for
+    // another one (the all-pairs ranking included) is refused instead of being ignored
+    const char* sort = getenv("HELIOS_RO_SORT");
+    if (sort && *sort && std::string(sort) != "lean")
+        return hx_fail(ctx, HX_E_ARG, "HELIOS_RO_SORT=%s: random overlap at %d Gauss points has the one kernel (lean)", sort, ny);
+    const long long npair = (long long)nbin * nlay_or_nint;
+    const int grid = (int)min(npair, (long long)256 * 12 * 16);
+    if (grid > 0)
+        k_add_to_mixed_opac_ny<<<grid, 64, 0, ctx->stream>>>(vmr, opac_spec, opac_wg, meanmolmass, gauss_weight, gauss_y,
+                                                            mass_spec, ny, nbin, nlay_or_nint, ctx->diag);
     HX_LAUNCH_CHECK(ctx);
     return 0;
 }

@@ -17,7 +17,7 @@ from . import hdf5_lite
 from . import host_functions as hsfunc
 from ._tool import DeviceObject, dp
 
-RO_NY = 20          # Gauss points of the random-overlap kernel (csrc/random_overlap.h, ro::NY)
+RO_NY = 20          # most Gauss points the random-overlap kernels hold (csrc/random_overlap.h, ro::NY; fewer: random_overlap_ny.h)
 UNIFORM_RTOL = 1e-9
 
 

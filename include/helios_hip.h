@@ -36,7 +36,7 @@ typedef struct hx_context hx_context;
 typedef struct hx_rt hx_rt;
 
 #define HX_E_ARG 1         /* invalid argument / unsupported dimension */
-#define HX_E_RO_NY 2       /* random-overlap mixing needs ny == 20 (source/kernels.cu:3315) */
+#define HX_E_RO_NY 2       /* random-overlap mixing holds 2 ... 20 Gauss points (hx_add_to_mixed_opac, the reference's kernel: 20 only) */
 #define HX_E_UNSUPPORTED 3 /* configuration outside the fused path; use the per-stage entry points */
 #define HX_E_STATE 4       /* call order violated (e.g. hx_rt_step before hx_rt_refresh) */
 
@@ -295,6 +295,12 @@ int hx_add_to_mixed_opac(hx_context* ctx, const double* vmr, const double* opac_
                          double* opac_wg, const double* meanmolmass, const double* gauss_weight,
                          const double* gauss_y, double mass_spec, int s, int ro_method, int ny,
                          int nbin, int nlay_or_nint);
+/* the same with random overlap for any 2 <= ny <= 20 (the reference's rule with 20 -> ny, 400 -> ny * ny): ny == 20, ny == 1,
+ * correlated-k and ny > 20 are hx_add_to_mixed_opac's */
+int hx_add_to_mixed_opac_ny(hx_context* ctx, const double* vmr, const double* opac_spec,
+                            double* opac_wg, const double* meanmolmass, const double* gauss_weight,
+                            const double* gauss_y, double mass_spec, int s, int ro_method, int ny,
+                            int nbin, int nlay_or_nint);
 /* calc_h2o_scat, kernels.cu:3404 / computation.py:1390 */
 int hx_calc_h2o_scat(hx_context* ctx, const double* temp, const double* press, const double* wave,
                      double* scat_cross, const double* vmr, double mass_h2o, int nbin,
