@@ -1,0 +1,357 @@
+// Line-by-line opacities: Voigt profiles of a resident line list summed onto a spectral grid, per (T, P) node
+// (include/helios_hip.h section 11; the contract and the host side are helios_amd/lines.py, the statements one line and one
+// point at a time tests/lines_reference.py).
+//
+//   k_lines_prepare   one thread per line: nu_0', s = S(T) a / sqrt pi, a and y of the node, kept [4][lines].
+//   k_lines_sum       a workgroup of LINES_THREADS owns LINES_TILE consecutive points, LINES_PPT per thread; point j of thread t is
+//                     tile + j * LINES_THREADS + t, so a wavefront's loads and stores are consecutive.  The host hands the tile the
+//                     index range of the lines that can reach it.  The workgroup stages their four numbers through LDS,
+//                     LINES_BLOCK lines at a time (every lane reads the same address: a broadcast), and every thread walks the
+//                     block in line order, tests the cut-off on nu_0' and adds: a point's sum has the order of the contract, and
+//                     there are no atomics.  A block whose every line is beyond |z| = LINES_FAR for the whole tile -- by its
+//                     distance to the tile or by its y, a test on the region and the same for the whole workgroup -- takes a loop
+//                     that knows the region: the same statements, so the same bits, without the branches.
+//   k_lines_voigt     K(x, y) of the sum at given pairs, for the tests.
+//
+// All arithmetic is fp64 without contraction and complex division is written out.
+#include "hx_tool.h"
+#include "lines_weideman.h"
+
+#include <cmath>
+#include <new>
+#include <vector>
+
+namespace {
+
+constexpr int LINES_THREADS = 256;           // lines.py: THREADS, POINTS_PER_THREAD, LDS_BLOCK, FAR_Z
+constexpr int LINES_PPT = 4;
+constexpr int LINES_TILE = LINES_THREADS * LINES_PPT;
+constexpr int LINES_BLOCK = 256;
+constexpr int LINES_WAVES = LINES_THREADS / 64;
+constexpr double LINES_FAR = 101.0;
+static_assert(LINES_BLOCK <= LINES_THREADS, "a thread stages at most one line of a block");
+
+// phys_const.py
+constexpr double LC_C = 2.99792458e10, LC_KB = 1.380649e-16, LC_H = 6.62607015e-27, LC_NA = 6.02214076e23;
+constexpr double LC_TREF = 296.0, LC_ATM = 1013250.0, LC_YMIN = 1e-8;
+constexpr double LC_LN2 = 0.6931471805599453, LC_INV_SQRT_PI = 0.5641895835477563;
+constexpr double LC_R2_WEIDEMAN = 42.25, LC_R2_EIGHT = 225.0, LC_R2_FOUR = 1.0e4;
+
+__device__ __forceinline__ double lines_k_weideman(double x, double y) {
+    constexpr double A[LINES_WEIDEMAN_N] = {LINES_WEIDEMAN_A};
+    const double lr = LINES_WEIDEMAN_L + y, li = -x;             // l = L - i z
+    const double nr = LINES_WEIDEMAN_L - y, ni = x;              // L + i z
+    const double d = lr * lr + li * li;
+    const double zr = (nr * lr + ni * li) / d, zi = (ni * lr - nr * li) / d;
+    double pr = A[0], pi = 0.0;
+#pragma unroll
+    for (int n = 1; n < LINES_WEIDEMAN_N; n++) {
+        const double tr = pr * zr - pi * zi + A[n];
+        pi = pr * zi + pi * zr;
+        pr = tr;
+    }
+    const double l2r = lr * lr - li * li, l2i = 2.0 * lr * li;
+    const double d2 = l2r * l2r + l2i * l2i;
+    return (2.0 * pr * l2r + 2.0 * pi * l2i) / d2 + LC_INV_SQRT_PI * lr / d;
+}
+
+// Re of (i / sqrt pi) / t with t = z, then t = z - (k/2) / t for k = LEVELS ... 1
+template <int LEVELS>
+__device__ __forceinline__ double lines_k_fraction(double x, double y) {
+    double tr = x, ti = y;
+#pragma unroll
+    for (int k = LEVELS; k >= 1; k--) {
+        const double c = 0.5 * (double)k;
+        const double d = tr * tr + ti * ti;
+        const double nr = x - c * tr / d;
+        ti = y + c * ti / d;
+        tr = nr;
+    }
+    return LC_INV_SQRT_PI * ti / (tr * tr + ti * ti);
+}
+
+__device__ __forceinline__ double lines_k(double x, double y) {
+    const double r2 = x * x + y * y;
+    if (r2 > LC_R2_FOUR) return lines_k_fraction<2>(x, y);
+    if (r2 > LC_R2_EIGHT) return lines_k_fraction<4>(x, y);
+    if (r2 > LC_R2_WEIDEMAN) return lines_k_fraction<8>(x, y);
+    return lines_k_weideman(x, y);
+}
+
+__global__ __launch_bounds__(256) void k_lines_voigt(int n, const double* __restrict__ x, const double* __restrict__ y,
+                                                     double* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = lines_k(x[i], y[i]);
+}
+
+__global__ __launch_bounds__(256) void k_lines_prepare(int n, size_t stride, const double* __restrict__ nu0,
+                                                       const double* __restrict__ s_ref, const double* __restrict__ g_air,
+                                                       const double* __restrict__ g_self, const double* __restrict__ e_low,
+                                                       const double* __restrict__ n_air, const double* __restrict__ delta,
+                                                       double temp, double press, double q_t, double q_ref, double molar_mass,
+                                                       double x_self, double* __restrict__ params) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const double c2 = LC_H * LC_C / LC_KB;
+    const double patm = press / LC_ATM;
+    const double v = nu0[j];
+    const double s = s_ref[j] * (q_ref / q_t) * exp(-c2 * e_low[j] * (1.0 / temp - 1.0 / LC_TREF)) *
+                     (expm1(-c2 * v / temp) / expm1(-c2 * v / LC_TREF));
+    const double vp = v + delta[j] * patm;
+    const double gamma = pow(LC_TREF / temp, n_air[j]) * patm * (g_air[j] * (1.0 - x_self) + g_self[j] * x_self);
+    const double alpha = (vp / LC_C) * sqrt(2.0 * LC_LN2 * LC_NA * LC_KB * temp / molar_mass);
+    const double a = sqrt(LC_LN2) / alpha;
+    params[j] = vp;
+    params[stride + j] = s * a * LC_INV_SQRT_PI;
+    params[2 * stride + j] = a;
+    params[3 * stride + j] = fmax(a * gamma, LC_YMIN);
+}
+
+__global__ __launch_bounds__(LINES_THREADS) void k_lines_sum(const int2* __restrict__ tile_lines, const double* __restrict__ params,
+                                                             size_t stride, int n_points, double nu_first, double dnu, double cutoff,
+                                                             double molar_mass, double* __restrict__ kappa64,
+                                                             float* __restrict__ kappa32) {
+    __shared__ double s_nu[LINES_BLOCK], s_s[LINES_BLOCK], s_a[LINES_BLOCK], s_y[LINES_BLOCK];
+    __shared__ int s_far[LINES_WAVES];
+    const int tid = threadIdx.x;
+    const int tile = blockIdx.x * LINES_TILE;
+    const int2 range = tile_lines[blockIdx.x];
+    double nu[LINES_PPT], acc[LINES_PPT];
+#pragma unroll
+    for (int j = 0; j < LINES_PPT; j++) {
+        nu[j] = nu_first + (double)(tile + j * LINES_THREADS + tid) * dnu;
+        acc[j] = 0.0;
+    }
+    const double tile_lo = nu_first + (double)tile * dnu;
+    const double tile_hi = nu_first + (double)(min(tile + LINES_TILE, n_points) - 1) * dnu;
+
+    for (int b = range.x; b < range.y; b += LINES_BLOCK) {
+        const int n = min(LINES_BLOCK, range.y - b);
+        __syncthreads();                                         // the block before has been walked by every thread
+        int far = 1;
+        if (tid < n) {
+            const double v = params[b + tid], a = params[2 * stride + b + tid], y = params[3 * stride + b + tid];
+            s_nu[tid] = v;
+            s_s[tid] = params[stride + b + tid];
+            s_a[tid] = a;
+            s_y[tid] = y;
+            const double dist = fmax(fmax(v - tile_hi, tile_lo - v), 0.0);
+            far = (a * dist > LINES_FAR) || (y > LINES_FAR);
+        }
+        const int wave_far = __all(far);
+        if ((tid & 63) == 0) s_far[tid >> 6] = wave_far;
+        __syncthreads();
+        int all_far = 1;
+#pragma unroll
+        for (int w = 0; w < LINES_WAVES; w++) all_far &= s_far[w];
+        if (__builtin_amdgcn_readfirstlane(all_far)) {
+            for (int l = 0; l < n; l++) {
+                const double v = s_nu[l], s = s_s[l], a = s_a[l], y = s_y[l];
+#pragma unroll
+                for (int j = 0; j < LINES_PPT; j++) {
+                    const double d = nu[j] - v;
+                    const double term = s * lines_k_fraction<2>(a * d, y);
+                    acc[j] = acc[j] + (fabs(d) <= cutoff ? term : 0.0);
+                }
+            }
+        } else {
+            for (int l = 0; l < n; l++) {
+                const double v = s_nu[l], s = s_s[l], a = s_a[l], y = s_y[l];
+#pragma unroll
+                for (int j = 0; j < LINES_PPT; j++) {
+                    const double d = nu[j] - v;
+                    if (fabs(d) <= cutoff) acc[j] = acc[j] + s * lines_k(a * d, y);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < LINES_PPT; j++) {
+        const int p = tile + j * LINES_THREADS + tid;
+        if (p < n_points) {
+            const double k = acc[j] * LC_NA / molar_mass;
+            kappa64[p] = k;
+            kappa32[p] = (float)k;
+        }
+    }
+}
+
+}  // namespace
+
+struct hx_lines {
+    hx_context* ctx;
+    int lines_max, points_max, n_lines, n_points;
+    double* in[7];                     // nu0, s_ref, gamma_air, gamma_self, e_low, n_air, delta_air: lines_max each
+    double* params;                    // [4][lines_max] of the last node
+    double* kappa64;                   // points_max
+    float* kappa32;
+    int2* tile_lines;                  // per tile of the largest grid
+    std::vector<double> nu0;           // host copy: the tiles' line ranges are searched in it
+    double max_abs_delta;
+    hx_owned owned;
+    hx_stream_timer t_prepare, t_sum;
+    double timing[2];                  // ms in k_lines_prepare and k_lines_sum, of the last run
+};
+
+extern "C" {
+
+int hx_lines_create(hx_context* ctx, int n_lines_max, int n_points_max, hx_lines** out_lines) {
+    if (!ctx || !out_lines) return HX_E_ARG;
+    HX_REQUIRE(ctx, n_lines_max >= 1 && n_lines_max <= (1 << 27), HX_E_ARG, "1 ... 2^27 lines");
+    HX_REQUIRE(ctx, n_points_max >= 1 && n_points_max <= (1 << 30), HX_E_ARG, "1 ... 2^30 spectral points");
+    hx_lines* h = new (std::nothrow) hx_lines();
+    if (!h) return hx_fail(ctx, HX_E_ARG, "no host memory");
+    h->ctx = ctx;
+    h->lines_max = n_lines_max;
+    h->points_max = n_points_max;
+    const size_t nl = (size_t)n_lines_max, np = (size_t)n_points_max;
+    int rc = 0;
+    for (int k = 0; k < 7 && !rc; k++) rc = hx_owned_alloc(ctx, h->owned, nl * 8, &h->in[k]);
+    if (!rc) rc = hx_owned_alloc(ctx, h->owned, 4 * nl * 8, &h->params);
+    if (!rc) rc = hx_owned_alloc(ctx, h->owned, np * 8, &h->kappa64);
+    if (!rc) rc = hx_owned_alloc(ctx, h->owned, np * 4, &h->kappa32);
+    if (!rc) rc = hx_owned_alloc(ctx, h->owned, (size_t)hx_cdiv(n_points_max, LINES_TILE) * sizeof(int2), &h->tile_lines);
+    if (!rc) rc = hx_stream_timer_create(ctx, h->t_prepare);
+    if (!rc) rc = hx_stream_timer_create(ctx, h->t_sum);
+    if (rc) {
+        hx_lines_destroy(h);
+        return rc;
+    }
+    *out_lines = h;
+    return 0;
+}
+
+int hx_lines_destroy(hx_lines* h) {
+    if (!h) return HX_E_ARG;
+    (void)hx_sync(h->ctx);
+    hx_owned_free_all(h->ctx, h->owned);
+    hx_stream_timer_destroy(h->t_prepare);
+    hx_stream_timer_destroy(h->t_sum);
+    delete h;
+    return 0;
+}
+
+int hx_lines_set_lines(hx_lines* h, int n_lines, const double* nu0, const double* s_ref, const double* gamma_air,
+                       const double* gamma_self, const double* e_low, const double* n_air, const double* delta_air) {
+    if (!h) return HX_E_ARG;
+    hx_context* ctx = h->ctx;
+    HX_REQUIRE(ctx, nu0 && s_ref && gamma_air && gamma_self && e_low && n_air && delta_air, HX_E_ARG, "null array");
+    if (n_lines < 1 || n_lines > h->lines_max)
+        return hx_fail(ctx, HX_E_ARG, "hx_lines_set_lines: %d lines, the handle holds 1 ... %d", n_lines, h->lines_max);
+    const double* src[7] = {nu0, s_ref, gamma_air, gamma_self, e_low, n_air, delta_air};
+    static const char* const names[7] = {"nu0", "s_ref", "gamma_air", "gamma_self", "e_low", "n_air", "delta_air"};
+    double max_delta = 0.0;
+    for (int j = 0; j < n_lines; j++) {
+        for (int k = 0; k < 7; k++)
+            if (!std::isfinite(src[k][j]))
+                return hx_fail(ctx, HX_E_ARG, "hx_lines_set_lines: line %d: %s = %g is not a finite number", j, names[k], src[k][j]);
+        if (!(nu0[j] > 0.0)) return hx_fail(ctx, HX_E_ARG, "hx_lines_set_lines: line %d: nu0 = %g is not > 0", j, nu0[j]);
+        if (s_ref[j] < 0.0) return hx_fail(ctx, HX_E_ARG, "hx_lines_set_lines: line %d: s_ref = %g is negative", j, s_ref[j]);
+        if (j > 0 && nu0[j] < nu0[j - 1])
+            return hx_fail(ctx, HX_E_ARG, "hx_lines_set_lines: line %d: nu0 = %.17g lies below line %d's %.17g: the list is sorted",
+                           j, nu0[j], j - 1, nu0[j - 1]);
+        max_delta = std::max(max_delta, fabs(delta_air[j]));
+    }
+    h->n_lines = 0;
+    for (int k = 0; k < 7; k++) {
+        int rc = hx_h2d(ctx, h->in[k], src[k], (size_t)n_lines * 8);
+        if (rc) return rc;
+    }
+    h->nu0.assign(nu0, nu0 + n_lines);
+    h->max_abs_delta = max_delta;
+    h->n_lines = n_lines;
+    h->n_points = 0;
+    return 0;
+}
+
+int hx_lines_run(hx_lines* h, double temp, double press, double q_t, double q_ref, double molar_mass, double x_self,
+                 double cutoff, double nu_first, double dnu, int n_points) {
+    if (!h) return HX_E_ARG;
+    hx_context* ctx = h->ctx;
+    if (h->n_lines < 1) return hx_fail(ctx, HX_E_STATE, "hx_lines_run: no line list (hx_lines_set_lines)");
+    if (n_points < 1 || n_points > h->points_max)
+        return hx_fail(ctx, HX_E_ARG, "hx_lines_run: %d spectral points, the handle holds 1 ... %d", n_points, h->points_max);
+    const struct { const char* name; double v; } positive[] = {{"T", temp}, {"P", press}, {"Q(T)", q_t}, {"Q(296)", q_ref},
+                                                               {"M", molar_mass}, {"cutoff", cutoff}, {"dnu", dnu}};
+    for (const auto& p : positive)
+        if (!(p.v > 0.0) || !std::isfinite(p.v))
+            return hx_fail(ctx, HX_E_ARG, "hx_lines_run: %s = %g is not a finite number > 0", p.name, p.v);
+    if (!(x_self >= 0.0 && x_self <= 1.0)) return hx_fail(ctx, HX_E_ARG, "hx_lines_run: x_self = %g lies outside [0, 1]", x_self);
+    if (!std::isfinite(nu_first)) return hx_fail(ctx, HX_E_ARG, "hx_lines_run: nu of point 0 = %g is not finite", nu_first);
+
+    // per tile the lines whose nu_0 lies within the cut-off, widened by the largest pressure shift, of the tile's points
+    const int n_tiles = hx_cdiv(n_points, LINES_TILE);
+    const double reach = cutoff + h->max_abs_delta * (press / LC_ATM);
+    const double widen = reach * (1.0 + 1e-12) + 1e-9;
+    std::vector<int2> tiles((size_t)n_tiles);
+    for (int t = 0; t < n_tiles; t++) {
+        const int first = t * LINES_TILE, last = std::min(first + LINES_TILE, n_points) - 1;
+        const double lo = nu_first + (double)first * dnu - widen, hi = nu_first + (double)last * dnu + widen;
+        tiles[t].x = (int)(std::lower_bound(h->nu0.begin(), h->nu0.end(), lo) - h->nu0.begin());
+        tiles[t].y = (int)(std::upper_bound(h->nu0.begin(), h->nu0.end(), hi) - h->nu0.begin());
+    }
+    int rc = hx_h2d(ctx, h->tile_lines, tiles.data(), tiles.size() * sizeof(int2));
+    if (!rc) rc = hx_stream_timer_start(ctx, h->t_prepare);
+    if (rc) return rc;
+    const size_t stride = (size_t)h->lines_max;
+    k_lines_prepare<<<hx_cdiv(h->n_lines, 256), 256, 0, ctx->stream>>>(h->n_lines, stride, h->in[0], h->in[1], h->in[2], h->in[3],
+                                                                      h->in[4], h->in[5], h->in[6], temp, press, q_t, q_ref,
+                                                                      molar_mass, x_self, h->params);
+    HX_LAUNCH_CHECK(ctx);
+    rc = hx_stream_timer_stop(ctx, h->t_prepare);
+    if (!rc) rc = hx_stream_timer_start(ctx, h->t_sum);
+    if (rc) return rc;
+    k_lines_sum<<<n_tiles, LINES_THREADS, 0, ctx->stream>>>(h->tile_lines, h->params, stride, n_points, nu_first, dnu, cutoff,
+                                                           molar_mass, h->kappa64, h->kappa32);
+    HX_LAUNCH_CHECK(ctx);
+    h->timing[0] = h->timing[1] = 0.0;  // of this run alone, and it has ended when the call returns
+    rc = hx_stream_timer_stop(ctx, h->t_sum);
+    if (!rc) rc = hx_stream_timer_settle(ctx, h->t_prepare, &h->timing[0]);
+    if (!rc) rc = hx_stream_timer_settle(ctx, h->t_sum, &h->timing[1]);
+    if (!rc) h->n_points = n_points;
+    return rc;
+}
+
+int hx_lines_get(hx_lines* h, const char* name, void* out, size_t out_bytes) {
+    if (!h || !name || !out) return HX_E_ARG;
+    hx_context* ctx = h->ctx;
+    const char* no_run = h->n_points ? nullptr : "no node has been run (hx_lines_run)";
+    if (!strcmp(name, "line_params")) {                          // [4][n_lines] out of [4][lines_max]
+        const size_t row = (size_t)h->n_lines * 8;
+        if (no_run) return hx_fail(ctx, HX_E_STATE, "hx_lines_get: %s", no_run);
+        if (out_bytes != 4 * row) return hx_fail(ctx, HX_E_ARG, "hx_lines_get(line_params): %zu bytes expected, got %zu", 4 * row, out_bytes);
+        for (int k = 0; k < 4; k++) {
+            int rc = hx_d2h(ctx, (char*)out + k * row, h->params + (size_t)k * h->lines_max, row);
+            if (rc) return rc;
+        }
+        return 0;
+    }
+    const hx_result rows[] = {{"kappa64", h->kappa64, (size_t)h->n_points * 8, true, no_run},
+                              {"kappa32", h->kappa32, (size_t)h->n_points * 4, true, no_run},
+                              {"timing_ms", h->timing, sizeof h->timing, false, nullptr}};
+    return hx_get_result(ctx, __func__, rows, 3, name, out, out_bytes);
+}
+
+int hx_lines_voigt(hx_context* ctx, int n, const double* x, const double* y, double* out) {
+    if (!ctx) return HX_E_ARG;
+    HX_REQUIRE(ctx, x && y && out, HX_E_ARG, "null array");
+    HX_REQUIRE(ctx, n >= 1 && n <= (1 << 26), HX_E_ARG, "1 ... 2^26 pairs");
+    hx_owned owned;
+    double *dx = nullptr, *dy = nullptr, *dout = nullptr;
+    const size_t bytes = (size_t)n * 8;
+    int rc = hx_owned_alloc(ctx, owned, bytes, &dx);
+    if (!rc) rc = hx_owned_alloc(ctx, owned, bytes, &dy);
+    if (!rc) rc = hx_owned_alloc(ctx, owned, bytes, &dout);
+    if (!rc) rc = hx_h2d(ctx, dx, x, bytes);
+    if (!rc) rc = hx_h2d(ctx, dy, y, bytes);
+    if (!rc) {
+        k_lines_voigt<<<hx_cdiv(n, 256), 256, 0, ctx->stream>>>(n, dx, dy, dout);
+        rc = hipGetLastError() == hipSuccess ? 0 : hx_fail(ctx, HX_E_ARG, "hx_lines_voigt: the launch failed");
+    }
+    if (!rc) rc = hx_d2h(ctx, out, dout, bytes);
+    (void)hx_sync(ctx);
+    hx_owned_free_all(ctx, owned);
+    return rc;
+}
+
+}  // extern "C"

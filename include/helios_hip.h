@@ -705,6 +705,35 @@ int hx_mie_destroy(hx_mie* mie);
 int hx_mie_run(hx_mie* mie, int n_pairs, const double* x, const double* m_re, const double* m_im, const int* order);
 int hx_mie_get(hx_mie* mie, const char* name, void* out, size_t out_bytes);
 
+/* ---- (11) Line-by-line opacities of a line list on a spectral grid (csrc/lines.hip; the contract and the host side are
+ * helios_amd/lines.py) -----------------------------------------------------------------------------------------------------------
+ * Per (T, P) node: k_lines_prepare writes nu_0', s = S(T) a / sqrt pi, a = sqrt(ln 2) / alpha_D and y = max(a gamma_L, 1e-8) of every
+ * line; k_lines_sum gives a workgroup a tile of consecutive points nu_i = nu_first + i dnu and adds, per point and in the order of
+ * the list, s K(a (nu_i - nu_0'), y) of the lines with |nu_i - nu_0'| <= cutoff, K = Re w(x + i y) in four regions of |z|.  The
+ * host finds a tile's lines by binary search on nu_0, widened by cutoff + max |delta_air| P_atm.  No atomics.
+ *
+ *   hx_lines_create     the largest number of lines and of spectral points the handle holds
+ *   hx_lines_set_lines  the seven per-line arrays, sorted by nu0 (ties in any order the caller fixed); they stay resident.
+ *                       Refused with HX_E_ARG and the line: a value that is not finite, nu0 <= 0, s_ref < 0, a list that is not
+ *                       sorted, more lines than the handle holds
+ *   hx_lines_run        one node: T [K], P [dyne cm^-2], Q(T), Q(296), the molar mass [g/mol], the self-broadening fraction, the
+ *                       cut-off [cm^-1], nu of point 0, dnu, the number of points.  A grid larger than the handle holds or a
+ *                       value out of range is refused before any launch.  Returns when the results are there
+ *   hx_lines_get        "kappa64" (double per point, cm^2 g^-1), "kappa32" (float per point: kappa64 rounded once),
+ *                       "line_params" (double[4][n_lines]: nu_0', s, a, y of the last node), "timing_ms" (double[2]: ms in
+ *                       k_lines_prepare and in k_lines_sum, of the last run)
+ *   hx_lines_voigt      the sum's own K(x, y) at n pairs of host arrays, for the tests
+ */
+typedef struct hx_lines hx_lines;
+int hx_lines_create(hx_context* ctx, int n_lines_max, int n_points_max, hx_lines** out_lines);
+int hx_lines_destroy(hx_lines* lines);
+int hx_lines_set_lines(hx_lines* lines, int n_lines, const double* nu0, const double* s_ref, const double* gamma_air,
+                       const double* gamma_self, const double* e_low, const double* n_air, const double* delta_air);
+int hx_lines_run(hx_lines* lines, double temp, double press, double q_t, double q_ref, double molar_mass, double x_self,
+                 double cutoff, double nu_first, double dnu, int n_points);
+int hx_lines_get(hx_lines* lines, const char* name, void* out, size_t out_bytes);
+int hx_lines_voigt(hx_context* ctx, int n, const double* x, const double* y, double* out);
+
 #ifdef __cplusplus
 }
 #endif
