@@ -22,11 +22,13 @@ def vp(a):
 class DeviceObject(object):
     PREFIX = None
 
-    def _create(self, ctx, *args):
+    def _create(self, ctx, *args, **how):
+        """`constructor`: another of the object's constructors than <PREFIX>_create"""
         from . import _lib
         self.ctx, self._l = ctx, _lib.lib()
         h = ctypes.c_void_p()
-        ctx.check(getattr(self._l, self.PREFIX + "_create")(ctx.handle, *(args + (ctypes.byref(h),))), self.PREFIX + "_create")
+        name = "%s_%s" % (self.PREFIX, how.get("constructor", "create"))
+        ctx.check(getattr(self._l, name)(ctx.handle, *(args + (ctypes.byref(h),))), name)
         self.handle = h
 
     def _call(self, what, *args):

@@ -441,18 +441,24 @@ int hx_ktable_set_grid(hx_ktable* kt, const double* lamda, const int* bin_start,
     return 0;
 }
 
-int hx_ktable_run(hx_ktable* kt, const void* opac_f32, int n_tp, int first_tp) {
-    if (!kt) return HX_E_ARG;
+// what hx_ktable_run and hx_kt_run_device share: the checks, then -- `upload`: the slabs into the table's own buffer first --
+// one launch over the slabs where they then are
+static int kt_run(hx_ktable* kt, const char* fn, const void* slabs, bool upload, int n_tp, int first_tp) {
     hx_context* ctx = kt->ctx;
-    HX_REQUIRE(ctx, kt->have_grid, HX_E_STATE, "set the grid first");
-    HX_REQUIRE(ctx, opac_f32 && n_tp >= 1 && n_tp <= kt->maxtp, HX_E_ARG, "1 ... max_tp_per_launch slabs per call");
-    HX_REQUIRE(ctx, first_tp >= 0 && first_tp <= kt->ntp - n_tp, HX_E_ARG, "the slabs reach beyond the table's (T, P) points");
+#define KT_REQUIRE(cond, code, msg)                                           \
+    do {                                                                      \
+        if (!(cond)) return hx_fail(ctx, (code), "%s: %s", fn, (msg));        \
+    } while (0)
+    KT_REQUIRE(kt->have_grid, HX_E_STATE, "set the grid first");
+    KT_REQUIRE(slabs && n_tp >= 1 && n_tp <= kt->maxtp, HX_E_ARG, "1 ... max_tp_per_launch slabs per call");
+    KT_REQUIRE(first_tp >= 0 && first_tp <= kt->ntp - n_tp, HX_E_ARG, "the slabs reach beyond the table's (T, P) points");
+#undef KT_REQUIRE
     int rc = kt_settle(kt);
-    if (!rc) rc = hx_h2d(ctx, kt->opac, opac_f32, (size_t)n_tp * kt->N * 4);
+    if (!rc && upload) rc = hx_h2d(ctx, kt->opac, slabs, (size_t)n_tp * kt->N * 4);
     if (rc) return rc;
     KtArgs A;
     A.lam = kt->lam; A.bstart = kt->bstart; A.bend = kt->bend; A.inter = kt->inter; A.yg = kt->yg;
-    A.opac = kt->opac; A.scratch = kt->scratch;
+    A.opac = upload ? kt->opac : (const float*)slabs; A.scratch = kt->scratch;
     A.out = kt->out + (size_t)first_tp * kt->nbin * kt->ng;
     A.N = kt->N; A.nbin = kt->nbin; A.ng = kt->ng; A.cap = kt->cap;
     rc = hx_stream_timer_start(ctx, kt->timer);
@@ -464,6 +470,17 @@ int hx_ktable_run(hx_ktable* kt, const void* opac_f32, int n_tp, int first_tp) {
     kt->timing[1] += 1.0;
     kt->timing[3] += n_tp;
     return 0;
+}
+
+int hx_ktable_run(hx_ktable* kt, const void* opac_f32, int n_tp, int first_tp) {
+    if (!kt) return HX_E_ARG;
+    return kt_run(kt, __func__, opac_f32, true, n_tp, first_tp);
+}
+
+int hx_kt_run_device(hx_ktable* kt, const void* d_opac_f32, int n_tp, int first_tp) {
+    if (!kt) return HX_E_ARG;
+    if (!d_opac_f32) return hx_fail(kt->ctx, HX_E_ARG, "hx_kt_run_device: the device slabs are a null pointer");
+    return kt_run(kt, __func__, d_opac_f32, false, n_tp, first_tp);
 }
 
 int hx_ktable_regrid(hx_ktable* kt, int nt_old, int np_old, int nt_new, int np_new, const int* t_left, const int* t_reduced,

@@ -10,6 +10,10 @@ for, sort by (log10 k, weight), accumulate the mid-points of the weights to y, a
 Gauss abscissae.  The host decides bin membership and the empty-bin rule once per species (fp64, the reference's own
 comparisons); the sort, the scan and the interpolation run in k_ktable_bins, or -- `backend="numpy"` -- in numpy, which is the
 checker of the device path and what a machine without a GPU gets when it asks for it.
+
+Where the slabs come from is build_table's `source`: FileSlabs reads them from the directory (build_species, as ever);
+lines.LineSlabs makes them from a line list and leaves them on the device, where KTableBuilder.run_device sorts them without an
+upload (`lines.py -ktable yes`).
 """
 import argparse
 import os
@@ -325,6 +329,11 @@ class KTableBuilder(DeviceObject):
         s = np.ascontiguousarray(slabs, np.float32).reshape(-1, self.n_points)
         self._call("run", vp(s), int(s.shape[0]), int(first))
 
+    def run_device(self, slabs_dptr, n, first):
+        """the same for n slabs [n][n_points] that stand on the device (LineOpacity.slab_pointer): no upload.  Queued on the
+        context's stream behind the kernels that wrote the slabs; returns at once"""
+        self.ctx.check(self._l.hx_kt_run_device(self.handle, slabs_dptr, int(n), int(first)), "hx_kt_run_device")
+
     def regrid(self, temp_old, press_old, temp_new, press_new):
         assert len(temp_old) * len(press_old) == self.n_tp
         plan = regrid_args(temp_old, press_old, temp_new, press_new)
@@ -404,35 +413,67 @@ class SpeciesFiles(object):
         return np.concatenate(chunks)
 
 
+class FileSlabs(object):
+    """where build_table's slabs come from: the files of one directory.  A source has the nodes (`temps`, `press`, ascending,
+    node = p + np * t), `axis()` = (numin of the first chunk, numax of the last, the step between points), `host_slabs` for the
+    numpy backend, `feed` for the device and `close`"""
+
+    def __init__(self, path, heliosk_format="binary"):
+        self.files = SpeciesFiles(path, heliosk_format)
+        self.temps, self.press = self.files.temps, self.files.press
+        self.points = [(t, c) for t in self.files.temps for c in self.files.codes]          # node = p + np * t
+
+    def axis(self):
+        self.res = self.files.resolution()
+        return self.files.numin[0], self.files.numax[-1], self.res
+
+    def read(self, k, n_points):
+        s = self.files.read_point(self.points[k][0], self.points[k][1], self.res)
+        if len(s) != n_points:
+            raise IOError("ktable: %d opacity points for %d wavenumbers at T = %d, %s" % (len(s), n_points, self.points[k][0],
+                                                                                           self.points[k][1]))
+        return s
+
+    def host_slabs(self, pool, n_points):
+        return pool.map(lambda k: self.read(k, n_points), range(len(self.points)))
+
+    def feed(self, b, pool, n_points):
+        # the files of batch n + 1 are read while the kernel of batch n runs; the upload itself is not overlapped
+        ntp = len(self.points)
+        batches = [range(f, min(f + b.max_tp, ntp)) for f in range(0, ntp, b.max_tp)]
+        pending = pool.map(lambda r: np.stack([self.read(k, n_points) for k in r]), batches)
+        for r, slabs in zip(batches, pending):
+            b.run(slabs, r[0])
+
+    def close(self):
+        pass
+
+
 def build_species(path, inter, n_gauss, heliosk_format="binary", backend="hip", ctx=None, tp_per_launch=4,
                   lds_points=LDS_POINTS, target=None, timing=None):
     """datasets of `<name>_opac_kdistr` and, with `target` = (temperatures, pressures), of `<name>_opac_ip_kdistr`"""
     if backend not in ("hip", "numpy"):
         raise IOError("ktable: backend is hip or numpy (got %r)" % (backend,))
-    files = SpeciesFiles(path, heliosk_format)
+    return build_table(FileSlabs(path, heliosk_format), inter, n_gauss, backend, ctx, tp_per_launch, lds_points, target, timing)
+
+
+def build_table(source, inter, n_gauss, backend="hip", ctx=None, tp_per_launch=4, lds_points=LDS_POINTS, target=None, timing=None):
+    """build_species with the slabs of `source`: FileSlabs, or a producer that leaves them on the device (lines.LineSlabs)"""
     inter = np.asarray(inter, np.float64)
     centre, width, yg = grid_datasets(inter, n_gauss)
-    res = files.resolution()
-    lam = spectral_axis(files.numin[0], files.numax[-1], res)
+    numin, numax, res = source.axis()
+    lam = spectral_axis(numin, numax, res)
     start, end = bin_ranges(lam, inter)
     check_empty_bins(lam, inter, start, end)
-    points = [(t, c) for t in files.temps for c in files.codes]          # node = p + np * t
-    nx, ny, ntp = len(start), len(yg), len(points)
+    nx, ny, ntp = len(start), len(yg), len(source.temps) * len(source.press)
     t0 = time.time()
-
-    def read(k):
-        s = files.read_point(points[k][0], points[k][1], res)
-        if len(s) != len(lam):
-            raise IOError("ktable: %d opacity points for %d wavenumbers at T = %d, %s" % (len(s), len(lam), points[k][0],
-                                                                                           points[k][1]))
-        return s
 
     ip = None
     with ThreadPoolExecutor(max_workers=min(MAX_READERS, max(1, tp_per_launch))) as pool:
         if backend == "numpy":
-            k = np.concatenate([numpy_slab(lam, inter, start, end, s, yg).reshape(-1) for s in pool.map(read, range(ntp))])
+            k = np.concatenate([numpy_slab(lam, inter, start, end, s, yg).reshape(-1) for s in source.host_slabs(pool, len(lam))])
             if target is not None:
-                ip = numpy_regrid(files.press, files.temps, k, target[0], target[1], nx, ny)
+                ip = numpy_regrid(source.press, source.temps, k, target[0], target[1], nx, ny)
         else:
             own = ctx is None
             if own:
@@ -442,26 +483,23 @@ def build_species(path, inter, n_gauss, heliosk_format="binary", backend="hip", 
             try:
                 b = KTableBuilder(ctx, len(lam), nx, ny, ntp, tp_per_launch, lds_points)
                 b.set_grid(lam, start, end, inter, yg)
-                # the files of batch n + 1 are read while the kernel of batch n runs; the upload itself is not overlapped
-                batches = [range(f, min(f + b.max_tp, ntp)) for f in range(0, ntp, b.max_tp)]
-                pending = pool.map(lambda r: np.stack([read(k) for k in r]), batches)
-                for r, slabs in zip(batches, pending):
-                    b.run(slabs, r[0])
+                source.feed(b, pool, len(lam))
                 k = b.get("kpoints")
                 if target is not None:
-                    b.regrid(files.temps, files.press, target[0], target[1])
+                    b.regrid(source.temps, source.press, target[0], target[1])
                     ip = b.get("kpoints_ip")
                 if timing is not None:
                     timing["device_ms"] = b.get("timing_ms")
             finally:
                 if b is not None:
                     b.close()
+                source.close()
                 if own:
                     ctx.close()
     if timing is not None:
         timing["seconds"], timing["points"], timing["resolution"] = time.time() - t0, ntp, res
     grid = {"interface wavelengths": inter, "center wavelengths": centre, "wavelength width of bins": width, "ypoints": yg}
-    native = dict(grid, pressures=np.asarray(files.press, np.float64), temperatures=np.asarray(files.temps, np.float64),
+    native = dict(grid, pressures=np.asarray(source.press, np.float64), temperatures=np.asarray(source.temps, np.float64),
                   kpoints=k)
     if ip is None:
         return native, None

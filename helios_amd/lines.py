@@ -50,8 +50,19 @@ because the file name carries them; pressure codes are the keys of ktable.pressu
 TILE_POINTS consecutive points and walks the lines that can reach it, LDS_BLOCK at a time, in order, without atomics.
 `backend="numpy"` computes the same contract on the CPU, line after line over the points in reach: the checker of the device
 path, and what a machine without a GPU gets when it asks for it.
+
+`-ktable yes`: from the line list to the species' k-table without the files (line_ktable).  k_lines_prepare_nodes and
+k_lines_sum_nodes take `-nodes_per_launch` nodes per launch and leave their fp32 slabs on the device, where k_ktable_bins
+(ktable.KTableBuilder.run_device) sorts them on the same stream; nothing but the table comes back.  The containers are the ones
+`lines.py` followed by `ktable.py` writes, to the bit, and what makes them so is part of the contract: the range is the one chunk
+0 ... numax (a chunk's nu is lo + i dnu, so chunks have other bits); the line kernel steps with the `-dnu` given, the k-table's
+axis with numax / points, which is what ktable.py computes from a file's length -- the two are not always the same double, and each
+side keeps its own; temperatures and pressures are sorted ascending and de-duplicated as ktable.SpeciesFiles does, node = p + np t;
+ktable.check_empty_bins and the limit of 2^28 points stand before the first launch.  Refused with `-ktable yes`: `-numin` other
+than 0, `-chunk_width`, `-output_format text`, `-output_directory` (files or table, one per call).
 """
 import argparse
+import ctypes
 import os
 import time
 
@@ -281,10 +292,17 @@ class LineOpacity(DeviceObject):
 
     PREFIX = "hx_lines"
 
-    def __init__(self, ctx, n_lines_max, n_points_max):
+    def __init__(self, ctx, n_lines_max, n_points_max, nodes_per_launch=0, n_nodes_max=0):
+        """`nodes_per_launch` > 0: the handle also runs up to that many of n_nodes_max nodes per launch into fp32 slabs that
+        stay on the device (set_nodes, run_nodes, slab_pointer)"""
         self.n_lines_max, self.n_points_max = int(n_lines_max), int(n_points_max)
-        self.n_lines = self.n_points = 0
-        self._create(ctx, self.n_lines_max, self.n_points_max)
+        self.nodes_per_launch, self.n_nodes_max = int(nodes_per_launch), int(n_nodes_max)
+        self.n_lines = self.n_points = self.n_nodes = self.node_points = self.rows_run = 0
+        if self.nodes_per_launch > 0:
+            self._create(ctx, self.n_lines_max, self.n_points_max, self.nodes_per_launch, self.n_nodes_max,
+                         constructor="create_nodes")
+        else:
+            self._create(ctx, self.n_lines_max, self.n_points_max)
 
     def set_lines(self, lines):
         arr = [np.ascontiguousarray(lines[k], np.float64).reshape(-1) for k in FIELDS]
@@ -297,9 +315,29 @@ class LineOpacity(DeviceObject):
                    float(cutoff), float(nu_first), float(dnu), int(n_points))
         self.n_points = int(n_points)
 
+    def set_nodes(self, temps, pressures, q_t, q_ref, molar_mass, self_fraction, cutoff, nu_first, dnu, n_points):
+        """T, P and Q(T) per node, and what the nodes share; the tiles' line ranges go to the device once, here"""
+        arr = [np.ascontiguousarray(a, np.float64).reshape(-1) for a in (temps, pressures, q_t)]
+        assert len(arr[0]) == len(arr[1]) == len(arr[2])
+        self.n_nodes = self.rows_run = 0
+        self._call("set_nodes", len(arr[0]), dp(arr[0]), dp(arr[1]), dp(arr[2]), float(q_ref), float(molar_mass),
+                   float(self_fraction), float(cutoff), float(nu_first), float(dnu), int(n_points))
+        self.n_nodes, self.node_points = len(arr[0]), int(n_points)
+
+    def run_nodes(self, first, n):
+        """queues nodes first ... first + n - 1 into slab rows 0 ... n - 1; returns at once"""
+        self._call("run_nodes", int(first), int(n))
+        self.rows_run = int(n)
+
+    def slab_pointer(self):
+        """device address of the fp32 slabs [nodes_per_launch][...], rows of the last run_nodes with the stride n_points"""
+        p = ctypes.c_void_p()
+        self._call("device_ptr", b"slabs32", ctypes.byref(p))
+        return p
+
     def _results(self):
         return {"kappa64": self.n_points, "kappa32": (self.n_points, np.float32), "line_params": (4, self.n_lines),
-                "timing_ms": 2}
+                "slabs32": ((self.rows_run, self.node_points), np.float32), "timing_ms": 2}
 
 
 def device_voigt(ctx, x, y):
@@ -422,6 +460,98 @@ def write_file(path, nu, kappa64, output_format):
                 f.write("%.12g %.9g\n" % row)
 
 
+# ---- from the line list to the k-table -----------------------------------------------------------------------------------
+MAX_TABLE_POINTS = 1 << 28            # hx_ktable_create
+
+
+class LineSlabs(object):
+    """ktable.build_table's slabs from a line list: one chunk 0 ... numax of `n_points` points, the nodes sorted ascending and
+    de-duplicated as ktable.SpeciesFiles does (node = p + np * t).  On the device the slabs never leave it; `ms` and `pairs`
+    hold the kernel times and the pairs evaluated once the table is built"""
+
+    def __init__(self, lines, q_table, temps, pressures, numax, dnu, n_points, molar_mass, self_fraction, cutoff,
+                 nodes_per_launch=4, count=True):
+        self.lines, self.numax, self.dnu, self.n_points = lines, int(numax), float(dnu), int(n_points)
+        self.temps, self.press = sorted(set(temps)), sorted(set(pressures))
+        self.molar_mass, self.self_fraction, self.cutoff = molar_mass, self_fraction, cutoff
+        self.q_ref = partition_value(q_table, T_REF)
+        self.q_t = [partition_value(q_table, t) for t in self.temps]
+        self.nodes_per_launch, self.count = max(1, int(nodes_per_launch)), count
+        self.handle, self.ms, self.pairs, self.by_region = None, np.zeros(2), 0, np.zeros(4, np.int64)
+
+    def axis(self):
+        return 0, self.numax, self.numax / self.n_points           # ktable.SpeciesFiles.resolution() of the file not written
+
+    def _check(self, n_points):
+        if n_points != self.n_points:
+            raise IOError("lines: the k-table's axis 0 ... %d cm^-1 at %.17g cm^-1 has %d points, the line kernel's grid at "
+                          "-dnu %.17g has %d" % (self.numax, self.numax / self.n_points, n_points, self.dnu, self.n_points))
+
+    def host_slabs(self, pool, n_points):
+        self._check(n_points)
+        for it, t in enumerate(self.temps):
+            for p in self.press:
+                prm = line_params(self.lines, float(t), p, self.q_t[it], self.q_ref, self.molar_mass, self.self_fraction)
+                yield numpy_node(prm, 0.0, self.dnu, self.n_points, self.cutoff, self.molar_mass,
+                                 self.by_region if self.count else None).astype(np.float32)
+        self.pairs = int(self.by_region.sum())
+
+    def feed(self, b, pool, n_points):
+        self._check(n_points)
+        nodes = [(float(t), p, self.q_t[it]) for it, t in enumerate(self.temps) for p in self.press]
+        per = min(self.nodes_per_launch, b.max_tp)
+        self.handle = h = LineOpacity(b.ctx, len(self.lines["nu0"]), self.n_points, per, len(nodes))
+        h.set_lines(self.lines)
+        h.set_nodes([n[0] for n in nodes], [n[1] for n in nodes], [n[2] for n in nodes], self.q_ref, self.molar_mass,
+                    self.self_fraction, self.cutoff, 0.0, self.dnu, self.n_points)
+        slabs = h.slab_pointer()
+        for first in range(0, len(nodes), per):
+            n = min(per, len(nodes) - first)
+            h.run_nodes(first, n)
+            b.run_device(slabs, n, first)
+
+    def close(self):
+        h, self.handle = self.handle, None
+        if h is not None:
+            try:
+                self.ms = h.get("timing_ms")
+            finally:
+                h.close()
+            if self.count:                          # nu_0' depends on P alone
+                self.pairs = len(self.temps) * sum(count_pairs(self.lines["nu0"] + self.lines["delta_air"] * (p / ATM), 0.0,
+                                                               self.dnu, self.n_points, self.cutoff) for p in self.press)
+
+
+def line_ktable(lines, q_table, temps, pressure_codes, numax, dnu, inter, n_gauss, molar_mass=None, self_fraction=0.0,
+                cutoff=DEFAULT_CUTOFF, target=None, backend="device", ctx=None, nodes_per_launch=4, lds_points=None, timing=None):
+    """the data sets of `<name>_opac_kdistr` and, with `target` = (temperatures, pressures), of `<name>_opac_ip_kdistr`, as
+    ktable.build_species returns them for the directory lines.py would write for the same arguments -- to the bit -- without the
+    files.  `temps`: integers in K; `pressure_codes`: keys of ktable.pressure_table(); the range is 0 ... numax in one chunk.
+    `timing` receives prepare_ms, sum_ms, pairs and build_table's entries"""
+    from . import ktable
+    if backend not in ("device", "numpy"):
+        raise ValueError("lines: backend is device or numpy (got %r)" % (backend,))
+    table = ktable.pressure_table()
+    for c in pressure_codes:
+        if c not in table:
+            raise IOError("lines: pressure code %r is not in the table (n800 ... p400)" % (c,))
+    for t in temps:
+        if int(t) != t:
+            raise IOError("lines: the temperature %r is not an integer in K" % (t,))
+    temps, pressures = [int(t) for t in temps], [table[c] for c in pressure_codes]
+    n_points = chunk_limits(0, int(numax), dnu)[0][2]
+    _check_node_inputs(temps, pressures, (0.0, dnu, n_points), molar_mass, self_fraction, cutoff)
+    if n_points > MAX_TABLE_POINTS:
+        raise IOError("lines: %d spectral points, the k-table's kernel takes 1 ... %d" % (n_points, MAX_TABLE_POINTS))
+    source = LineSlabs(sort_lines(lines), q_table, temps, pressures, numax, dnu, n_points, molar_mass, self_fraction, cutoff,
+                       nodes_per_launch, count=timing is not None)
+    out = ktable.build_table(source, inter, n_gauss, "hip" if backend == "device" else "numpy", ctx, source.nodes_per_launch,
+                             ktable.LDS_POINTS if lds_points is None else lds_points, target, timing)
+    if timing is not None:
+        timing["prepare_ms"], timing["sum_ms"], timing["pairs"] = float(source.ms[0]), float(source.ms[1]), source.pairs
+    return out
+
+
 # ---- the tool ----------------------------------------------------------------------------------------------------------
 def parse_args(argv=None):
     p = argparse.ArgumentParser(prog="lines.py", description="line-by-line opacities of a species from a HITRAN line list")
@@ -433,7 +563,7 @@ def parse_args(argv=None):
     p.add_argument("-numin", type=int, default=0)
     p.add_argument("-numax", type=int, required=True)
     p.add_argument("-dnu", type=float, required=True)
-    p.add_argument("-output_directory", required=True)
+    p.add_argument("-output_directory", default=None, help="of the files; required without -ktable yes")
     p.add_argument("-chunk_width", type=int, default=None)
     p.add_argument("-output_format", default="binary", choices=("binary", "text"))
     p.add_argument("-isotopologue", default="1")
@@ -441,7 +571,22 @@ def parse_args(argv=None):
     p.add_argument("-self_fraction", type=float, default=0.0)
     p.add_argument("-cutoff", type=float, default=DEFAULT_CUTOFF)
     p.add_argument("-backend", default="device", choices=("device", "numpy"))
-    return p.parse_args(argv)
+    p.add_argument("-ktable", default="no", choices=("yes", "no"),
+                   help="the species' k-table in place of the files; the options below are ktable.py's")
+    p.add_argument("-grid_format", default="fixed_resolution")
+    p.add_argument("-wavelength_grid", default="50 0.34 200")
+    p.add_argument("-path_to_grid_file", default=None)
+    p.add_argument("-number_of_gaussian_points", type=int, default=20)
+    p.add_argument("-directory_with_individual_files", default="./output/")
+    p.add_argument("-interpolate", default="yes", choices=("yes", "no"))
+    p.add_argument("-temperature_grid", default=None)
+    p.add_argument("-pressure_grid", default=None)
+    p.add_argument("-container", default="h5", choices=("h5", "npz"))
+    p.add_argument("-nodes_per_launch", type=int, default=4)
+    opt = p.parse_args(argv)
+    if opt.ktable == "no" and opt.output_directory is None:
+        p.error("the following arguments are required: -output_directory")
+    return opt
 
 
 def parse_temperatures(text):
@@ -471,12 +616,53 @@ def parse_pressure_codes(text):
     return codes, [table[c] for c in codes]
 
 
+def _refuse_with_ktable(opt):
+    if opt.numin != 0:
+        raise IOError("lines: -ktable yes with -numin %d: the k-table's wavelength axis starts at 0 cm^-1, and ktable.py refuses "
+                      "a directory whose first chunk does not" % opt.numin)
+    if opt.chunk_width is not None:
+        raise IOError("lines: -ktable yes with -chunk_width %d: the table is built from the one chunk 0 ... numax; a chunk's "
+                      "points are lo + i dnu, which are other bits than 0 + i dnu" % opt.chunk_width)
+    if opt.output_format != "binary":
+        raise IOError("lines: -ktable yes with -output_format %s: no opacity file is written, the fp32 opacities stay on the "
+                      "device" % opt.output_format)
+    if opt.output_directory is not None:
+        raise IOError("lines: -ktable yes with -output_directory %s: a call writes the files or the table, not both; the table "
+                      "goes to -directory_with_individual_files" % opt.output_directory)
+    if opt.number_of_gaussian_points < 1:
+        raise IOError("lines: -number_of_gaussian_points is an integer >= 1")
+    if opt.nodes_per_launch < 1:
+        raise IOError("lines: -nodes_per_launch is an integer >= 1")
+
+
+def _main_ktable(opt, lines, q_table, temps, codes, molar_mass, t0):
+    """-ktable yes: `<name>_opac_kdistr` and, with -interpolate yes, `<name>_opac_ip_kdistr`"""
+    from . import ktable
+    inter = ktable.wavelength_grid(opt.grid_format, opt.wavelength_grid.split(), opt.path_to_grid_file)
+    target = ktable.target_grid(opt.temperature_grid, opt.pressure_grid) if opt.interpolate == "yes" else None
+    timing = {}
+    native, ip = line_ktable(lines, q_table, temps, codes, opt.numax, opt.dnu, inter, opt.number_of_gaussian_points, molar_mass,
+                             opt.self_fraction, opt.cutoff, target, opt.backend, None, opt.nodes_per_launch, None, timing)
+    stem = os.path.join(opt.directory_with_individual_files, opt.name)
+    written = [ktable.write_table("%s_opac_kdistr.%s" % (stem, opt.container), native)]
+    if ip is not None:
+        written.append(ktable.write_table("%s_opac_ip_kdistr.%s" % (stem, opt.container), ip))
+    how = "numpy" if opt.backend == "numpy" else "k_lines_prepare_nodes %.1f ms, k_lines_sum_nodes %.1f ms, k_ktable_bins %.1f ms" % (
+        timing["prepare_ms"], timing["sum_ms"], timing["device_ms"][0])
+    print("lines: %d nodes of %d points into %d bins x %d Gauss points, %d pairs, %s, %.2f s -> %s" % (
+        timing["points"], chunk_limits(0, opt.numax, opt.dnu)[0][2], len(inter) - 1,
+        opt.number_of_gaussian_points, timing["pairs"], how, time.time() - t0, ", ".join(written)))
+    return written
+
+
 def main(argv=None):
-    """lines.py: the directory of one species; returns the paths written"""
+    """lines.py: the directory of one species, or with -ktable yes its k-table; returns the paths written"""
     opt = parse_args(argv)
     t0 = time.time()
     temps = parse_temperatures(opt.temperatures)
     codes, pressures = parse_pressure_codes(opt.pressure_codes)
+    if opt.ktable == "yes":
+        _refuse_with_ktable(opt)
     chunks = chunk_limits(opt.numin, opt.numax, opt.dnu, opt.chunk_width)
     if not 0.0 <= opt.self_fraction <= 1.0:
         raise IOError("lines: -self_fraction %r lies outside [0, 1]" % (opt.self_fraction,))
@@ -498,6 +684,8 @@ def main(argv=None):
     n_lines = len(lines["nu0"])
     print("lines: %d lines of isotopologue %s of %s, %d lines of other isotopologues skipped" % (n_lines, opt.isotopologue,
                                                                                                  opt.line_list, skipped))
+    if opt.ktable == "yes":
+        return _main_ktable(opt, lines, q_table, temps, codes, molar_mass, t0)
     if opt.numin != 0:
         print("lines: -numin %d is not 0: ktable.py will refuse the directory" % opt.numin)
     directory = os.path.join(str(opt.output_directory), "")

@@ -580,6 +580,10 @@ int hx_premix_get(hx_premix* pm, const char* name, void* out, size_t out_bytes);
  *   hx_ktable_run       n_tp slabs of fp32 opacities [n_tp][n_points] in ascending WAVENUMBER (as HELIOS-K writes them: point
  *                       j of lamda is entry n_points - 1 - j) into the nodes first_tp ... of the table.  Returns when the
  *                       slabs are on the device; the kernel may still run
+ *   hx_kt_run_device    the same for slabs [n_tp][n_points] that are on the device already (hx_lines_device_ptr): no upload, the
+ *                       same checks and bookkeeping; a null pointer is refused.  The launch goes onto the context's stream, behind
+ *                       the kernels that wrote the slabs and in front of those that overwrite them.  Returns when it is queued.  (The
+ *                       name: the suite holds the set hx_ktable_* to the seven calls of the file route)
  *   hx_ktable_put       a table kpoints[n_tp][n_bins][n_gauss] made elsewhere, in place of hx_ktable_run's
  *   hx_ktable_regrid    bilinear in T and log10 P onto nt_new x np_new nodes (table node = p + np_old * t); per target node
  *                       the left source node and whether the axis is clamped there, as the reference's routine finds them
@@ -593,6 +597,7 @@ int hx_ktable_destroy(hx_ktable* kt);
 int hx_ktable_set_grid(hx_ktable* kt, const double* lamda, const int* bin_start, const int* bin_end, const double* interfaces,
                        const double* gauss_y);
 int hx_ktable_run(hx_ktable* kt, const void* opac_f32, int n_tp, int first_tp);
+int hx_kt_run_device(hx_ktable* kt, const void* d_opac_f32, int n_tp, int first_tp);
 int hx_ktable_put(hx_ktable* kt, const double* kpoints);
 int hx_ktable_regrid(hx_ktable* kt, int nt_old, int np_old, int nt_new, int np_new, const int* t_left, const int* t_reduced,
                      const int* p_left, const int* p_reduced, const double* temp_old, const double* logp_old,
@@ -723,6 +728,24 @@ int hx_mie_get(hx_mie* mie, const char* name, void* out, size_t out_bytes);
  *                       "line_params" (double[4][n_lines]: nu_0', s, a, y of the last node), "timing_ms" (double[2]: ms in
  *                       k_lines_prepare and in k_lines_sum, of the last run)
  *   hx_lines_voigt      the sum's own K(x, y) at n pairs of host arrays, for the tests
+ *
+ * Several nodes per launch, for a consumer on the device (hx_kt_run_device): k_lines_prepare_nodes and k_lines_sum_nodes take the
+ * node as a grid dimension and apply the single-node kernels' statements; the sum stores fp32 only.  Every row of "slabs32" equals,
+ * bit for bit, the "kappa32" hx_lines_run gives for that node alone.
+ *
+ *   hx_lines_create_nodes  a handle of hx_lines_create that also owns params [nodes_per_launch][4][n_lines_max], the fp32 slabs
+ *                       [nodes_per_launch][n_points_max], the records of up to n_nodes_max nodes and the tiles' line ranges.  An
+ *                       allocation the device does not give is refused with its byte count
+ *   hx_lines_set_nodes  T, P, Q(T) per node and what the nodes share, checked as hx_lines_run checks them (a refusal names the
+ *                       node and the value).  The tiles' line ranges are searched once per distinct pressure -- the reach is
+ *                       cutoff + max |delta_air| P_atm -- and go to the device with the records: the only upload of a table
+ *   hx_lines_run_nodes  queues the prepare and the sum of the nodes first_node ... first_node + n_nodes - 1, n_nodes <=
+ *                       nodes_per_launch, on the context's stream: slab rows 0 ... n_nodes - 1, row stride n_points.  No copy and
+ *                       no wait; the timers settle in the next call or in hx_lines_get.  Nodes beyond hx_lines_set_nodes' count or
+ *                       more than the handle holds per launch are refused before any launch, with the counts
+ *   hx_lines_device_ptr "slabs32": the slab buffer's device address
+ *   hx_lines_get        also "slabs32" (float [n_nodes of the last hx_lines_run_nodes][n_points]); after node runs "timing_ms" is
+ *                       the ms in the two node kernels summed since hx_lines_set_nodes
  */
 typedef struct hx_lines hx_lines;
 int hx_lines_create(hx_context* ctx, int n_lines_max, int n_points_max, hx_lines** out_lines);
@@ -733,6 +756,12 @@ int hx_lines_run(hx_lines* lines, double temp, double press, double q_t, double 
                  double cutoff, double nu_first, double dnu, int n_points);
 int hx_lines_get(hx_lines* lines, const char* name, void* out, size_t out_bytes);
 int hx_lines_voigt(hx_context* ctx, int n, const double* x, const double* y, double* out);
+int hx_lines_create_nodes(hx_context* ctx, int n_lines_max, int n_points_max, int nodes_per_launch, int n_nodes_max,
+                          hx_lines** out_lines);
+int hx_lines_set_nodes(hx_lines* lines, int n_nodes, const double* temp, const double* press, const double* q_t, double q_ref,
+                       double molar_mass, double x_self, double cutoff, double nu_first, double dnu, int n_points);
+int hx_lines_run_nodes(hx_lines* lines, int first_node, int n_nodes);
+int hx_lines_device_ptr(hx_lines* lines, const char* name, void** out_dptr);
 
 #ifdef __cplusplus
 }
