@@ -220,8 +220,7 @@ __global__ void __launch_bounds__(64 * COEF_TPB) HX_COEF_KERNEL(KArgs a HX_PLANE
             const Slab s = plain ? slab_coeffs_plain(w0, dtau, a.epsi)
                                  : slab_coeffs(w0, dtau, g0, a.epsi, a.epsi2, cp.mu_star, a.scat_corr, a.i2s, a.dir_beam == 1);
             if (a.diag != nullptr && a.dir_beam == 1) {  // G_limiter's warning (kernels.cu:217-231) as a count
-                const int nlim = (fabs(s.Gp) >= 1e8 ? 1 : 0) + (fabs(s.Gm) >= 1e8 ? 1 : 0);
-                if (nlim) atomicAdd(a.diag + HX_DIAG_G_LIMITED, (unsigned long long)nlim);
+                if (s.nlim) atomicAdd(a.diag + HX_DIAG_G_LIMITED, (unsigned long long)s.nlim);
             }
             double invM = 1.0 / s.M;
             alpha = s.P * invM;

@@ -124,14 +124,21 @@ HX_FLUX_HEAD {
             const double tiny_u_even = scatters ? 0.0 : ((a.iso || odd0) ? 1e-100 : 0.0), tiny_u_odd = scatters ? 0.0 : ((a.iso || !odd0) ? 1e-100 : 0.0);
             auto patch = [&](double v, double tiny) { return flip_negative ? (v < 1e-100 ? fabs(v) : v) : tiny_abs_below(v, tiny); };
             // ---------------- rho: surface -> TOA ----------------
+            // The Moebius map of a half-layer, rho -> alpha^2 rho / (1 - beta rho) + beta, is composed in the variable
+            // e = 1 - rho: [[alpha^2 + beta (1 - beta), (1 - beta - alpha) (1 - beta + alpha)], [beta, 1 - beta]].  Its entries are
+            // formed without cancellation and are not negative (alpha + beta <= 1), so neither the products nor the final
+            // quotient cancel: e comes out to a few ulps.  In rho itself ([[alpha^2 - beta^2, beta], [-beta, 1]]) a deep stack
+            // of nearly conservative scatterers -- the two fixed points 5e-5 apart -- lost nine digits of rho in the product:
+            // 5.5e-5 of the fluxes at 200 half-layers of w0 = 1 - 1e-10, dtau = 700 (tests/test_gpu_coef_edges.py).
             // (the tiles' padding rows and lanes hold alpha = 1, beta = 0: the identity)
             Moebius P = {1.0, 0.0, 0.0, 1.0};
 #pragma unroll
             for (int r = 0; r < ROWS; r++) {
-                const double ga = fma(al[r], al[r], -(be[r] * be[r]));
-                const double n11 = fma(ga, P.p11, be[r] * P.p21), n12 = fma(ga, P.p12, be[r] * P.p22);
-                P.p21 = fma(-be[r], P.p11, P.p21);
-                P.p22 = fma(-be[r], P.p12, P.p22);
+                const double omb = 1.0 - be[r];
+                const double m11 = fma(al[r], al[r], be[r] * omb), m12 = (omb - al[r]) * (omb + al[r]);
+                const double n11 = fma(m11, P.p11, m12 * P.p21), n12 = fma(m11, P.p12, m12 * P.p22);
+                P.p21 = fma(be[r], P.p11, omb * P.p21);
+                P.p22 = fma(be[r], P.p12, omb * P.p22);
                 P.p11 = n11;
                 P.p12 = n12;
             }
@@ -144,7 +151,7 @@ HX_FLUX_HEAD {
             double e11 = K ? below_fixed<K>(P.p11) : from_lane_below<1>(P.p11, k), e12 = K ? below_fixed<K>(P.p12) : from_lane_below<1>(P.p12, k);
             double e21 = K ? below_fixed<K>(P.p21) : from_lane_below<1>(P.p21, k), e22 = K ? below_fixed<K>(P.p22) : from_lane_below<1>(P.p22, k);
             const double alb = K ? group_first_lane<K>(albedo, m.lane) : __shfl(albedo, 0, k);
-            double rho = fma(e11, alb, e12) / fma(e21, alb, e22);   // at this lane's lowest node
+            double rho = 1.0 - fma(e11, 1.0 - alb, e12) / fma(e21, 1.0 - alb, e22);   // at this lane's lowest node
             if (m.j == 0) rho = alb;
             // per row: a = alpha / (1 - beta rho_b) -- the factor of BOTH affine recurrences --, the constant of the sigma
             // recurrence s_up + a rho_b s_down, what the D recurrence needs: beta / (1 - beta rho_b), s_down / (1 - beta rho_b),

@@ -484,7 +484,7 @@ __global__ void __launch_bounds__(256) k_rt_dtau_halves(KArgs a) {
 // (Thomas' c' at the even rows is -1 / rho_n: the reference carries the reciprocal form, which loses digits where the
 // atmosphere below reflects little -- tests/matrix_referee.py measures it against an extended-precision solve.)  rho -- the
 // reflectivity of everything below a node -- follows a Moebius map, i.e. the composition of the 2 x 2 matrices
-// [[alpha^2 - beta^2, beta], [-beta, 1]]; sigma and D are affine recurrences.  All three run on the sweeps' tiling inside
+// [[alpha^2 - beta^2, beta], [-beta, 1]] (composed in 1 - rho, where no entry cancels: rt_flux_kernel.inc); sigma and D are affine recurrences.  All three run on the sweeps' tiling inside
 // k_rt_flux<ROWS, K, true>: local product of a lane's rows, prefix product over the k lanes of the spectral point (DPP), the
 // lane's rows again from its true start value -- on the three coefficient planes the sweeps read, with nothing kept between
 // iterations (no flux state, no work arrays): 1.0 GB per launch at config 2 where the reference-shaped solver moved 9.

@@ -24,6 +24,9 @@ __device__ __forceinline__ double clip_G(double G) {  // kernels.cu:218-231
 
 struct Slab {
     double w0, E, trans, M, N, P, Gp, Gm;
+    int nlim;  // how many of G+- clip_G limited: G_limiter's warnings (kernels.cu:226-228).  Counted where the limit acts --
+               // 1e8 * G / |G| rounds twice and is 1e8 (1 - 2^-53) for one G in twenty, and a NaN is "limited" to a NaN, so
+               // |G| >= 1e8 afterwards misses both
 };
 
 // everything calc_trans_* derives from (w0, total optical depth, g0) for one (half-)layer
@@ -44,14 +47,18 @@ __device__ __forceinline__ Slab slab_coeffs(double w0, double dtau, double g0, d
     s.P = ((zm * zm) - (zp * zp)) * s.trans;
     s.Gp = 0.0;
     s.Gm = 0.0;
+    s.nlim = 0;
     if (!need_G) return s;  // only the direct-beam terms use G+-
     // G+-, :149-213
     const double num = w0 * (E * omg + g0 * epsi / epsi2);
     const double den = E * (1.0 / (epsi * epsi)) * (E - w0) * omg - 1.0 / (mu_star * mu_star);
     const double third = epsi * w0 * g0 * mu_star / (epsi2 * E * omg);
     const double inv = 1.0 / (mu_star * E * omg);
-    s.Gp = clip_G(0.5 * (num / den * (1.0 / epsi + inv) + third));
-    s.Gm = clip_G(0.5 * (num / den * (1.0 / epsi - inv) - third));
+    const double Gp = 0.5 * (num / den * (1.0 / epsi + inv) + third);
+    const double Gm = 0.5 * (num / den * (1.0 / epsi - inv) - third);
+    s.Gp = clip_G(Gp);
+    s.Gm = clip_G(Gm);
+    s.nlim = (fabs(Gp) < 1e8 ? 0 : 1) + (fabs(Gm) < 1e8 ? 0 : 1);
     return s;
 }
 
@@ -72,6 +79,7 @@ __device__ __forceinline__ Slab slab_coeffs_plain(double w0, double dtau, double
     s.P = ((zm * zm) - (zp * zp)) * s.trans;
     s.Gp = 0.0;
     s.Gm = 0.0;
+    s.nlim = 0;
     return s;
 }
 

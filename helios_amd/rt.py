@@ -347,6 +347,7 @@ def case_flags(c):
                 smooth=int(c.smooth), real_star=int(c.real_star),
                 planet_type_gas=0 if c.get("planet_type", "gas") == "rocky" else 1,
                 kcoeff_mixing_ro=0 if c.get("kcoeff_mixing", "RO") == "correlated-k" else 1, iso=int(c.get("iso", 0)),
+                debug=int(c.get("debug", 0) or 0),
                 singlewalk=int(c.get("singlewalk", 0)), matrix=1 if c.get("flux_calc_method", "iteration") == "matrix" else 0,
                 coef_fp32=1 if c.get("prec", "double") == "single" else 0,
                 epsi=float(c.epsi), epsi2=float(c.epsi2), g_0=float(c.g_0),
