@@ -1,7 +1,15 @@
 // k_rt_coef (fp64 coefficient planes) and k_rt_coef_f32 (fp32, `precision = single`: every value computed in fp64 and
 // rounded to nearest once, when it is stored -- see plane_code.h): one source, included twice by rt_kernels.h (as
-// rt_flux_kernel.inc)
-template <int ROWS, int COEF_TPB>
+// rt_flux_kernel.inc).
+// A third inclusion defines HX_COEF_FLAG so that the batch's flags are compile-time values (k_rt_coef_plain, rt_kernels.h):
+// the same statements, of which the compiler then keeps one path.
+#ifndef HX_COEF_FLAG
+#define HX_COEF_FLAG(name) a.name
+#define HX_COEF_FROM_TABLE a.from_table
+#define HX_COEF_TEMPLATE template <int ROWS, int COEF_TPB>
+#define HX_COEF_FLAG_DEFAULTS
+#endif
+HX_COEF_TEMPLATE
 __global__ void __launch_bounds__(64 * COEF_TPB) HX_COEF_KERNEL(KArgs a HX_PLANE_ARG) {
     using CT = HX_PLANE_T;
     extern __shared__ __align__(16) double smem[];
@@ -21,7 +29,7 @@ __global__ void __launch_bounds__(64 * COEF_TPB) HX_COEF_KERNEL(KArgs a HX_PLANE
     // not depend on the Gauss point; read per lane from the band arrays (level-strided: one 64-byte sector per double)
     // they were 18 scattered loads per half-layer -- config 5's k_rt_coef 7.4 ms per refresh against 2.9 ms expected
     // from config 2's rate
-    const size_t ncl = a.cloud_lds ? (size_t)a.H * NBX : 0;
+    const size_t ncl = HX_COEF_FLAG(cloud_lds) ? (size_t)a.H * NBX : 0;
     double* sh_g0 = sh_dc + a.H;
     double* sh_cab = sh_g0 + ncl;
     double* sh_csc = sh_cab + ncl;
@@ -54,7 +62,7 @@ __global__ void __launch_bounds__(64 * COEF_TPB) HX_COEF_KERNEL(KArgs a HX_PLANE
         const double* pint = a.p_int + (size_t)col * a.I;
         const double grav = a.colpar[col].g;
         for (int h = threadIdx.x; h < a.H; h += blockDim.x) {
-            if (a.iso) {  // whole layers (calc_trans_iso, kernels.cu:1015-1104): delta_colmass of host_functions.py:733
+            if (HX_COEF_FLAG(iso)) {  // whole layers (calc_trans_iso, kernels.cu:1015-1104): delta_colmass of host_functions.py:733
                 sh_mu[h] = mml[h];
                 sh_dc[h] = (pint[h] - pint[h + 1]) / grav;
             } else {
@@ -68,7 +76,7 @@ __global__ void __launch_bounds__(64 * COEF_TPB) HX_COEF_KERNEL(KArgs a HX_PLANE
             const int xs = t / a.H, h = t - xs * a.H, x = min(x_base + xs, a.X - 1);
             const size_t src = ((size_t)col * a.X + x) * a.H + h;
             sh_ray[(size_t)h * NBX + xs] = a.half_ray[src];
-            if (a.cloud_lds) {
+            if (HX_COEF_FLAG(cloud_lds)) {
                 sh_g0[(size_t)h * NBX + xs] = a.half_g0[src];
                 sh_cab[(size_t)h * NBX + xs] = a.half_cab[src];
                 sh_csc[(size_t)h * NBX + xs] = a.half_csc[src];
@@ -82,12 +90,12 @@ __global__ void __launch_bounds__(64 * COEF_TPB) HX_COEF_KERNEL(KArgs a HX_PLANE
         // workgroup size (both are powers of two).
         const int q0 = threadIdx.x % TS, nrun = blockDim.x / TS, run = threadIdx.x / TS;
         const int cq = c_of_q[q0];
-        if (a.from_table) {
+        if (HX_COEF_FROM_TABLE) {
             // premixed k-table look-up done while staging (kernels.cu:561-608): the opacity arrays of
             // the reference are not materialised on this path (hx_rt_get rebuilds them on demand)
             const size_t sp = nc, st = nc * a.npress;
             const double* ktable = a.coltab[col].k;   // the k-table of this column's set: col is uniform, one scalar load
-            for (int pass = 0; pass < (a.iso ? 1 : 2); pass++) {
+            for (int pass = 0; pass < (HX_COEF_FLAG(iso) ? 1 : 2); pass++) {
                 const int nlev = pass == 0 ? a.L : a.I;
                 const TPIndex* tp = (pass == 0 ? a.tp_lay : a.tp_int) + (size_t)col * a.I;
                 double* dst = pass == 0 ? sh_lay : sh_int;
@@ -122,7 +130,7 @@ __global__ void __launch_bounds__(64 * COEF_TPB) HX_COEF_KERNEL(KArgs a HX_PLANE
             const double* opi = a.opac_wg_int + col * wgI;
             for (int lev = run; lev < a.L; lev += nrun)
                 sh_lay[(size_t)lev * TSP + q0] = cq >= 0 ? opl[(size_t)cq + nc * lev] : 0.0;
-            if (!a.iso)
+            if (!HX_COEF_FLAG(iso))
                 for (int lev = run; lev < a.I; lev += nrun)
                     sh_int[(size_t)lev * TSP + q0] = cq >= 0 ? opi[(size_t)cq + nc * lev] : 0.0;
         }
@@ -136,7 +144,7 @@ __global__ void __launch_bounds__(64 * COEF_TPB) HX_COEF_KERNEL(KArgs a HX_PLANE
     const hx_rt_column cp = a.colpar[col];
     CT* ctile = HX_PLANES + col * a.coef_col + (size_t)tl * a.nplane * ROWS * 64;   // (strides in elements of CT)
     const double nmu = -cp.mu_star;
-    const bool plain = a.clouds != 1 && a.scat_corr != 1 && a.g_0 == 0.0 && a.dir_beam != 1;
+    const bool plain = HX_COEF_FLAG(clouds) != 1 && HX_COEF_FLAG(scat_corr) != 1 && HX_COEF_FLAG(g_0) == 0.0 && HX_COEF_FLAG(dir_beam) != 1;
     // The beam at the nodes of this lane's half-layers.  Half-layer h spans the nodes h (bottom) and h + 1 (top) -- even
     // nodes are interfaces (F_dir_wg), odd ones layer centres (Fc_dir_wg); isothermal: node = interface -- so the top value
     // of one row is the bottom value of the next: ONE load per row instead of two, requested a whole row of arithmetic
@@ -145,8 +153,8 @@ __global__ void __launch_bounds__(64 * COEF_TPB) HX_COEF_KERNEL(KArgs a HX_PLANE
     const double* Fd = a.F_dir_wg + col * wgI;
     const double* Fc = a.Fc_dir_wg + col * wgI;
     auto beam_at_node = [&](int n) -> double {
-        if (!(a.dir_beam == 1 && valid && n <= a.H)) return 0.0;
-        if (a.iso) return Fd[(size_t)c + nc * n];
+        if (!(HX_COEF_FLAG(dir_beam) == 1 && valid && n <= a.H)) return 0.0;
+        if (HX_COEF_FLAG(iso)) return Fd[(size_t)c + nc * n];
         return (n & 1) ? Fc[(size_t)c + nc * (n >> 1)] : Fd[(size_t)c + nc * (n >> 1)];
     };
     double F_here = beam_at_node(j * ROWS), F_above = beam_at_node(j * ROWS + 1);
@@ -156,27 +164,27 @@ __global__ void __launch_bounds__(64 * COEF_TPB) HX_COEF_KERNEL(KArgs a HX_PLANE
     // u' B_near + v' B_far, so the planes serve both branches.  The trigger is a property of the whole column: the k lanes of a
     // point vote before any of them writes a coefficient.
     bool scatters = true;
-    if (a.matrix) {
+    if (HX_COEF_FLAG(matrix)) {
         bool mine = false;
 #pragma unroll 1
         for (int r = 0; r < ROWS; r++) {
             const int h = j * ROWS + r;
             if (valid && h < a.H) {
-                const int i = a.iso ? h : h >> 1;
-                const bool lower = a.iso || (h & 1) == 0;
+                const int i = HX_COEF_FLAG(iso) ? h : h >> 1;
+                const bool lower = HX_COEF_FLAG(iso) || (h & 1) == 0;
                 const int ii = lower ? i : i + 1;
                 double ray = 0.0, csc = 0.0, cab = 0.0;
-                if (a.cloud_lds) {
+                if (HX_COEF_FLAG(cloud_lds)) {
                     cab = sh_cab[(size_t)h * NBX + xs];
                     csc = sh_csc[(size_t)h * NBX + xs];
-                } else if (a.clouds == 1) {
+                } else if (HX_COEF_FLAG(clouds) == 1) {
                     const size_t src = ((size_t)col * a.X + x) * a.H + h;
                     cab = a.half_cab[src];
                     csc = a.half_csc[src];
                 }
                 if (a.scat == 1) ray = sh_ray[(size_t)h * NBX + xs];
-                const double o_l = sh_lay[(size_t)i * TSP + q], o_i = a.iso ? o_l : sh_int[(size_t)ii * TSP + q];
-                const double kap = a.iso ? o_l : (lower ? (o_i + o_l) / 2.0 : (o_l + o_i) / 2.0);
+                const double o_l = sh_lay[(size_t)i * TSP + q], o_i = HX_COEF_FLAG(iso) ? o_l : sh_int[(size_t)ii * TSP + q];
+                const double kap = HX_COEF_FLAG(iso) ? o_l : (lower ? (o_i + o_l) / 2.0 : (o_l + o_i) / 2.0);
                 mine = mine || single_scat_albedo(ray + csc, kap * sh_mu[h] + cab, a.w_0_limit) > a.w_0_scat_limit;
             }
         }
@@ -192,35 +200,37 @@ __global__ void __launch_bounds__(64 * COEF_TPB) HX_COEF_KERNEL(KArgs a HX_PLANE
         F_here = F_above;
         F_above = beam_at_node(h + 2);      // the next row's top node: in flight during this row's arithmetic
         if (valid && h < a.H) {
-            const int i = a.iso ? h : h >> 1;
-            const bool lower = a.iso || (h & 1) == 0;
+            const int i = HX_COEF_FLAG(iso) ? h : h >> 1;
+            const bool lower = HX_COEF_FLAG(iso) || (h & 1) == 0;
             // lower half averages (interface i, centre i); upper half (centre i, interface i+1); isothermal layers take
             // the layer-centre values as they are
             const int ii = lower ? i : i + 1;
-            double g0 = a.g_0, ray = 0.0, csc = 0.0, cab = 0.0;
-            if (a.cloud_lds) {
+            double g0 = HX_COEF_FLAG(g_0), ray = 0.0, csc = 0.0, cab = 0.0;
+            if (HX_COEF_FLAG(cloud_lds)) {
                 g0 = sh_g0[(size_t)h * NBX + xs];
                 cab = sh_cab[(size_t)h * NBX + xs];
                 csc = sh_csc[(size_t)h * NBX + xs];
-            } else if (a.clouds == 1) {  // the staged image would not fit the LDS: from the bin-major rows
+            } else if (HX_COEF_FLAG(clouds) == 1) {  // the staged image would not fit the LDS: from the bin-major rows
                 const size_t src = ((size_t)col * a.X + x) * a.H + h;
                 g0 = a.half_g0[src];
                 cab = a.half_cab[src];
                 csc = a.half_csc[src];
             }
             if (a.scat == 1) ray = sh_ray[(size_t)h * NBX + xs];
-            const double o_l = sh_lay[(size_t)i * TSP + q], o_i = a.iso ? o_l : sh_int[(size_t)ii * TSP + q];
-            const double kap = a.iso ? o_l : (lower ? (o_i + o_l) / 2.0 : (o_l + o_i) / 2.0);
+            const double o_l = sh_lay[(size_t)i * TSP + q], o_i = HX_COEF_FLAG(iso) ? o_l : sh_int[(size_t)ii * TSP + q];
+            const double kap = HX_COEF_FLAG(iso) ? o_l : (lower ? (o_i + o_l) / 2.0 : (o_l + o_i) / 2.0);
             const double mu = sh_mu[h], dcol = sh_dc[h];
             const double w0 = single_scat_albedo(ray + csc, kap * mu + cab, a.w_0_limit);
+            // (ray / mu does not depend on the Gauss point.  k_rt_half_bands storing the quotient for k_rt_coef_plain to read was
+            // measured: 404-414 -> 428-433 us per refresh, and 4 us more in k_rt_half_bands -- the kernel is not at the issue rate)
             const double dtau_gas = dcol * (kap + ray / mu);
             // `plain` (wave-uniform): no clouds, no I2S correction, g0 = 0, no beam -- the cloud term is an exact zero and
             // E (1 - w0 g0) an exact one: the general formulas minus their no-ops, same bits (two_stream.h)
             const double dtau = plain ? dtau_gas : dtau_gas + dcol * (cab + csc) / mu;
             const Slab s = plain ? slab_coeffs_plain(w0, dtau, a.epsi)
-                                 : slab_coeffs(w0, dtau, g0, a.epsi, a.epsi2, cp.mu_star, a.scat_corr, a.i2s, a.dir_beam == 1);
-            if (a.diag != nullptr && a.dir_beam == 1) {  // G_limiter's warning (kernels.cu:217-231) as a count
-                if (s.nlim) atomicAdd(a.diag + HX_DIAG_G_LIMITED, (unsigned long long)s.nlim);
+                                 : slab_coeffs(w0, dtau, g0, a.epsi, a.epsi2, cp.mu_star, HX_COEF_FLAG(scat_corr), a.i2s, HX_COEF_FLAG(dir_beam) == 1);
+            if (HX_COEF_FLAG(diag) != nullptr && HX_COEF_FLAG(dir_beam) == 1) {  // G_limiter's warning (kernels.cu:217-231) as a count
+                if (s.nlim) atomicAdd(HX_COEF_FLAG(diag) + HX_DIAG_G_LIMITED, (unsigned long long)s.nlim);
             }
             double invM = 1.0 / s.M;
             alpha = s.P * invM;
@@ -234,14 +244,14 @@ __global__ void __launch_bounds__(64 * COEF_TPB) HX_COEF_KERNEL(KArgs a HX_PLANE
                 beta = 0.0;
                 invM = 1.0;
                 K = 2.0 * HX_PI * a.epsi;
-                if (a.iso || dtau < a.dtau_limit) {
+                if (HX_COEF_FLAG(iso) || dtau < a.dtau_limit) {
                     u = v = (1.0 - s.trans) / 2.0;
                 } else {
                     const double gq = a.epsi * (s.trans - 1.0) / dtau;
                     u = 1.0 + gq;
                     v = -s.trans - gq;
                 }
-            } else if (a.iso || dtau < a.dtau_limit) {  // isothermal source: B (N + M - P) (kernels.cu:1442, :1640-1643)
+            } else if (HX_COEF_FLAG(iso) || dtau < a.dtau_limit) {  // isothermal source: B (N + M - P) (kernels.cu:1442, :1640-1643)
                 u = v = (s.N + s.M - s.P) / 2.0;
             } else {
                 const double qq = (plain ? a.epsi : a.epsi / (s.E * (1.0 - w0 * g0))) * (s.P - s.M + s.N) / dtau;
@@ -250,7 +260,7 @@ __global__ void __launch_bounds__(64 * COEF_TPB) HX_COEF_KERNEL(KArgs a HX_PLANE
             }
             up = K * u * invM;
             vp = K * v * invM;
-            if (a.dir_beam == 1 && scatters) {
+            if (HX_COEF_FLAG(dir_beam) == 1 && scatters) {
                 // beam at node h (bottom) and h+1 (top) of this half-layer: Fbot, Ftop from above
                 const double dn = Fbot / nmu * (s.Gm * s.M + s.Gp * s.N) - Ftop / nmu * s.Gm * s.P;
                 const double upw = Ftop / nmu * (s.Gm * s.N + s.Gp * s.M) - Fbot / nmu * s.P * s.Gp;
@@ -259,7 +269,7 @@ __global__ void __launch_bounds__(64 * COEF_TPB) HX_COEF_KERNEL(KArgs a HX_PLANE
             }
             if (h == 0) {
                 a.boaK[col * nc + c] = scatters ? (1.0 - w0) / (s.E - w0) : 1.0;   // (pure absorption: (1 - A) pi B_surf, :2349)
-                a.Fdir0[col * nc + c] = a.dir_beam == 1 ? (a.F_dir_wg + col * wgI)[c] : 0.0;
+                a.Fdir0[col * nc + c] = HX_COEF_FLAG(dir_beam) == 1 ? (a.F_dir_wg + col * wgI)[c] : 0.0;
             }
         }
         const size_t off = plane_off(r, lane, ROWS);
@@ -268,16 +278,22 @@ __global__ void __launch_bounds__(64 * COEF_TPB) HX_COEF_KERNEL(KArgs a HX_PLANE
             __builtin_nontemporal_store(alpha, ctile + 0 * ROWS * 64 + off);
             __builtin_nontemporal_store(beta, ctile + 1 * ROWS * 64 + off);
             __builtin_nontemporal_store(up, ctile + 2 * ROWS * 64 + off);
-            if (a.has_vp) __builtin_nontemporal_store(vp, ctile + (size_t)a.pl_vp * ROWS * 64 + off);
+            if (HX_COEF_FLAG(has_vp)) __builtin_nontemporal_store(vp, ctile + (size_t)a.pl_vp * ROWS * 64 + off);
         } else {   // fp32: see plane_code.h (the rows without a half-layer: alpha = 1, beta = 0, rest -0.0)
             __builtin_nontemporal_store(plane0_code(alpha, beta), ctile + 0 * ROWS * 64 + off);
             __builtin_nontemporal_store(plane1_code(beta), ctile + 1 * ROWS * 64 + off);
             __builtin_nontemporal_store((CT)up, ctile + 2 * ROWS * 64 + off);
-            if (a.has_vp) __builtin_nontemporal_store((CT)(up + vp), ctile + (size_t)a.pl_vp * ROWS * 64 + off);
+            if (HX_COEF_FLAG(has_vp)) __builtin_nontemporal_store((CT)(up + vp), ctile + (size_t)a.pl_vp * ROWS * 64 + off);
         }
-        if (a.dir_beam == 1) {
+        if (HX_COEF_FLAG(dir_beam) == 1) {
             __builtin_nontemporal_store((CT)dd, ctile + (size_t)a.pl_dd * ROWS * 64 + off);
             __builtin_nontemporal_store((CT)du, ctile + (size_t)(a.pl_dd + 1) * ROWS * 64 + off);
         }
     }
 }
+#ifdef HX_COEF_FLAG_DEFAULTS
+#undef HX_COEF_FLAG
+#undef HX_COEF_FROM_TABLE
+#undef HX_COEF_TEMPLATE
+#undef HX_COEF_FLAG_DEFAULTS
+#endif

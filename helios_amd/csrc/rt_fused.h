@@ -78,6 +78,8 @@ struct hx_rt {
     bool generic_scans = false;  // k_rt_flux with the runtime-k scans also where k = 16 or 32 (HELIOS_RT_GENERIC_SCANS)
     bool conv_shmem_raised = false;  // dynamic-LDS limit of the convection kernels lifted (deep atmospheres)
     bool coef_shmem_raised = false;  // k_rt_coef's dynamic-LDS limit lifted above 64 KiB (deep atmospheres)
+    bool coef_general = false;       // plain columns too run k_rt_coef, not k_rt_coef_plain (HELIOS_RT_COEF_GENERAL)
+    bool coef_plain_shmem_raised[2] = {false, false};  // the same limit of k_rt_coef_plain<.., FROM_TABLE>
 
     // shared device arrays
     double *interwave = nullptr, *deltawave = nullptr, *wave = nullptr, *gauss_y = nullptr,

@@ -278,7 +278,10 @@ void launch_coef(hx_rt* rt, KArgs a) {
     if (a.cloud_lds) shmem += cloud_image;
     const dim3 grid((ntiles + tpb - 1) / tpb, rt->C);
     if (rt->coef32) select_coef_f32(rt, a, grid, shmem);   // `precision = single` (rt_fused_f32.hip)
-    else select_coef<double>(rt, a, grid, shmem);
+    else if (coef_runs_plain(rt, a)) {
+        ProfScope ps(rt, "rt_coef_plain");                 // (inside "rt_coef": tells a reader which kernel ran)
+        select_coef<double>(rt, a, grid, shmem);
+    } else select_coef<double>(rt, a, grid, shmem);
 }
 
 int set_flux_shmem_limits(hx_rt* rt) {
@@ -370,6 +373,7 @@ static int rt_create_into(hx_rt* rt, hx_context* ctx, const hx_rt_dims* dims, co
     while (rt->coef_tpb > 1 && coef_shmem_bytes(rt, rt->coef_tpb) > 150 * 1024) rt->coef_tpb /= 2;   // (deep columns: the staged layers of fewer tiles)
     if (coef_shmem_bytes(rt, rt->coef_tpb) > 160 * 1024)
         return hx_fail(ctx, HX_E_UNSUPPORTED, "k_rt_coef's staging of one tile exceeds the 160 KiB of LDS");
+    if (const char* e = getenv("HELIOS_RT_COEF_GENERAL")) rt->coef_general = atoi(e) != 0;   // A/B knob, same results
     if (const char* e = getenv("HELIOS_RT_NCHUNK")) rt->nchunk = std::max(1, std::min(4096, atoi(e)));  // tuning knob
     {
         // The up-flux state is the one array a k_rt_flux launch writes and the next one reads.  Where it is larger than

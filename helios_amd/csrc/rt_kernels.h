@@ -109,22 +109,53 @@ __global__ void __launch_bounds__(256) k_rt_nodes(KArgs a) {
     if (blockIdx.x == 0 && blockIdx.y == 0)
         for (int i = threadIdx.x; i < a.I; i += blockDim.x)
             a.T_int[(size_t)col * a.I + i] = interface_T(T, i, a.L);
-    for (int r = ty; r < 32; r += 8) {
-        const int n = n0 + r, x = x0 + tx;
-        if (n < NN && x < a.X) {
-            double v;
-            if (n == a.H + 1) {
-                v = a.Bstar[(size_t)col * a.X + x];
-            } else {
-                double Tn;
-                if (n == a.H + 2) Tn = T[a.L];
-                else if (a.iso) Tn = T[min(n, a.L - 1)];  // isothermal layers: "node" n = layer n (slot H is not used)
-                else if (n & 1) Tn = T[(n - 1) >> 1];
-                else Tn = interface_T(T, n >> 1, a.L);
-                v = planck_lookup(a.planck_grid, Tn, x, a.X, a.dim, a.step);
-            }
-            tile[r][tx] = v;
-        }
+    // A thread's four nodes (rows ty, ty + 8, ...).  Node by node this was eight dependent round trips -- the temperature,
+    // then the two rows of the 0.6 GB Planck table it selects; now two: every temperature is requested first (branch-free,
+    // through indices), then all eight table rows, then the blends exactly as interface_T and planck_lookup write them.
+    enum { DEAD, STAR, LEVEL, INT_BOTTOM, INT_TOP, INT_MID };
+    const int x = x0 + tx, xc = min(x, a.X - 1);
+    int kind[4];
+    double Ta[4], Tb[4], star[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int n = n0 + ty + 8 * q, i = n >> 1;
+        int kd, ia, ib = 0;
+        if (!(n < NN && x < a.X)) { kd = DEAD; ia = 0; }
+        else if (n == a.H + 1) { kd = STAR; ia = 0; }
+        else if (n == a.H + 2) { kd = LEVEL; ia = a.L; }
+        else if (a.iso) { kd = LEVEL; ia = min(n, a.L - 1); }  // isothermal layers: "node" n = layer n (slot H is not used)
+        else if (n & 1) { kd = LEVEL; ia = (n - 1) >> 1; }
+        else if (i == 0) { kd = INT_BOTTOM; ia = 0; ib = 1; }          // interface_T's three cases
+        else if (i == a.L) { kd = INT_TOP; ia = a.L - 1; ib = max(a.L - 2, 0); }
+        else { kd = INT_MID; ia = i - 1; ib = i; }
+        kind[q] = kd;
+        Ta[q] = T[ia];
+        Tb[q] = T[ib];
+        star[q] = kd == STAR ? a.Bstar[(size_t)col * a.X + x] : 0.0;
+    }
+    int tdown[4], tup[4];
+    double tt[4], gd[4], gu[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        double Tn = Ta[q];
+        if (kind[q] == INT_BOTTOM) Tn = Ta[q] - 0.5 * (Tb[q] - Ta[q]);
+        else if (kind[q] == INT_TOP) Tn = Ta[q] + 0.5 * (Ta[q] - Tb[q]);
+        else if (kind[q] == INT_MID) Tn = Ta[q] + 0.5 * (Tb[q] - Ta[q]);
+        // planck_lookup (two_stream.h), its two loads issued for every node (a node on a table row reads that row twice)
+        double t = (Tn - 1.0) / a.step;
+        t = dmax(0.001, dmin(a.dim - 1.001, t));
+        tt[q] = t;
+        tdown[q] = (int)floor(t);
+        tup[q] = (int)ceil(t);
+        gd[q] = a.planck_grid[xc + (size_t)tdown[q] * a.X];
+        gu[q] = a.planck_grid[xc + (size_t)tup[q] * a.X];
+    }
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        double v = gd[q];
+        if (tdown[q] != tup[q]) v = gd[q] * (tup[q] - tt[q]) + gu[q] * (tt[q] - tdown[q]);
+        if (kind[q] == STAR) v = star[q];
+        if (kind[q] != DEAD) tile[ty + 8 * q][tx] = v;
     }
     __syncthreads();
     for (int r = ty; r < 32; r += 8) {
@@ -436,6 +467,31 @@ __global__ void __launch_bounds__(256) k_rt_half_bands(KArgs a) {
 #undef HX_PLANE_T
 #undef HX_PLANE_ARG
 #undef HX_PLANES
+// k_rt_coef_plain<ROWS, TPB, FROM_TABLE>: the fp64 kernel for a plain column -- the sweeps over half-layers, no clouds, no
+// beam, no I2S correction, g_0 = 0 (BASELINE configs 2-4) -- with those flags as compile-time values.  k_rt_coef carries
+// every configuration at run time (109 VGPRs, a row loop of some 25 scalar branches); here the compiler keeps the one path
+// such a column takes.  No statement differs, so the planes have k_rt_coef's bits (tests/test_gpu_coef_plain.py);
+// select_coef chooses between the two (coef_runs_plain, rt_select.h).
+struct CoefPlainFlags {
+    static constexpr int matrix = 0, iso = 0, dir_beam = 0, clouds = 0, cloud_lds = 0, scat_corr = 0, has_vp = 0;
+    static constexpr double g_0 = 0.0;
+    static constexpr unsigned long long* diag = nullptr;
+};
+#define HX_COEF_KERNEL k_rt_coef_plain
+#define HX_PLANE_T double
+#define HX_PLANE_ARG
+#define HX_PLANES a.coef
+#define HX_COEF_FLAG(name) CoefPlainFlags::name
+#define HX_COEF_FROM_TABLE FROM_TABLE
+#define HX_COEF_TEMPLATE template <int ROWS, int COEF_TPB, bool FROM_TABLE>
+#include "rt_coef_kernel.inc"
+#undef HX_COEF_KERNEL
+#undef HX_PLANE_T
+#undef HX_PLANE_ARG
+#undef HX_PLANES
+#undef HX_COEF_FLAG
+#undef HX_COEF_FROM_TABLE
+#undef HX_COEF_TEMPLATE
 
 #ifndef HX_PLANE_KERNELS_ONLY
 // gas optical depths of the half-layers in the reference's layout (needed by the direct beam only)
@@ -595,7 +651,8 @@ __global__ void __launch_bounds__(flux_one_wave(ROWS) ? 64 : 320) k_rt_flux_f32(
 // ---- per iteration: wavelength totals, level 1 ---------------------------------------------------
 // grid (nchunk, C), 256 threads.  Thread t owns the (dir, i) slots t, t+256, ... (< 2I) and walks the
 // bins of its chunk; consecutive threads read consecutive addresses of the [x][i] band arrays.
-__global__ void __launch_bounds__(256) k_rt_totals_a(KArgs a) {
+// (209 workgroups at 10 000 bins, fewer than the chip has CUs: registers are free, the loads of a round all get their own)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) k_rt_totals_a(KArgs a) {
     const int col = blockIdx.y, chunk = blockIdx.x;
     if (a.done[col]) return;
     const int I = a.I;
@@ -606,19 +663,23 @@ __global__ void __launch_bounds__(256) k_rt_totals_a(KArgs a) {
     for (int t = threadIdx.x; t < 2 * I; t += blockDim.x) {
         const int dir = t / I, i = t - dir * I;
         const double* __restrict__ band = (dir == 0 ? a.F_down_band_n : a.F_up_band_n) + (size_t)col * a.X * I;
-        // loads issued eight bins at a time (the loop is latency-bound otherwise); summed in bin order
+        // loads issued NB bins at a time (the loop is latency-bound otherwise: a chunk of 48 bins is two rounds); summed in
+        // bin order
+        constexpr int NB = 24;
         double acc = 0.0;
-        for (int xb = x0; xb < x1; xb += 8) {
-            double v[8];
+        for (int xb = x0; xb < x1; xb += NB) {
+            double v[NB], w[NB];
 #pragma unroll
-            for (int u = 0; u < 8; u++) {  // branch-free so that all 16 loads are in flight together
+            for (int u = 0; u < NB; u++) {  // branch-free so that all loads are in flight together, the bin widths among them
                 const int x = min(xb + u, x1 - 1);
-                const double f = fdir[(size_t)x * I + i], b = band[(size_t)x * I + i];
+                const unsigned o = (unsigned)x * (unsigned)I + (unsigned)i;   // (a column's band array holds fewer than 2^32 values)
+                const double f = fdir[o], b = band[o];
                 v[u] = dir == 0 ? f + b : b;
+                w[u] = dl[x];               // (inside the conditional add below, each width was a round trip of its own)
             }
 #pragma unroll
-            for (int u = 0; u < 8; u++)
-                if (xb + u < x1) acc += v[u] * dl[xb + u];
+            for (int u = 0; u < NB; u++)
+                if (xb + u < x1) acc += v[u] * w[u];
         }
         a.tot_part[(((size_t)col * a.nchunk + chunk) * 2) * I + t] = acc;
     }
@@ -650,6 +711,8 @@ __global__ void __launch_bounds__(1024) k_rt_totals_b(TotalsBArgs q) {
         double s = 0.0;
         if (t < 2 * I) {
             const double* __restrict__ part = a.tot_part + ((size_t)col * a.nchunk * 2) * I + t;
+            // (eight partials in flight at a time.  All of a segment's -- 53 at 10 000 bins -- in two rounds of 32 was measured:
+            // 15.1 us against 15.0, no gain; profiles/step_outside_sweeps_ab.json)
             for (int cb = c0; cb < c1; cb += 8) {
                 double v[8];
 #pragma unroll

@@ -80,8 +80,30 @@ inline size_t coef_shmem_bytes(const hx_rt* rt, int tpb) {
     return ((size_t)(rt->L + rt->I) * TS + (size_t)rt->H * (coef_nbx(rt, tpb) + 2)) * sizeof(double) + 2 * TS * sizeof(int);
 }
 
+// Does this refresh run k_rt_coef_plain?  Exactly the flags that kernel holds at compile time (CoefPlainFlags, rt_kernels.h),
+// on fp64 planes, unless HELIOS_RT_COEF_GENERAL=1 keeps the general kernel (A/B and tests: same bits)
+inline bool coef_runs_plain(const hx_rt* rt, const KArgs& a) {
+    return !rt->coef32 && !rt->coef_general && a.matrix == 0 && a.iso == 0 && a.dir_beam != 1 && a.clouds != 1 && a.cloud_lds == 0 &&
+           a.scat_corr != 1 && a.has_vp == 0 && a.g_0 == 0.0;
+}
+
+template <int ROWS, int TPB, bool FROM_TABLE>
+void coef_plain_kernel(hx_rt* rt, const KArgs& a, dim3 grid, size_t shmem) {
+    if (shmem > 64 * 1024 && !rt->coef_plain_shmem_raised[FROM_TABLE]) {
+        (void)hipFuncSetAttribute((const void*)k_rt_coef_plain<ROWS, TPB, FROM_TABLE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+        rt->coef_plain_shmem_raised[FROM_TABLE] = true;
+    }
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rt_coef_plain<ROWS, TPB, FROM_TABLE>), grid, dim3(64 * TPB), shmem, rt->ctx->stream, a);
+}
+
 template <class CT, int ROWS, int TPB>
 void coef_kernel(hx_rt* rt, const KArgs& a, dim3 grid, size_t shmem) {
+    if constexpr (!planes_fp32<CT>)
+        if (coef_runs_plain(rt, a)) {
+            if (a.from_table) coef_plain_kernel<ROWS, TPB, true>(rt, a, grid, shmem);
+            else coef_plain_kernel<ROWS, TPB, false>(rt, a, grid, shmem);
+            return;
+        }
     const void* kernel;
     if constexpr (planes_fp32<CT>) kernel = (const void*)k_rt_coef_f32<ROWS, TPB>;
     else kernel = (const void*)k_rt_coef<ROWS, TPB>;
