@@ -763,6 +763,45 @@ int hx_lines_set_nodes(hx_lines* lines, int n_nodes, const double* temp, const d
 int hx_lines_run_nodes(hx_lines* lines, int first_node, int n_nodes);
 int hx_lines_device_ptr(hx_lines* lines, const char* name, void** out_dptr);
 
+/* ---- (12) Collision-induced absorption from the blocks of a HITRAN CIA file (csrc/cia.hip; the contract and the host side are
+ * helios_amd/cia.py) -------------------------------------------------------------------------------------------------------------
+ * A block is one temperature's table nu [cm^-1], k [cm^5 molecule^-2]; the blocks of one spectral range form a band, ordered by T.
+ * Per (T, P) node and point nu_i = nu_first + i dnu: the band that holds nu_i, its two blocks around T (one beyond the band's
+ * temperatures), each interpolated linearly in nu with both weights from differences and 0 outside its own points, the two
+ * combined linearly in T, times (P / (K_B T)) N_A / M: cm^2 per gram of the partner of molar mass M.  k_cia_nodes takes the node as
+ * a grid dimension, gives a workgroup a tile of consecutive points and stages the blocks' windows for the tile through LDS.
+ *
+ *   hx_cia_create      the largest number of tabulated values (all blocks together), of blocks and of spectral points, the nodes
+ *                      per launch and in all; with_fp64 != 0: the handle also keeps the rows before rounding.  An allocation the
+ *                      device does not give is refused with its byte count
+ *   hx_cia_set_blocks  block b holds the values block_off[b] ... block_off[b + 1] - 1 of nu and k and stands at block_temp[b];
+ *                      band n holds the blocks band_first[n] ... band_first[n + 1] - 1 and covers band_numin[n] ... band_numax[n].
+ *                      Refused with HX_E_ARG and the place: a block of fewer than 2 points, nu that does not strictly ascend, a
+ *                      value that is not finite, k < 0, temperatures of a band that do not strictly ascend, bands that are not in
+ *                      ascending order or that overlap or touch, more than the handle holds.  The table stays resident
+ *   hx_cia_set_nodes   T [K] and P [dyne cm^-2] per node, the partner's molar mass [g/mol], nu of point 0, dnu, the number of
+ *                      points; a refusal names the node and the value.  The nodes' blocks and weights go to the device here
+ *   hx_cia_run_nodes   queues the nodes first_node ... first_node + n_nodes - 1, n_nodes <= nodes_per_launch, on the context's
+ *                      stream: rows 0 ... n_nodes - 1, row stride n_points.  No copy and no wait; the timer settles in the next
+ *                      call or in hx_cia_get.  Nodes beyond hx_cia_set_nodes' count or more than the handle holds per launch are
+ *                      refused before any launch, with the counts
+ *   hx_cia_device_ptr  "slabs32": the fp32 slab buffer's device address (hx_kt_run_device)
+ *   hx_cia_get         "slabs32" (float [n_nodes of the last hx_cia_run_nodes][n_points]), "kappa64" (double, the same rows
+ *                      before rounding; with_fp64 only), "timing_ms" (double[2]: ms in k_cia_nodes and its launches since
+ *                      hx_cia_set_nodes)
+ */
+typedef struct hx_cia hx_cia;
+int hx_cia_create(hx_context* ctx, int n_values_max, int n_blocks_max, int n_points_max, int nodes_per_launch, int n_nodes_max,
+                  int with_fp64, hx_cia** out_cia);
+int hx_cia_destroy(hx_cia* cia);
+int hx_cia_set_blocks(hx_cia* cia, int n_blocks, const int* block_off, const double* nu, const double* k, const double* block_temp,
+                      int n_bands, const int* band_first, const double* band_numin, const double* band_numax);
+int hx_cia_set_nodes(hx_cia* cia, int n_nodes, const double* temp, const double* press, double partner_mass, double nu_first,
+                     double dnu, int n_points);
+int hx_cia_run_nodes(hx_cia* cia, int first_node, int n_nodes);
+int hx_cia_device_ptr(hx_cia* cia, const char* name, void** out_dptr);
+int hx_cia_get(hx_cia* cia, const char* name, void* out, size_t out_bytes);
+
 #ifdef __cplusplus
 }
 #endif
