@@ -1,0 +1,711 @@
+"""Opacities of one species from an ExoMol line list, on the device (include/helios_hip.h section 13, csrc/exomol.hip).
+
+`lines.py` reads HITRAN `.par` records, a room-temperature data base.  The hot lists are ExoMol's: a `.states` table, one or more
+`.trans` files and `.broad` files per broadener.  This tool makes from them what `lines.py` makes from a `.par` file: the files
+`Out_<name>_<numin>_<numax>_<T>_<pcode>.bin` that `ktable.py` reads, or with `-ktable yes` the species' k-table itself.
+
+States.  Whitespace-separated: id, E [cm^-1], g, J; everything after J is ignored.  The ids are 1, 2, ... n in file order, anything
+else is refused with the line.  J >= 0 and 2 J is an integer to within 1e-9; jidx = round(2 J).
+
+Transitions.  Whitespace-separated: upper id, lower id, A [s^-1]; a fourth column is ignored.  Several files are concatenated in
+the order given.  The wavenumber is always nu_0 = E[up] - E[low] from the states, one fp64 subtraction.  A transition with
+nu_0 <= 0 is skipped and counted.  Refused, with file and line: an id outside 1 ... n, a field that is not a finite number, A < 0;
+and a list of which no transition is left.
+
+Partition function.  lines.read_partition_function and lines.partition_value; nothing here is referred to 296 K, so 296 K need not
+be inside the file.
+
+Broadeners.  `name:fraction:file[:gamma_default:n_default]` each.  Of a `.broad` file only the rows `a0 gamma n J''` are used
+(gamma in cm^-1 bar^-1 at 296 K); rows of other codes are skipped and counted; two `a0` rows for one J'' are refused with both
+line numbers; a J'' the file does not hold takes the broadener's defaults (`-default_broadening`, 0.07 and 0.5, unless the entry
+gives its own).  Fractions are > 0 and used as given.  Without `-broadeners` there is one broadener of fraction 1 with the
+defaults.  The host makes the table [broadener][jidx][gamma, n] up to the states' largest jidx; the device never sees a file.
+
+The contract.  All arithmetic is fp64 and nothing is contracted; H, C, K_B, N_A are phys_const's; every statement is evaluated
+left to right.  With c2 = H C / K_B and P_bar = P / 1e6 dyne cm^-2 (ExoMol's reference pressure is 1 bar), per transition and node:
+    pre    = g[up] * A / (8 * pi * C * nu_0 * nu_0)
+    S      = pre * exp(-c2 * E[low] / T) * (-expm1(-c2 * nu_0 / T)) / Q(T)                          [cm / molecule]
+    gamma  = P_bar * sum over the broadeners b, in the order given, of x_b * gamma_b[jidx[low]] * (296 / T)^n_b[jidx[low]]
+    alpha  = (nu_0 / C) * sqrt(2 * ln 2 * N_A * K_B * T / M),   a = sqrt(ln 2) / alpha,   y = max(a * gamma, 1e-8),
+    s      = S * a * (1 / sqrt pi)
+There is no pressure shift: nu_0' = nu_0.  The sum over the broadeners starts from 0.
+The transitions are sorted by (nu_0, position in the concatenated files), by a stable sort on the host, and every spectral point
+adds its terms in ascending order of that index.
+The strength cut.  At a node a transition is kept iff S >= S_min (`-strength_cutoff`), S the fp64 number above.  With S_min = 0
+every transition is kept, those whose S underflowed to 0 included.  The node's list is the kept transitions in list order.
+The sum is lines.py's, unchanged, over the node's list: the inclusive cut-off |nu_i - nu_0| <= C, K(x, y) in its four regions,
+kappa = sigma N_A / M rounded once to fp32 when written; lines_k and lines_sum_tile on the device, lines.voigt_k and
+lines.numpy_node on the host.  The tool prints per node how many transitions were kept.
+
+Not modelled: `.broad` codes other than `a0`, a pressure shift, a cut relative to the strongest line, super-lines, several
+isotopologues per call; and what lines.py does not model either (no renormalisation for the cut wings, no sub-Lorentzian factor).
+
+`backend="device"`: per launch of up to `-nodes_per_launch` nodes, the node a grid dimension: k_exomol_count flags S >= S_min and
+counts per workgroup of COMPACT_BLOCK transitions, k_exomol_scan turns the counts into offsets, k_exomol_prepare writes nu_0, s, a,
+y of the kept transitions to their positions, k_exomol_ranges finds per tile of TILE_POINTS points the kept transitions within the
+cut-off by bisection in the compacted nu_0, k_exomol_sum is lines_sum_tile.  `backend="numpy"` computes the same contract on the
+CPU: gather, strengths, cut, lines.numpy_node; the checker of the device path, and what a machine without a GPU gets.
+
+`-ktable yes`: as `lines.py -ktable yes`, word for word.  One chunk 0 ... numax; the kernel steps with the `-dnu` given and the
+k-table's axis with numax / points; the nodes sorted ascending and de-duplicated (node = p + np t); ktable.check_empty_bins and the
+limit of 2^28 points stand before the first launch; the fp32 slabs stay on the device for k_ktable_bins.  The containers are the
+ones `exomol.py` followed by `ktable.py` writes, to the bit.  Refused with `-ktable yes`: `-numin` other than 0, `-chunk_width`,
+`-output_format text`, `-output_directory`.
+"""
+import argparse
+import bz2
+import ctypes
+import os
+import time
+import warnings
+
+import numpy as np
+
+from . import phys_const as pc
+from ._tool import DeviceObject, dp, ip
+from .lines import (DEFAULT_CUTOFF, INV_SQRT_PI, LDS_BLOCK, LN2, MAX_TABLE_POINTS, TILE_POINTS, T_REF, WAVEFRONT, Y_MIN, chunk_limits,
+                    count_pairs, file_name, numpy_node, parse_pressure_codes, parse_temperatures, partition_value,
+                    read_partition_function, write_file)
+
+BAR = 1.0e6                           # dyne cm^-2
+DEFAULT_BROADENING = (0.07, 0.5)      # gamma [cm^-1 bar^-1 at 296 K], n
+COMPACT_BLOCK = 256                   # csrc/exomol.hip: EXO_B, the count kernel's block (tests/test_gpu_exomol.py derives its sizes)
+JIDX_MAX = 1 << 20
+RANGE_WIDEN = (1e-12, 1e-9)           # lines_tile_ranges: reach * (1 + 1e-12) + 1e-9
+
+
+# ---- the inputs --------------------------------------------------------------------------------------------------------
+def _open(path):
+    return bz2.open(path, "rt") if str(path).endswith(".bz2") else open(path)
+
+
+def _number(word):
+    try:
+        v = float(word)
+    except ValueError:
+        return np.nan
+    return v if np.isfinite(v) else np.nan
+
+
+def read_states(path):
+    """{"E", "g", "J", "jidx"} of a `.states` file, in the order of the ids 1 ... n"""
+    e, g, jj, jidx = [], [], [], []
+    with _open(path) as f:
+        for nr, line in enumerate(f, 1):
+            if not line.strip():
+                continue
+            where = "line %d of %s (%r)" % (nr, path, line.rstrip("\r\n")[:60])
+            col = line.split()
+            if len(col) < 4:
+                raise IOError("exomol: %s holds %d columns, a state needs id, E, g and J" % (where, len(col)))
+            v = [_number(c) for c in col[:4]]
+            for name, x, c in zip(("id", "E", "g", "J"), v, col):
+                if np.isnan(x):
+                    raise IOError("exomol: %s: %s = %r is not a finite number" % (where, name, c))
+            if v[0] != len(e) + 1:
+                raise IOError("exomol: %s: id %s where %d is expected; the ids are 1, 2, ... in file order" % (where, col[0], len(e) + 1))
+            if v[2] < 0:
+                raise IOError("exomol: %s: g = %r is negative" % (where, v[2]))
+            two_j = 2.0 * v[3]
+            if v[3] < 0 or abs(two_j - round(two_j)) > 1e-9 or round(two_j) > JIDX_MAX:
+                raise IOError("exomol: %s: J = %s; J is >= 0 and 2 J a whole number up to %d" % (where, col[3], JIDX_MAX))
+            e.append(v[1]); g.append(v[2]); jj.append(v[3]); jidx.append(int(round(two_j)))
+    if not e:
+        raise IOError("exomol: %s holds no state" % (path,))
+    return {"E": np.array(e), "g": np.array(g), "J": np.array(jj), "jidx": np.array(jidx, np.int32)}
+
+
+def _transition_columns(path, n_states):
+    """[rows][upper id, lower id, A] of a file whose every row passes the checks of read_transitions, by numpy's reader; None where
+    a row does not, and the caller reads the file line by line to name it"""
+    with _open(path) as f:
+        try:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                v = np.loadtxt(f, dtype=np.float64, usecols=(0, 1, 2), ndmin=2, comments=None)
+        except (ValueError, IndexError):
+            return None
+    ids = v[:, :2]
+    if not (np.all(np.isfinite(v)) and np.all(ids == np.floor(ids)) and np.all((ids >= 1) & (ids <= n_states)) and np.all(v[:, 2] >= 0)):
+        return None
+    return v
+
+
+def read_transitions(paths, states):
+    """({"up", "low" (0-based int32), "A", "nu0"} sorted by (nu_0, position in the concatenated files), skipped) of `.trans` files"""
+    if isinstance(paths, str):
+        paths = [paths]
+    n = len(states["E"])
+    up, low, a = [], [], []
+    for path in paths:
+        v = _transition_columns(path, n)
+        if v is not None:
+            up.append(v[:, 0].astype(np.int64) - 1); low.append(v[:, 1].astype(np.int64) - 1); a.append(v[:, 2].copy())
+            continue
+        rows = ([], [], [])
+        with _open(path) as f:
+            for nr, line in enumerate(f, 1):
+                if not line.strip():
+                    continue
+                col = line.split()
+                where = "line %d of %s (%r)" % (nr, path, line.rstrip("\r\n")[:60])
+                if len(col) < 3:
+                    raise IOError("exomol: %s holds %d columns, a transition needs upper id, lower id and A" % (where, len(col)))
+                v = [_number(c) for c in col[:3]]
+                for name, x, c in zip(("upper id", "lower id", "A"), v, col):
+                    if np.isnan(x):
+                        raise IOError("exomol: %s: %s = %r is not a finite number" % (where, name, c))
+                for name, x, c in zip(("upper id", "lower id"), v, col):
+                    if x != int(x) or not 1 <= x <= n:
+                        raise IOError("exomol: %s: %s = %s lies outside the states' 1 ... %d" % (where, name, c, n))
+                if v[2] < 0:
+                    raise IOError("exomol: %s: A = %r is negative" % (where, v[2]))
+                rows[0].append(int(v[0]) - 1); rows[1].append(int(v[1]) - 1); rows[2].append(v[2])
+        up.append(np.array(rows[0], np.int64)); low.append(np.array(rows[1], np.int64)); a.append(np.array(rows[2], np.float64))
+    return sort_transitions({"up": np.concatenate(up), "low": np.concatenate(low), "A": np.concatenate(a)}, states,
+                            ", ".join(str(p) for p in paths))
+
+
+def sort_transitions(trans, states, origin="the list"):
+    """(the arrays with nu_0 = E[up] - E[low], without the transitions of nu_0 <= 0, sorted by (nu_0, position); skipped)"""
+    up = np.asarray(trans["up"], np.int64).reshape(-1)
+    low = np.asarray(trans["low"], np.int64).reshape(-1)
+    a = np.asarray(trans["A"], np.float64).reshape(-1)
+    n = len(states["E"])
+    if not (len(up) == len(low) == len(a)):
+        raise ValueError("exomol: the three per-transition arrays have one length")
+    for name, v in (("upper", up), ("lower", low)):
+        bad = (v < 0) | (v >= n)
+        if bad.any():
+            j = int(np.argmax(bad))
+            raise ValueError("exomol: transition %d: %s state %d (0-based) lies outside the states' 0 ... %d" % (j, name, v[j], n - 1))
+    bad = ~np.isfinite(a) | (a < 0)
+    if bad.any():
+        j = int(np.argmax(bad))
+        raise ValueError("exomol: transition %d: A = %r is not a finite number >= 0" % (j, float(a[j])))
+    energy = np.asarray(states["E"], np.float64)
+    nu0 = energy[up] - energy[low]
+    keep = nu0 > 0
+    skipped = int(len(nu0) - np.count_nonzero(keep))
+    if not keep.any():
+        raise IOError("exomol: no transition is left of %s (%d with nu_0 <= 0 skipped)" % (origin, skipped))
+    up, low, a, nu0 = up[keep], low[keep], a[keep], nu0[keep]
+    order = np.argsort(nu0, kind="stable")
+    return {"up": np.ascontiguousarray(up[order], np.int32), "low": np.ascontiguousarray(low[order], np.int32),
+            "A": np.ascontiguousarray(a[order]), "nu0": np.ascontiguousarray(nu0[order])}, skipped
+
+
+def read_broad(path):
+    """({jidx: (gamma, n)} of the `a0` rows, rows of other codes skipped) of a `.broad` file"""
+    rows, lines_of, skipped = {}, {}, 0
+    with _open(path) as f:
+        for nr, line in enumerate(f, 1):
+            col = line.split()
+            if not col:
+                continue
+            if col[0] != "a0":
+                skipped += 1
+                continue
+            where = "line %d of %s (%r)" % (nr, path, line.rstrip("\r\n")[:60])
+            if len(col) < 4:
+                raise IOError("exomol: %s holds %d columns, an a0 row needs gamma, n and J''" % (where, len(col)))
+            v = [_number(c) for c in col[1:4]]
+            for name, x, c in zip(("gamma", "n", "J''"), v, col[1:4]):
+                if np.isnan(x):
+                    raise IOError("exomol: %s: %s = %r is not a finite number" % (where, name, c))
+            two_j = 2.0 * v[2]
+            if v[0] < 0 or v[2] < 0 or abs(two_j - round(two_j)) > 1e-9:
+                raise IOError("exomol: %s: gamma is >= 0, J'' is >= 0 and 2 J'' a whole number" % (where,))
+            j = int(round(two_j))
+            if j in rows:
+                raise IOError("exomol: %s: a second a0 row for J'' = %s; the first is line %d" % (where, col[3], lines_of[j]))
+            rows[j], lines_of[j] = (v[0], v[1]), nr
+    return rows, skipped
+
+
+def parse_default_broadening(text):
+    word = str(text).split()
+    v = [_number(w) for w in word]
+    if len(v) != 2 or np.isnan(v).any() or v[0] < 0:
+        raise IOError("exomol: -default_broadening %r: gamma >= 0 and n, separated by a blank" % (text,))
+    return v[0], v[1]
+
+
+def parse_broadeners(text, default=DEFAULT_BROADENING):
+    """[(name, fraction, file or None, gamma_default, n_default)] of `name:fraction:file[:gamma_default:n_default] ...`"""
+    if text is None or not str(text).split():
+        return [("default", 1.0, None, float(default[0]), float(default[1]))]
+    out = []
+    for entry in str(text).split():
+        part = entry.split(":")
+        if len(part) not in (3, 5) or not part[0] or not part[2]:
+            raise IOError("exomol: -broadeners entry %r is not name:fraction:file[:gamma_default:n_default]" % (entry,))
+        v = [_number(w) for w in [part[1]] + part[3:]]
+        if np.isnan(v).any():
+            raise IOError("exomol: -broadeners entry %r: fraction and defaults are finite numbers" % (entry,))
+        if not v[0] > 0:
+            raise IOError("exomol: -broadeners entry %r: the fraction %s is not > 0" % (entry, part[1]))
+        if len(v) == 3 and v[1] < 0:
+            raise IOError("exomol: -broadeners entry %r: the default gamma %s is negative" % (entry, part[3]))
+        out.append((part[0], v[0], part[2]) + ((v[1], v[2]) if len(v) == 3 else (float(default[0]), float(default[1]))))
+    return out
+
+
+def broadening_table(broadeners, max_jidx, report=None):
+    """(fractions [b], table [b][jidx 0 ... max_jidx][gamma, n]); `broadeners`: parse_broadeners' entries, the file of an entry
+    may be a dict {jidx: (gamma, n)} in place of a path.  `report` receives a line per broadener"""
+    x = np.array([b[1] for b in broadeners], np.float64)
+    table = np.empty((len(broadeners), int(max_jidx) + 1, 2))
+    for k, (name, fraction, source, gamma_d, n_d) in enumerate(broadeners):
+        table[k, :, 0], table[k, :, 1] = gamma_d, n_d
+        rows, skipped = ({}, 0) if source is None else (source, 0) if isinstance(source, dict) else read_broad(source)
+        for j, (gamma, n) in rows.items():
+            if j <= max_jidx:
+                table[k, j] = gamma, n
+        if report is not None:
+            held = sum(1 for j in rows if j <= max_jidx)
+            report("exomol: broadener %s, fraction %g: %d of the %d values of 2 J'' from %s, the others gamma = %g, n = %g; "
+                   "%d rows of other codes than a0 skipped" % (name, fraction, held, int(max_jidx) + 1,
+                                                               "a table" if isinstance(source, dict) else source, gamma_d, n_d, skipped))
+    if report is not None:
+        report("exomol: the fractions of the %d broadeners sum to %.12g" % (len(x), float(np.sum(x))))
+    return x, table
+
+
+# ---- the contract in numpy ---------------------------------------------------------------------------------------------
+def strengths(states, trans, temp, q_t):
+    """S(T) per transition [cm / molecule]"""
+    c2 = pc.H * pc.C / pc.K_B
+    nu0 = trans["nu0"]
+    pre = states["g"][trans["up"]] * trans["A"] / (8.0 * np.pi * pc.C * nu0 * nu0)
+    with np.errstate(under="ignore"):
+        return pre * np.exp(-c2 * states["E"][trans["low"]] / temp) * (-np.expm1(-c2 * nu0 / temp)) / q_t
+
+
+def node_params(states, trans, broadening, temp, press, q_t, molar_mass, s_min=0.0):
+    """([4][kept]: nu_0, s = S a / sqrt pi, a, y of the node's kept transitions in list order; their indices in the list)"""
+    strength = strengths(states, trans, temp, q_t)
+    kept = np.nonzero(strength >= s_min)[0]
+    x, table = broadening
+    nu0, jx = trans["nu0"][kept], states["jidx"][trans["low"][kept]]
+    total = np.zeros(len(kept))
+    for b in range(len(x)):
+        total = total + x[b] * table[b, jx, 0] * (T_REF / temp) ** table[b, jx, 1]
+    gamma = (press / BAR) * total
+    alpha = (nu0 / pc.C) * np.sqrt(2.0 * LN2 * pc.N_A * pc.K_B * temp / molar_mass)
+    a = np.sqrt(LN2) / alpha
+    y = np.maximum(a * gamma, Y_MIN)
+    return np.stack([nu0, strength[kept] * a * INV_SQRT_PI, a, y]), kept
+
+
+# ---- device ------------------------------------------------------------------------------------------------------------
+class ExomolOpacity(DeviceObject):
+    """hx_exomol: resident states, broadening table and sorted transitions; nodes of up to n_points_max spectral points,
+    nodes_per_launch per launch into fp32 slabs that stay on the device; `with_fp64`: the rows before rounding as well"""
+
+    PREFIX = "hx_exomol"
+
+    def __init__(self, ctx, n_states_max, n_trans_max, n_broadeners_max, n_points_max, nodes_per_launch, n_nodes_max, with_fp64=False):
+        self.n_points_max, self.nodes_per_launch, self.n_nodes_max = int(n_points_max), int(nodes_per_launch), int(n_nodes_max)
+        self.with_fp64 = bool(with_fp64)
+        self.n_nodes = self.n_points = self.rows_run = self._params_len = 0
+        self._create(ctx, int(n_states_max), int(n_trans_max), int(n_broadeners_max), self.n_points_max, self.nodes_per_launch,
+                     self.n_nodes_max, int(self.with_fp64))
+
+    @classmethod
+    def of(cls, ctx, states, trans, broadening, n_points_max, nodes_per_launch, n_nodes_max, with_fp64=False):
+        """a handle that holds the three inputs"""
+        h = cls(ctx, len(states["E"]), len(trans["nu0"]), len(broadening[0]), n_points_max, nodes_per_launch, n_nodes_max, with_fp64)
+        try:
+            h.set_states(states)
+            h.set_broadening(*broadening)
+            h.set_transitions(trans)
+        except Exception:
+            h.close()
+            raise
+        return h
+
+    def set_states(self, states):
+        e, g = (np.ascontiguousarray(states[k], np.float64).reshape(-1) for k in ("E", "g"))
+        jidx = np.ascontiguousarray(states["jidx"], np.int32).reshape(-1)
+        assert len(e) == len(g) == len(jidx)
+        self.n_nodes = self.rows_run = 0
+        self._call("set_states", len(e), dp(e), dp(g), ip(jidx))
+
+    def set_broadening(self, fractions, table):
+        x = np.ascontiguousarray(fractions, np.float64).reshape(-1)
+        t = np.ascontiguousarray(table, np.float64)
+        assert t.ndim == 3 and t.shape[0] == len(x) and t.shape[2] == 2
+        self.n_nodes = self.rows_run = 0
+        self._call("set_broadening", len(x), t.shape[1], dp(x), dp(t.reshape(-1)))
+
+    def set_transitions(self, trans):
+        up, low = (np.ascontiguousarray(trans[k], np.int32).reshape(-1) for k in ("up", "low"))
+        a = np.ascontiguousarray(trans["A"], np.float64).reshape(-1)
+        assert len(up) == len(low) == len(a)
+        self.n_nodes = self.rows_run = 0
+        self._call("set_transitions", len(a), ip(up), ip(low), dp(a))
+
+    def set_nodes(self, temps, pressures, q_t, molar_mass, cutoff, s_min, nu_first, dnu, n_points):
+        """T, P and Q(T) per node, and what the nodes share"""
+        arr = [np.ascontiguousarray(a, np.float64).reshape(-1) for a in (temps, pressures, q_t)]
+        assert len(arr[0]) == len(arr[1]) == len(arr[2])
+        self.n_nodes = self.rows_run = 0
+        self._call("set_nodes", len(arr[0]), dp(arr[0]), dp(arr[1]), dp(arr[2]), float(molar_mass), float(cutoff), float(s_min),
+                   float(nu_first), float(dnu), int(n_points))
+        self.n_nodes, self.n_points = len(arr[0]), int(n_points)
+
+    def run_nodes(self, first, n):
+        """queues nodes first ... first + n - 1 into rows 0 ... n - 1; returns at once"""
+        self._call("run_nodes", int(first), int(n))
+        self.rows_run = int(n)
+
+    def slab_pointer(self):
+        """device address of the fp32 slabs [nodes_per_launch][...], rows of the last run_nodes with the stride n_points"""
+        p = ctypes.c_void_p()
+        self._call("device_ptr", b"slabs32", ctypes.byref(p))
+        return p
+
+    def get(self, name):
+        """"line_params": a list of [4][kept[row]] per row of the last launch"""
+        if name != "line_params":
+            return DeviceObject.get(self, name)
+        kept = DeviceObject.get(self, "kept")
+        self._params_len = 4 * int(kept.sum())
+        flat = DeviceObject.get(self, name)
+        at = np.concatenate([[0], np.cumsum(4 * kept.astype(np.int64))])
+        return [flat[at[r]:at[r + 1]].reshape(4, int(kept[r])) for r in range(len(kept))]
+
+    def _results(self):
+        tiles = -(-self.n_points // TILE_POINTS)
+        return {"slabs32": ((self.rows_run, self.n_points), np.float32), "kappa64": (self.rows_run, self.n_points),
+                "kept": ((self.rows_run,), np.int32), "tile_ranges": ((self.rows_run, tiles, 2), np.int32),
+                "line_params": self._params_len, "timing_ms": 2}
+
+
+# ---- the library functions -----------------------------------------------------------------------------------------------
+def _check_node_inputs(temps, pressures, nu_grid, molar_mass, cutoff, s_min):
+    temps = np.asarray(temps, np.float64).reshape(-1)
+    pressures = np.asarray(pressures, np.float64).reshape(-1)
+    if len(temps) == 0 or not np.all(np.isfinite(temps) & (temps > 0)):
+        raise ValueError("exomol: every temperature is a finite number > 0 (got %r)" % (temps.tolist(),))
+    if len(pressures) == 0 or not np.all(np.isfinite(pressures) & (pressures > 0)):
+        raise ValueError("exomol: every pressure is a finite number > 0 dyne cm^-2 (got %r)" % (pressures.tolist(),))
+    nu_first, dnu, n_points = float(nu_grid[0]), float(nu_grid[1]), int(nu_grid[2])
+    if not (np.isfinite(dnu) and dnu > 0):
+        raise ValueError("exomol: dnu = %r is not > 0" % (dnu,))
+    if n_points < 1 or not np.isfinite(nu_first):
+        raise ValueError("exomol: the grid (nu_first, dnu, points) = %r needs a finite start and at least one point" % (tuple(nu_grid),))
+    if molar_mass is None or not (np.isfinite(molar_mass) and molar_mass > 0):
+        raise ValueError("exomol: no molar mass (got %r): give one > 0 g/mol" % (molar_mass,))
+    if not (np.isfinite(cutoff) and cutoff > 0):
+        raise ValueError("exomol: the cut-off %r is not > 0 cm^-1" % (cutoff,))
+    if not (np.isfinite(s_min) and s_min >= 0):
+        raise ValueError("exomol: the strength cut-off %r is not a finite number >= 0 cm / molecule" % (s_min,))
+    return temps, pressures, (nu_first, dnu, n_points)
+
+
+def exomol_opacity(states, trans, broadening, q_table, temps, pressures_cgs, nu_grid, molar_mass=None, cutoff=DEFAULT_CUTOFF,
+                   strength_cutoff=0.0, backend="device", ctx=None, nodes_per_launch=4, handle=None, timing=None):
+    """kappa [T][P][nu] in cm^2 g^-1, fp64.  `states`: read_states' arrays; `trans`: sort_transitions' arrays; `broadening`:
+    broadening_table's pair; `q_table`: (T, Q); `nu_grid`: (nu of point 0, dnu, points); `handle`: an ExomolOpacity with fp64 rows
+    that already holds the three inputs.  `timing` receives prepare_ms, sum_ms and pairs, summed over the nodes, and `kept`, the
+    number of transitions kept per node [T][P]"""
+    if backend not in ("device", "numpy"):
+        raise ValueError("exomol: backend is device or numpy (got %r)" % (backend,))
+    s_min = float(strength_cutoff)
+    temps, pressures, (nu_first, dnu, n_points) = _check_node_inputs(temps, pressures_cgs, nu_grid, molar_mass, cutoff, s_min)
+    q_t = [partition_value(q_table, t) for t in temps]
+    out = np.empty((len(temps), len(pressures), n_points))
+    kept = np.zeros((len(temps), len(pressures)), np.int64)
+    pairs, ms = 0, np.zeros(2)
+    if backend == "numpy":
+        for it, t in enumerate(temps):
+            for jp, p in enumerate(pressures):
+                prm, idx = node_params(states, trans, broadening, t, p, q_t[it], molar_mass, s_min)
+                kept[it, jp] = len(idx)
+                out[it, jp] = numpy_node(prm, nu_first, dnu, n_points, cutoff, molar_mass)
+                if timing is not None:
+                    pairs += count_pairs(prm[0], nu_first, dnu, n_points, cutoff)
+    else:
+        own_ctx, own_handle = ctx is None and handle is None, handle is None
+        if own_ctx:
+            from .device import Context
+            ctx = Context(int(os.environ.get("HELIOS_DEVICE", "0")))
+        try:
+            nodes = [(t, p, q_t[it]) for it, t in enumerate(temps) for p in pressures]
+            if own_handle:
+                handle = ExomolOpacity.of(ctx, states, trans, broadening, n_points, max(1, min(int(nodes_per_launch), len(nodes))),
+                                          len(nodes), True)
+            try:
+                per = handle.nodes_per_launch
+                flat, flat_kept = out.reshape(len(nodes), n_points), kept.reshape(-1)
+                for lo in range(0, len(nodes), handle.n_nodes_max):          # a handle made for fewer nodes takes them in turns
+                    part = nodes[lo:lo + handle.n_nodes_max]
+                    handle.set_nodes([n[0] for n in part], [n[1] for n in part], [n[2] for n in part], molar_mass, cutoff, s_min,
+                                     nu_first, dnu, n_points)
+                    for first in range(0, len(part), per):
+                        n = min(per, len(part) - first)
+                        handle.run_nodes(first, n)
+                        flat[lo + first:lo + first + n] = handle.get("kappa64")
+                        flat_kept[lo + first:lo + first + n] = handle.get("kept")
+                        if timing is not None:
+                            pairs += sum(count_pairs(prm[0], nu_first, dnu, n_points, cutoff) for prm in handle.get("line_params"))
+                    ms += handle.get("timing_ms")
+            finally:
+                if own_handle:
+                    handle.close()
+        finally:
+            if own_ctx:
+                ctx.close()
+    if timing is not None:
+        timing["prepare_ms"] = timing.get("prepare_ms", 0.0) + float(ms[0])
+        timing["sum_ms"] = timing.get("sum_ms", 0.0) + float(ms[1])
+        timing["pairs"] = timing.get("pairs", 0) + pairs
+        timing["kept"] = kept
+    return out
+
+
+# ---- from the line list to the k-table -----------------------------------------------------------------------------------
+class ExomolSlabs(object):
+    """ktable.build_table's slabs from an ExoMol list: one chunk 0 ... numax of `n_points` points, the nodes sorted ascending and
+    de-duplicated as ktable.SpeciesFiles does (node = p + np * t).  On the device the slabs never leave it; `ms` holds the kernel
+    times and `kept` the transitions kept per node once the table is built"""
+
+    def __init__(self, states, trans, broadening, q_table, temps, pressures, numax, dnu, n_points, molar_mass, cutoff, s_min,
+                 nodes_per_launch=4):
+        self.states, self.trans, self.broadening = states, trans, broadening
+        self.numax, self.dnu, self.n_points = int(numax), float(dnu), int(n_points)
+        self.temps, self.press = sorted(set(temps)), sorted(set(pressures))
+        self.molar_mass, self.cutoff, self.s_min = molar_mass, cutoff, float(s_min)
+        self.q_t = [partition_value(q_table, t) for t in self.temps]
+        self.nodes_per_launch = max(1, int(nodes_per_launch))
+        self.handle, self.ms, self.kept = None, np.zeros(2), []
+
+    def axis(self):
+        return 0, self.numax, self.numax / self.n_points           # ktable.SpeciesFiles.resolution() of the file not written
+
+    def _check(self, n_points):
+        if n_points != self.n_points:
+            raise IOError("exomol: the k-table's axis 0 ... %d cm^-1 at %.17g cm^-1 has %d points, the line kernel's grid at "
+                          "-dnu %.17g has %d" % (self.numax, self.numax / self.n_points, n_points, self.dnu, self.n_points))
+
+    def host_slabs(self, pool, n_points):
+        self._check(n_points)
+        for it, t in enumerate(self.temps):
+            for p in self.press:
+                prm, idx = node_params(self.states, self.trans, self.broadening, float(t), p, self.q_t[it], self.molar_mass, self.s_min)
+                self.kept.append(len(idx))
+                yield numpy_node(prm, 0.0, self.dnu, self.n_points, self.cutoff, self.molar_mass).astype(np.float32)
+
+    def feed(self, b, pool, n_points):
+        self._check(n_points)
+        nodes = [(float(t), p, self.q_t[it]) for it, t in enumerate(self.temps) for p in self.press]
+        per = min(self.nodes_per_launch, b.max_tp)
+        self.handle = h = ExomolOpacity.of(b.ctx, self.states, self.trans, self.broadening, self.n_points, per, len(nodes))
+        h.set_nodes([n[0] for n in nodes], [n[1] for n in nodes], [n[2] for n in nodes], self.molar_mass, self.cutoff, self.s_min,
+                    0.0, self.dnu, self.n_points)
+        slabs = h.slab_pointer()
+        for first in range(0, len(nodes), per):
+            n = min(per, len(nodes) - first)
+            h.run_nodes(first, n)
+            b.run_device(slabs, n, first)
+            self.kept.extend(int(k) for k in h.get("kept"))        # after the launch's sort is queued: the counts are the tool's report
+
+    def close(self):
+        h, self.handle = self.handle, None
+        if h is not None:
+            try:
+                self.ms = h.get("timing_ms")
+            finally:
+                h.close()
+
+
+def exomol_ktable(states, trans, broadening, q_table, temps, pressure_codes, numax, dnu, inter, n_gauss, molar_mass=None,
+                  cutoff=DEFAULT_CUTOFF, strength_cutoff=0.0, target=None, backend="device", ctx=None, nodes_per_launch=4,
+                  lds_points=None, timing=None):
+    """the data sets of `<name>_opac_kdistr` and, with `target` = (temperatures, pressures), of `<name>_opac_ip_kdistr`, as
+    ktable.build_species returns them for the directory exomol.py would write for the same arguments -- to the bit -- without the
+    files.  `temps`: integers in K; `pressure_codes`: keys of ktable.pressure_table(); the range is 0 ... numax in one chunk.
+    `timing` receives prepare_ms, sum_ms, kept (per node, node = p + np t) and build_table's entries"""
+    from . import ktable
+    if backend not in ("device", "numpy"):
+        raise ValueError("exomol: backend is device or numpy (got %r)" % (backend,))
+    table = ktable.pressure_table()
+    for c in pressure_codes:
+        if c not in table:
+            raise IOError("exomol: pressure code %r is not in the table (n800 ... p400)" % (c,))
+    for t in temps:
+        if int(t) != t:
+            raise IOError("exomol: the temperature %r is not an integer in K" % (t,))
+    temps, pressures = [int(t) for t in temps], [table[c] for c in pressure_codes]
+    n_points = chunk_limits(0, int(numax), dnu)[0][2]
+    _check_node_inputs(temps, pressures, (0.0, dnu, n_points), molar_mass, cutoff, float(strength_cutoff))
+    if n_points > MAX_TABLE_POINTS:
+        raise IOError("exomol: %d spectral points, the k-table's kernel takes 1 ... %d" % (n_points, MAX_TABLE_POINTS))
+    source = ExomolSlabs(states, trans, broadening, q_table, temps, pressures, numax, dnu, n_points, molar_mass, cutoff,
+                         strength_cutoff, nodes_per_launch)
+    out = ktable.build_table(source, inter, n_gauss, "hip" if backend == "device" else "numpy", ctx, source.nodes_per_launch,
+                             ktable.LDS_POINTS if lds_points is None else lds_points, target, timing)
+    if timing is not None:
+        timing["prepare_ms"], timing["sum_ms"], timing["kept"] = float(source.ms[0]), float(source.ms[1]), list(source.kept)
+    return out
+
+
+# ---- the tool ----------------------------------------------------------------------------------------------------------
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(prog="exomol.py", description="line-by-line opacities of a species from an ExoMol line list")
+    p.add_argument("-name", required=True)
+    p.add_argument("-states", required=True, help="the .states file (.bz2 is read too)")
+    p.add_argument("-trans", required=True, help="one or more .trans files separated by blanks, concatenated in this order")
+    p.add_argument("-partition_function", required=True)
+    p.add_argument("-broadeners", default=None, help="name:fraction:file[:gamma_default:n_default], separated by blanks")
+    p.add_argument("-default_broadening", default="%g %g" % DEFAULT_BROADENING, help="gamma [cm^-1 / bar at 296 K] and n")
+    p.add_argument("-strength_cutoff", type=float, default=0.0, help="S_min in cm / molecule: per node, transitions below it are left out")
+    p.add_argument("-temperatures", required=True, help="integers in K, separated by blanks")
+    p.add_argument("-pressure_codes", required=True, help="HELIOS-K's codes, n800 ... p400, separated by blanks")
+    p.add_argument("-numin", type=int, default=0)
+    p.add_argument("-numax", type=int, required=True)
+    p.add_argument("-dnu", type=float, required=True)
+    p.add_argument("-output_directory", default=None, help="of the files; required without -ktable yes")
+    p.add_argument("-chunk_width", type=int, default=None)
+    p.add_argument("-output_format", default="binary", choices=("binary", "text"))
+    p.add_argument("-molar_mass", type=float, default=None)
+    p.add_argument("-cutoff", type=float, default=DEFAULT_CUTOFF)
+    p.add_argument("-backend", default="device", choices=("device", "numpy"))
+    p.add_argument("-ktable", default="no", choices=("yes", "no"),
+                   help="the species' k-table in place of the files; the options below are ktable.py's")
+    p.add_argument("-grid_format", default="fixed_resolution")
+    p.add_argument("-wavelength_grid", default="50 0.34 200")
+    p.add_argument("-path_to_grid_file", default=None)
+    p.add_argument("-number_of_gaussian_points", type=int, default=20)
+    p.add_argument("-directory_with_individual_files", default="./output/")
+    p.add_argument("-interpolate", default="yes", choices=("yes", "no"))
+    p.add_argument("-temperature_grid", default=None)
+    p.add_argument("-pressure_grid", default=None)
+    p.add_argument("-container", default="h5", choices=("h5", "npz"))
+    p.add_argument("-nodes_per_launch", type=int, default=4)
+    opt = p.parse_args(argv)
+    if opt.ktable == "no" and opt.output_directory is None:
+        p.error("the following arguments are required: -output_directory")
+    return opt
+
+
+def _refuse_with_ktable(opt):
+    if opt.numin != 0:
+        raise IOError("exomol: -ktable yes with -numin %d: the k-table's wavelength axis starts at 0 cm^-1, and ktable.py refuses "
+                      "a directory whose first chunk does not" % opt.numin)
+    if opt.chunk_width is not None:
+        raise IOError("exomol: -ktable yes with -chunk_width %d: the table is built from the one chunk 0 ... numax; a chunk's "
+                      "points are lo + i dnu, which are other bits than 0 + i dnu" % opt.chunk_width)
+    if opt.output_format != "binary":
+        raise IOError("exomol: -ktable yes with -output_format %s: no opacity file is written, the fp32 opacities stay on the "
+                      "device" % opt.output_format)
+    if opt.output_directory is not None:
+        raise IOError("exomol: -ktable yes with -output_directory %s: a call writes the files or the table, not both; the table "
+                      "goes to -directory_with_individual_files" % opt.output_directory)
+    if opt.number_of_gaussian_points < 1:
+        raise IOError("exomol: -number_of_gaussian_points is an integer >= 1")
+    if opt.nodes_per_launch < 1:
+        raise IOError("exomol: -nodes_per_launch is an integer >= 1")
+
+
+def _print_kept(kept, nodes, n_trans):
+    for (t, code), k in zip(nodes, kept):
+        print("exomol: %d K, %s: %d of %d transitions kept" % (t, code, int(k), n_trans))
+
+
+def _main_ktable(opt, states, trans, broadening, q_table, temps, codes, molar_mass, t0):
+    """-ktable yes: `<name>_opac_kdistr` and, with -interpolate yes, `<name>_opac_ip_kdistr`"""
+    from . import ktable
+    inter = ktable.wavelength_grid(opt.grid_format, opt.wavelength_grid.split(), opt.path_to_grid_file)
+    target = ktable.target_grid(opt.temperature_grid, opt.pressure_grid) if opt.interpolate == "yes" else None
+    timing = {}
+    native, table_ip = exomol_ktable(states, trans, broadening, q_table, temps, codes, opt.numax, opt.dnu, inter,
+                                     opt.number_of_gaussian_points, molar_mass, opt.cutoff, opt.strength_cutoff, target, opt.backend,
+                                     None, opt.nodes_per_launch, None, timing)
+    table = ktable.pressure_table()
+    by_pressure = sorted(set(codes), key=lambda c: table[c])
+    _print_kept(timing["kept"], [(t, c) for t in sorted(set(temps)) for c in by_pressure], len(trans["nu0"]))
+    stem = os.path.join(opt.directory_with_individual_files, opt.name)
+    written = [ktable.write_table("%s_opac_kdistr.%s" % (stem, opt.container), native)]
+    if table_ip is not None:
+        written.append(ktable.write_table("%s_opac_ip_kdistr.%s" % (stem, opt.container), table_ip))
+    how = "numpy" if opt.backend == "numpy" else "count to ranges %.1f ms, k_exomol_sum %.1f ms, k_ktable_bins %.1f ms" % (
+        timing["prepare_ms"], timing["sum_ms"], timing["device_ms"][0])
+    print("exomol: %d nodes of %d points into %d bins x %d Gauss points, %s, %.2f s -> %s" % (
+        timing["points"], chunk_limits(0, opt.numax, opt.dnu)[0][2], len(inter) - 1, opt.number_of_gaussian_points, how,
+        time.time() - t0, ", ".join(written)))
+    return written
+
+
+def main(argv=None):
+    """exomol.py: the directory of one species, or with -ktable yes its k-table; returns the paths written"""
+    opt = parse_args(argv)
+    t0 = time.time()
+    temps = parse_temperatures(opt.temperatures)
+    codes, pressures = parse_pressure_codes(opt.pressure_codes)
+    if opt.ktable == "yes":
+        _refuse_with_ktable(opt)
+    chunks = chunk_limits(opt.numin, opt.numax, opt.dnu, opt.chunk_width)
+    if not (np.isfinite(opt.strength_cutoff) and opt.strength_cutoff >= 0):
+        raise IOError("exomol: -strength_cutoff %r is not a finite number >= 0 cm / molecule" % (opt.strength_cutoff,))
+    if not (np.isfinite(opt.cutoff) and opt.cutoff > 0):
+        raise IOError("exomol: -cutoff %r is not > 0 cm^-1" % (opt.cutoff,))
+    molar_mass = opt.molar_mass
+    if molar_mass is None:
+        from .species_data import species_lib
+        if opt.name not in species_lib:
+            raise IOError("exomol: no molar mass: %r is not in species_data.py, give -molar_mass" % (opt.name,))
+        molar_mass = species_lib[opt.name].weight
+    if not (np.isfinite(molar_mass) and molar_mass > 0):
+        raise IOError("exomol: no molar mass: -molar_mass %r is not > 0 g/mol" % (molar_mass,))
+    entries = parse_broadeners(opt.broadeners, parse_default_broadening(opt.default_broadening))
+    q_table = read_partition_function(opt.partition_function)
+    try:
+        for t in temps:
+            partition_value(q_table, t)
+    except ValueError as e:
+        raise IOError(str(e).replace("lines:", "exomol:", 1))
+    states = read_states(opt.states)
+    t_parsed = time.time()
+    trans, skipped = read_transitions(opt.trans.split(), states)
+    n_trans = len(trans["nu0"])
+    print("exomol: %d states of %s (largest J %.17g), %d transitions of %s, %d with nu_0 <= 0 skipped, read and sorted in %.2f s"
+          % (len(states["E"]), opt.states, float(states["J"].max()), n_trans, opt.trans, skipped, time.time() - t_parsed))
+    broadening = broadening_table(entries, int(states["jidx"].max()), print)
+    if opt.ktable == "yes":
+        return _main_ktable(opt, states, trans, broadening, q_table, temps, codes, molar_mass, t0)
+    if opt.numin != 0:
+        print("exomol: -numin %d is not 0: ktable.py will refuse the directory" % opt.numin)
+    directory = os.path.join(str(opt.output_directory), "")
+    os.makedirs(directory, exist_ok=True)
+    ending = ".bin" if opt.output_format == "binary" else ".dat"
+    n_nodes = len(temps) * len(codes)
+    ctx = handle = None
+    timing, written = {}, []
+    try:
+        if opt.backend == "device":
+            from .device import Context
+            ctx = Context(int(os.environ.get("HELIOS_DEVICE", "0")))
+            handle = ExomolOpacity.of(ctx, states, trans, broadening, max(c[2] for c in chunks),
+                                      max(1, min(opt.nodes_per_launch, n_nodes)), n_nodes, True)
+        for lo, hi, n in chunks:
+            kappa = exomol_opacity(states, trans, broadening, q_table, temps, pressures, (float(lo), opt.dnu, n), molar_mass, opt.cutoff,
+                                   opt.strength_cutoff, opt.backend, ctx, opt.nodes_per_launch, handle, timing)
+            if (lo, hi, n) == chunks[0]:                # the cut does not depend on the chunk
+                _print_kept(timing["kept"].reshape(-1), [(t, c) for t in temps for c in codes], n_trans)
+            nu = float(lo) + np.arange(n, dtype=np.float64) * opt.dnu
+            for it, t in enumerate(temps):
+                for jp, code in enumerate(codes):
+                    written.append(directory + file_name(opt.name, lo, hi, t, code, ending))
+                    write_file(written[-1], nu, kappa[it, jp], opt.output_format)
+    finally:
+        if handle is not None:
+            handle.close()
+        if ctx is not None:
+            ctx.close()
+    how = "numpy" if opt.backend == "numpy" else "count to ranges %.1f ms, k_exomol_sum %.1f ms" % (timing["prepare_ms"], timing["sum_ms"])
+    print("exomol: %d nodes x %d chunks, %d pairs, %s, %.2f s -> %d files in %s" % (
+        n_nodes, len(chunks), timing["pairs"], how, time.time() - t0, len(written), directory))
+    return written

@@ -802,6 +802,58 @@ int hx_cia_run_nodes(hx_cia* cia, int first_node, int n_nodes);
 int hx_cia_device_ptr(hx_cia* cia, const char* name, void** out_dptr);
 int hx_cia_get(hx_cia* cia, const char* name, void* out, size_t out_bytes);
 
+/* ---- (13) Opacities from an ExoMol line list: states, transitions and broadening per J'' (csrc/exomol.hip; the contract and the
+ * host side are helios_amd/exomol.py) --------------------------------------------------------------------------------------------
+ * A transition is (upper state, lower state, A); E, g and 2 J live in the state table, nu_0 = E[up] - E[low].  Per (T, P) node:
+ * S = g' A / (8 pi c nu_0^2) exp(-c2 E'' / T) (1 - exp(-c2 nu_0 / T)) / Q(T); a transition is kept iff S >= S_min; of the kept ones,
+ * in list order, nu_0, s = S a / sqrt pi, a = sqrt(ln 2) / alpha_D and y = max(a gamma_L, 1e-8) with gamma_L = P_bar sum_b x_b
+ * gamma_b[2 J''] (296 / T)^n_b[2 J''] go to the node's params; the sum over them is section 11's (lines_sum_tile), so a row has the
+ * bits hx_lines gives for the same four numbers.  k_exomol_count flags and counts per workgroup, k_exomol_scan turns the counts
+ * into offsets (one workgroup per node, no atomics), k_exomol_prepare writes the kept transitions to their positions,
+ * k_exomol_ranges searches per tile the compacted nu_0 for the lines within the cut-off, k_exomol_sum adds.  The node is a grid
+ * dimension of all five, and nothing goes through the host between them.
+ *
+ *   hx_exomol_create          the largest number of states, transitions, broadeners and spectral points, the nodes per launch and
+ *                             in all; want_fp64 != 0: the handle also keeps the rows before rounding.  Resident per launch row:
+ *                             params [4][n_trans_max], the block counts and offsets, the tile ranges, the fp32 slab row.  An
+ *                             allocation the device does not give is refused with its byte count
+ *   hx_exomol_set_states      E [cm^-1], g and jidx = 2 J per state, in the order of the ids.  Refused with the state: a value that is
+ *                             not finite, g < 0, jidx outside 0 ... 2^20, more states than the handle holds.  Transitions,
+ *                             broadening and nodes set before are dropped
+ *   hx_exomol_set_broadening  fraction [n_broadeners] and table [n_broadeners][n_jidx][gamma at 296 K and 1 bar, n]; n_jidx is the
+ *                             states' largest jidx + 1.  Refused with the place: a fraction that is not > 0, gamma < 0, a value that
+ *                             is not finite, another n_jidx, more broadeners than the handle holds
+ *   hx_exomol_set_transitions up, low (0-based) and A [s^-1], sorted by nu_0 (ties in any order the caller fixed); they stay
+ *                             resident, 24 bytes per transition with nu_0.  Refused with HX_E_ARG and the index: an id outside
+ *                             the table, A that is not finite or < 0, nu_0 <= 0, a list that is not sorted, more transitions than
+ *                             the handle holds
+ *   hx_exomol_set_nodes       T, P [dyne cm^-2], Q(T) per node, and what the nodes share: the molar mass [g/mol], the cut-off
+ *                             [cm^-1], S_min [cm / molecule, >= 0], nu of point 0, dnu, the number of points.  A refusal names the
+ *                             node and the value
+ *   hx_exomol_run_nodes       queues the five steps for the nodes first_node ... first_node + n_nodes - 1, n_nodes <=
+ *                             nodes_per_launch, on the context's stream: rows 0 ... n_nodes - 1, row stride n_points.  No copy and
+ *                             no wait; the timers settle in the next call or in hx_exomol_get.  Nodes beyond hx_exomol_set_nodes'
+ *                             count or more than the handle holds per launch are refused before any launch, with the counts
+ *   hx_exomol_device_ptr      "slabs32": the fp32 slab buffer's device address (hx_kt_run_device)
+ *   hx_exomol_get             of the last hx_exomol_run_nodes: "slabs32" (float [rows][n_points]), "kappa64" (double, the same
+ *                             rows before rounding; want_fp64 only), "kept" (int per row), "line_params" (row after row,
+ *                             double[4][kept[row]]: nu_0, s, a, y of the kept transitions), "tile_ranges" (int [rows][tiles][2]:
+ *                             first and one past the last kept transition a tile walks); "timing_ms" (double[2]: ms in count +
+ *                             scan + prepare + ranges and in the sum, summed since hx_exomol_set_nodes)
+ */
+typedef struct hx_exomol hx_exomol;
+int hx_exomol_create(hx_context* ctx, int n_states_max, int n_trans_max, int n_broadeners_max, int n_points_max,
+                     int nodes_per_launch, int n_nodes_max, int want_fp64, hx_exomol** out_exomol);
+int hx_exomol_destroy(hx_exomol* exomol);
+int hx_exomol_set_states(hx_exomol* exomol, int n_states, const double* energy, const double* g, const int* jidx);
+int hx_exomol_set_broadening(hx_exomol* exomol, int n_broadeners, int n_jidx, const double* fraction, const double* table);
+int hx_exomol_set_transitions(hx_exomol* exomol, int n_trans, const int* up, const int* low, const double* a);
+int hx_exomol_set_nodes(hx_exomol* exomol, int n_nodes, const double* temp, const double* press, const double* q_t, double molar_mass,
+                        double cutoff, double s_min, double nu_first, double dnu, int n_points);
+int hx_exomol_run_nodes(hx_exomol* exomol, int first_node, int n_nodes);
+int hx_exomol_device_ptr(hx_exomol* exomol, const char* name, void** out_dptr);
+int hx_exomol_get(hx_exomol* exomol, const char* name, void* out, size_t out_bytes);
+
 #ifdef __cplusplus
 }
 #endif
