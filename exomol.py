@@ -11,8 +11,10 @@ opacities in cm^2 g^-1 at numin + i dnu, which `ktable.py` reads as it reads HEL
 and `<name>_opac_ip_kdistr` without the files; its grid options are ktable.py's.  `-trans` takes one or more files, concatenated
 in the order given; `.bz2` files are read as they are.  `-broadeners` names each broadener's fraction and `.broad` file,
 `-default_broadening "gamma n"` what a J'' without a row takes, `-strength_cutoff S_min` leaves out, per node, the transitions
-weaker than S_min at the node's temperature.  `-numin`, `-chunk_width`, `-output_format`, `-cutoff`, `-molar_mass`, `-backend
-numpy` and `-nodes_per_launch` work as in lines.py.  The pipeline is exomol.py -> ktable.py -> helios.py.
+weaker than S_min at the node's temperature.  `-superline_threshold S_sl` merges, per node, the kept transitions weaker than S_sl
+into one super-line per cell of `-superline_step d` cm^-1 (default: `-dnu`), so that no strength is thrown away.  `-numin`,
+`-chunk_width`, `-output_format`, `-cutoff`, `-molar_mass`, `-backend numpy` and `-nodes_per_launch` work as in lines.py.
+The pipeline is exomol.py -> ktable.py -> helios.py.
 """
 import sys
 

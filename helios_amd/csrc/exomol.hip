@@ -14,6 +14,15 @@
 //   k_exomol_ranges   one thread per tile: lower and upper bound of the tile's reach in the node's compacted nu_0 (ascending,
 //                     there is no pressure shift), widened as lines_tile_ranges widens.
 //   k_exomol_sum      lines_sum_tile (lines_device.h) over the node's own ranges: the bits of k_lines_sum for the same four numbers.
+// With super-lines (hx_exomol_set_superlines) count, scan and prepare give way to:
+//   k_exomol_classify S once per transition into the launch row's strengths; strong (S >= S_min and S >= S_sl) and weak (S_min <=
+//                     S < S_sl) counted per workgroup.
+//   k_exomol_cells    a wavefront per occupied cell of width d: S_c and G_c of the cell's weak transitions, which cells emit a
+//                     super-line (a 64-bit mask per wavefront of cells) and how many per workgroup of EXO_B cells.
+//   k_exomol_scan     as it is, over the strong and weak counts and over the cells' counts.
+//   k_exomol_merge    strong transitions and super-lines to their positions by the key (cell, kind, position).
+// k_exomol_ranges then searches with a reach wider by d -- inside a cell a super-line's nu_c may lie above a strong nu_0 -- and
+// k_exomol_sum is unchanged.
 #include "lines_device.h"
 
 #include <cmath>
@@ -184,6 +193,189 @@ __global__ __launch_bounds__(LINES_THREADS) void k_exomol_sum_fp64(const int2* _
                          slabs32 + (size_t)blockIdx.y * n_points);
 }
 
+// ---- super-lines: weak transitions (S_min <= S < S_sl) merged per cell of width d, cell = floor(nu_0 / d) ---------------------
+// The occupied cells, each cell's first transition and every transition's occupied cell come from the host once per list.
+
+struct ExoCells {
+    int n_cells;
+    const int* first;                  // [n_cells + 1]: the first transition of occupied cell k; first[n_cells] = n
+    const int* id;                     // [n_cells]: floor(nu_0 / d) of the cell's transitions
+    const int* of;                     // [n]: the occupied cell of a transition
+};
+
+__device__ __forceinline__ double exomol_gamma(const ExoLists& in, const ExoBroad& br, int j, const ExoNode& node) {
+    const double pbar = node.press / EXO_BAR;
+    const int jx = in.jidx[in.low[j]];
+    double sum = 0.0;
+    for (int b = 0; b < br.n_b; b++) {
+        const double* row = br.table + ((size_t)b * br.n_j + jx) * 2;
+        sum = sum + br.x[b] * row[0] * pow(LC_TREF / node.temp, row[1]);
+    }
+    return pbar * sum;
+}
+
+// S of every transition once, to strength [node][stride]; per workgroup the number of strong and of weak transitions, to
+// counts [node][2][n_blocks]
+__global__ __launch_bounds__(EXO_B) void k_exomol_classify(int n, size_t stride, ExoLists in, const ExoNode* __restrict__ nodes,
+                                                           double s_min, double s_sl, int n_blocks, double* __restrict__ strength,
+                                                           int* __restrict__ counts) {
+    __shared__ int s_w[2][EXO_WAVES];
+    const int j = blockIdx.x * EXO_B + threadIdx.x;
+    const ExoNode node = nodes[blockIdx.y];
+    int strong = 0, weak = 0;
+    if (j < n) {
+        const double s = exomol_strength(in, j, node.temp, node.q_t);
+        strength[(size_t)blockIdx.y * stride + j] = s;
+        const int keep = s >= s_min;
+        strong = keep && s >= s_sl;
+        weak = keep && !strong;
+    }
+    const unsigned long long ms = __ballot(strong), mw = __ballot(weak);
+    if ((threadIdx.x & 63) == 0) {
+        s_w[0][threadIdx.x >> 6] = __popcll(ms);
+        s_w[1][threadIdx.x >> 6] = __popcll(mw);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        int c = 0;
+#pragma unroll
+        for (int w = 0; w < EXO_WAVES; w++) c += s_w[threadIdx.x][w];
+        counts[((size_t)blockIdx.y * 2 + threadIdx.x) * n_blocks + blockIdx.x] = c;
+    }
+}
+
+// A wavefront per occupied cell, 64 cells one after the other per wavefront, so a workgroup covers EXO_B cells: the lanes stride
+// through the cell's run of the list, each adds its weak transitions' S and S gamma in list order, and a butterfly of shuffles
+// adds the 64 partial sums -- a fixed order, whatever else the launch holds.  Lane i keeps cell i's sums; the wavefront's
+// ballot of "holds a weak transition" is the emit mask, its population the workgroup's count.
+// sums [node][2][n_cells]: S_c, G_c; masks [node][4 n_cblocks]; counts [node][n_cblocks]
+__global__ __launch_bounds__(EXO_B) void k_exomol_cells(ExoCells cells, size_t stride, ExoLists in, ExoBroad br,
+                                                        const ExoNode* __restrict__ nodes, double s_min, double s_sl,
+                                                        const double* __restrict__ strength, int n_cblocks,
+                                                        double* __restrict__ sums, unsigned long long* __restrict__ masks,
+                                                        int* __restrict__ counts) {
+    __shared__ int s_w[EXO_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const ExoNode node = nodes[blockIdx.y];
+    const double* s_of = strength + (size_t)blockIdx.y * stride;
+    const int base = blockIdx.x * EXO_B + wave * 64;
+    double my_s = 0.0, my_g = 0.0;
+    int my_emit = 0;
+    for (int i = 0; i < 64; i++) {
+        const int k = base + i;
+        if (k >= cells.n_cells) break;                           // the same for the whole wavefront
+        const int first = cells.first[k], last = cells.first[k + 1];
+        double ps = 0.0, pg = 0.0;
+        int any = 0;
+        for (int j = first + lane; j < last; j += 64) {
+            const double s = s_of[j];
+            if (s >= s_min && !(s >= s_sl)) {
+                ps = ps + s;
+                pg = pg + s * exomol_gamma(in, br, j, node);
+                any = 1;
+            }
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            ps = ps + __shfl_xor(ps, d);
+            pg = pg + __shfl_xor(pg, d);
+        }
+        const int emit = __ballot(any) != 0ull;
+        if (lane == i) {
+            my_s = ps;
+            my_g = pg;
+            my_emit = emit;
+        }
+    }
+    if (base + lane < cells.n_cells) {
+        double* out = sums + (size_t)blockIdx.y * 2 * cells.n_cells;
+        out[base + lane] = my_s;
+        out[cells.n_cells + base + lane] = my_g;
+    }
+    const unsigned long long m = __ballot(my_emit);
+    if (lane == 0) {
+        masks[((size_t)blockIdx.y * n_cblocks + blockIdx.x) * EXO_WAVES + wave] = m;
+        s_w[wave] = __popcll(m);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int c = 0;
+#pragma unroll
+        for (int w = 0; w < EXO_WAVES; w++) c += s_w[w];
+        counts[(size_t)blockIdx.y * n_cblocks + blockIdx.x] = c;
+    }
+}
+
+// The node's list by the key (cell, kind, position): a strong transition goes to (strong transitions before it) + (super-lines
+// of the cells up to its own); a cell's super-line goes to (strong transitions before the cell's first transition) +
+// (super-lines of the cells before it), and the thread of that first transition writes it.  totals [node][2]: strong, weak, and
+// n_super [node] are k_exomol_scan's; length [node] receives strong + super-lines, the list's length.
+__global__ __launch_bounds__(EXO_B) void k_exomol_merge(int n, size_t stride, ExoLists in, ExoBroad br, ExoCells cells,
+                                                        const ExoNode* __restrict__ nodes, double s_min, double s_sl, double step,
+                                                        double molar_mass, const double* __restrict__ strength, int n_blocks,
+                                                        const int* __restrict__ offsets, int n_cblocks,
+                                                        const double* __restrict__ sums,
+                                                        const unsigned long long* __restrict__ masks,
+                                                        const int* __restrict__ cell_offsets, const int* __restrict__ totals,
+                                                        const int* __restrict__ n_super, int* __restrict__ length,
+                                                        double* __restrict__ params) {
+    __shared__ int s_w[EXO_WAVES];
+    const int j = blockIdx.x * EXO_B + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const ExoNode node = nodes[blockIdx.y];
+    if (j == 0) length[blockIdx.y] = totals[blockIdx.y * 2] + n_super[blockIdx.y];
+    double s = 0.0;
+    int strong = 0;
+    if (j < n) {
+        s = strength[(size_t)blockIdx.y * stride + j];
+        strong = s >= s_min && s >= s_sl;
+    }
+    const unsigned long long m = __ballot(strong);
+    if (lane == 0) s_w[wave] = __popcll(m);
+    __syncthreads();
+    if (j >= n) return;
+    const int k = cells.of[j];
+    const bool opens = cells.first[k] == j;
+    if (!strong && !opens) return;
+    int before = offsets[(size_t)blockIdx.y * 2 * n_blocks + blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
+#pragma unroll
+    for (int w = 0; w < EXO_WAVES; w++)
+        if (w < wave) before += s_w[w];
+    const unsigned long long* mk = masks + (size_t)blockIdx.y * n_cblocks * EXO_WAVES;
+    const int kw = k / 64, kb = k / EXO_B;                       // k_exomol_cells: a mask word per 64 cells, a count per EXO_B
+    int supers = cell_offsets[(size_t)blockIdx.y * n_cblocks + kb];
+    for (int w = kb * EXO_WAVES; w < kw; w++) supers += __popcll(mk[w]);
+    const unsigned long long mine = mk[kw];
+    supers += __popcll(mine & ((1ull << (k & 63)) - 1ull));
+    const int emits = (int)((mine >> (k & 63)) & 1ull);
+    const double doppler = sqrt(2.0 * LC_LN2 * LC_NA * LC_KB * node.temp / molar_mass);
+    double* p = params + (size_t)blockIdx.y * 4 * stride;
+    if (opens && emits) {
+        const double* sc = sums + (size_t)blockIdx.y * 2 * cells.n_cells;
+        const double s_c = sc[k], g_c = sc[cells.n_cells + k];
+        const double gamma = s_c > 0.0 ? g_c / s_c : 0.0;
+        const double v = ((double)cells.id[k] + 0.5) * step;
+        const double alpha = (v / LC_C) * doppler;
+        const double a = sqrt(LC_LN2) / alpha;
+        const int pos = before + supers;
+        p[pos] = v;
+        p[stride + pos] = s_c * a * LC_INV_SQRT_PI;
+        p[2 * stride + pos] = a;
+        p[3 * stride + pos] = fmax(a * gamma, LC_YMIN);
+    }
+    if (strong) {
+        const double gamma = exomol_gamma(in, br, j, node);
+        const double v = in.nu0[j];
+        const double alpha = (v / LC_C) * doppler;
+        const double a = sqrt(LC_LN2) / alpha;
+        const int pos = before + supers + emits;
+        p[pos] = v;
+        p[stride + pos] = s * a * LC_INV_SQRT_PI;
+        p[2 * stride + pos] = a;
+        p[3 * stride + pos] = fmax(a * gamma, LC_YMIN);
+    }
+}
+
 }  // namespace
 
 struct hx_exomol {
@@ -211,7 +403,37 @@ struct hx_exomol {
     hx_owned owned;
     hx_stream_timer t_prepare, t_sum;
     double timing[2];                  // ms in count + scan + prepare + ranges and in the sum since set_nodes
+    // super-lines (hx_exomol_set_superlines); nothing below is allocated while they are off
+    double sl_threshold, sl_step;      // sl_step = 0: off
+    int n_cells, n_cblocks;            // occupied cells, and workgroups of EXO_B of them
+    int *cell_first, *cell_id;         // [n_cells + 1], [n_cells]
+    int* cell_of;                      // trans_max
+    double* strength;                  // [per_launch][trans_max]
+    int *sl_counts, *sl_offsets;       // [per_launch][2][blocks_max]: strong, weak
+    int* sl_totals;                    // [per_launch][2]
+    double* cell_sums;                 // [per_launch][2][n_cells]: S_c, G_c
+    unsigned long long* cell_masks;    // [per_launch][4 n_cblocks]
+    int *cell_counts, *cell_offsets;   // [per_launch][n_cblocks]
+    int* n_super;                      // per_launch
+    int* list_len;                     // per_launch: strong + super-lines
+    int cells_held;                    // the cells the per-cell arrays were allocated for
 };
+
+// (strong, weak, super-lines) of the rows of the last launch
+static int exomol_superline_counts(hx_exomol* h, std::vector<int>& out) {
+    const size_t rows = (size_t)h->rows_run;
+    std::vector<int> sw(2 * rows), ns(rows);
+    int rc = hx_d2h(h->ctx, sw.data(), h->sl_totals, sw.size() * 4);
+    if (!rc) rc = hx_d2h(h->ctx, ns.data(), h->n_super, ns.size() * 4);
+    if (rc) return rc;
+    out.resize(3 * rows);
+    for (size_t r = 0; r < rows; r++) {
+        out[3 * r] = sw[2 * r];
+        out[3 * r + 1] = sw[2 * r + 1];
+        out[3 * r + 2] = ns[r];
+    }
+    return 0;
+}
 
 static int exomol_settle(hx_exomol* h) {
     int rc = hx_stream_timer_settle(h->ctx, h->t_prepare, &h->timing[0]);
@@ -297,6 +519,7 @@ int hx_exomol_set_states(hx_exomol* h, int n_states, const double* energy, const
         max_jidx = std::max(max_jidx, jidx[k]);
     }
     h->n_states = h->n_trans = h->n_broad = h->n_nodes = h->rows_run = 0;      // the lists and the table were another table's
+    h->sl_step = h->sl_threshold = 0.0;
     int rc = hx_h2d(ctx, h->e, energy, (size_t)n_states * 8);
     if (!rc) rc = hx_h2d(ctx, h->g, g, (size_t)n_states * 8);
     if (!rc) rc = hx_h2d(ctx, h->jidx, jidx, (size_t)n_states * 4);
@@ -371,6 +594,7 @@ int hx_exomol_set_transitions(hx_exomol* h, int n_trans, const int* up, const in
                            "list is sorted", j, nu0[j], j - 1, nu0[j - 1]);
     }
     h->n_trans = h->n_nodes = h->rows_run = 0;
+    h->sl_step = h->sl_threshold = 0.0;                          // the cells were the other list's
     int rc = hx_h2d(ctx, h->up, up, (size_t)n_trans * 4);
     if (!rc) rc = hx_h2d(ctx, h->low, low, (size_t)n_trans * 4);
     if (!rc) rc = hx_h2d(ctx, h->a, a, (size_t)n_trans * 8);
@@ -378,6 +602,93 @@ int hx_exomol_set_transitions(hx_exomol* h, int n_trans, const int* up, const in
     if (rc) return rc;
     h->n_trans = n_trans;
     h->n_blocks = hx_cdiv(n_trans, EXO_B);
+    return 0;
+}
+
+int hx_exomol_set_superlines(hx_exomol* h, double s_sl, double step) {
+    if (!h) return HX_E_ARG;
+    hx_context* ctx = h->ctx;
+    if (h->n_trans < 1) return hx_fail(ctx, HX_E_STATE, "hx_exomol_set_superlines: no transitions (hx_exomol_set_transitions)");
+    // from here on every return, a refusal included, leaves super-lines off until the call has succeeded, and the nodes dropped:
+    // their tile reach was the other step's
+    h->n_nodes = h->rows_run = 0;
+    h->sl_step = h->sl_threshold = 0.0;
+    if (!(s_sl >= 0.0)) return hx_fail(ctx, HX_E_ARG, "hx_exomol_set_superlines: S_sl = %g is not a number >= 0", s_sl);
+    if (!(step >= 0.0) || !std::isfinite(step))
+        return hx_fail(ctx, HX_E_ARG, "hx_exomol_set_superlines: the step %g is not a finite number > 0, or 0 for none", step);
+    if (step == 0.0) return 0;
+    const int n = h->n_trans;
+    std::vector<double> nu0((size_t)n);
+    int rc = hx_d2h(ctx, nu0.data(), h->nu0, nu0.size() * 8);    // waits for the stream: queued launches have read their cells
+    if (rc) return rc;
+    if (!(nu0[n - 1] / step < 2147483648.0))
+        return hx_fail(ctx, HX_E_ARG, "hx_exomol_set_superlines: the step %.17g puts the largest nu_0 = %.17g into cell %.17g, cells "
+                       "are numbered below 2^31", step, nu0[n - 1], std::floor(nu0[n - 1] / step));
+    std::vector<int> first, id, of((size_t)n);
+    for (int j = 0; j < n; j++) {
+        const int c = (int)std::floor(nu0[j] / step);
+        if (id.empty() || c != id.back()) {
+            id.push_back(c);
+            first.push_back(j);
+        }
+        of[j] = (int)id.size() - 1;
+    }
+    first.push_back(n);
+    const int n_cells = (int)id.size(), ncb = hx_cdiv(n_cells, EXO_B);
+    const size_t nt = (size_t)h->trans_max, npl = (size_t)h->per_launch, nb = (size_t)h->blocks_max;
+    if (!h->cell_of) {                                           // what does not depend on the number of cells: once per handle
+        const struct { const char* what; size_t bytes; void** where; } want[] = {
+            {"cell of every transition", nt * 4, (void**)&h->cell_of}, {"strengths", npl * nt * 8, (void**)&h->strength},
+            {"class counts", npl * 2 * nb * 4, (void**)&h->sl_counts}, {"class offsets", npl * 2 * nb * 4, (void**)&h->sl_offsets},
+            {"class totals", npl * 2 * 4, (void**)&h->sl_totals}, {"super-line counts", npl * 4, (void**)&h->n_super},
+            {"list lengths", npl * 4, (void**)&h->list_len}};
+        for (const auto& w : want)
+            if (!rc && hx_owned_alloc(ctx, h->owned, w.bytes, w.where)) {
+                (void)hipGetLastError();
+                rc = hx_fail(ctx, HX_E_ARG, "hx_exomol_set_superlines: the %s of %d transitions and %d nodes per launch need %zu bytes, "
+                             "which the device does not give", w.what, h->trans_max, h->per_launch, w.bytes);
+            }
+        if (rc) {                                                // all or nothing
+            void* got[] = {h->cell_of, h->strength, h->sl_counts, h->sl_offsets, h->sl_totals, h->n_super, h->list_len};
+            for (void* p : got) (void)hx_owned_free(ctx, h->owned, p);
+            h->cell_of = nullptr; h->strength = nullptr; h->sl_counts = h->sl_offsets = h->sl_totals = h->n_super = h->list_len = nullptr;
+            return rc;
+        }
+    }
+    if (n_cells > h->cells_held) {
+        void* old[] = {h->cell_first, h->cell_id, h->cell_sums, h->cell_masks, h->cell_counts, h->cell_offsets};
+        for (void* p : old) (void)hx_owned_free(ctx, h->owned, p);
+        h->cell_first = h->cell_id = h->cell_counts = h->cell_offsets = nullptr;
+        h->cell_sums = nullptr; h->cell_masks = nullptr;
+        h->cells_held = 0;
+        const size_t nc = (size_t)n_cells, nbc = (size_t)ncb;
+        const struct { size_t bytes; void** where; } want[] = {
+            {(nc + 1) * 4, (void**)&h->cell_first}, {nc * 4, (void**)&h->cell_id}, {npl * 2 * nc * 8, (void**)&h->cell_sums},
+            {npl * nbc * EXO_WAVES * 8, (void**)&h->cell_masks}, {npl * nbc * 4, (void**)&h->cell_counts},
+            {npl * nbc * 4, (void**)&h->cell_offsets}};
+        for (const auto& w : want)
+            if (!rc && hx_owned_alloc(ctx, h->owned, w.bytes, w.where)) {
+                (void)hipGetLastError();
+                rc = hx_fail(ctx, HX_E_ARG, "hx_exomol_set_superlines: the arrays of %d occupied cells and %d nodes per launch need "
+                             "%zu bytes more, which the device does not give", n_cells, h->per_launch, w.bytes);
+            }
+        if (rc) {
+            void* got[] = {h->cell_first, h->cell_id, h->cell_sums, h->cell_masks, h->cell_counts, h->cell_offsets};
+            for (void* p : got) (void)hx_owned_free(ctx, h->owned, p);
+            h->cell_first = h->cell_id = h->cell_counts = h->cell_offsets = nullptr;
+            h->cell_sums = nullptr; h->cell_masks = nullptr;
+            return rc;
+        }
+        h->cells_held = n_cells;
+    }
+    rc = hx_h2d(ctx, h->cell_first, first.data(), first.size() * 4);
+    if (!rc) rc = hx_h2d(ctx, h->cell_id, id.data(), id.size() * 4);
+    if (!rc) rc = hx_h2d(ctx, h->cell_of, of.data(), of.size() * 4);
+    if (rc) return rc;
+    h->n_cells = n_cells;
+    h->n_cblocks = ncb;
+    h->sl_threshold = s_sl;
+    h->sl_step = step;
     return 0;
 }
 
@@ -399,6 +710,9 @@ int hx_exomol_set_nodes(hx_exomol* h, int n_nodes, const double* temp, const dou
     if (!(s_min >= 0.0) || !std::isfinite(s_min))
         return hx_fail(ctx, HX_E_ARG, "hx_exomol_set_nodes: S_min = %g is not a finite number >= 0", s_min);
     if (!std::isfinite(nu_first)) return hx_fail(ctx, HX_E_ARG, "hx_exomol_set_nodes: nu of point 0 = %g is not finite", nu_first);
+    if (h->sl_step > cutoff)
+        return hx_fail(ctx, HX_E_ARG, "hx_exomol_set_nodes: the super-line step %.17g is greater than the cut-off %.17g", h->sl_step,
+                       cutoff);
     std::vector<ExoNode> nodes((size_t)n_nodes);
     for (int k = 0; k < n_nodes; k++) {
         const struct { const char* name; double v; } node[] = {{"T", temp[k]}, {"P", press[k]}, {"Q(T)", q_t[k]}};
@@ -412,7 +726,8 @@ int hx_exomol_set_nodes(hx_exomol* h, int n_nodes, const double* temp, const dou
     // hx_h2d waits for the stream: node runs still queued have read the records they were queued with
     if (!rc) rc = hx_h2d(ctx, h->nodes, nodes.data(), nodes.size() * sizeof(ExoNode));
     if (rc) return rc;
-    const double common[6] = {molar_mass, cutoff, s_min, nu_first, dnu, cutoff * (1.0 + 1e-12) + 1e-9};
+    // in super-line mode nu ascends only from cell to cell: a tile's reach is wider by the step
+    const double common[6] = {molar_mass, cutoff, s_min, nu_first, dnu, cutoff * (1.0 + 1e-12) + 1e-9 + h->sl_step};
     memcpy(h->common, common, sizeof common);
     h->n_nodes = n_nodes;
     h->n_points = n_points;
@@ -440,16 +755,41 @@ int hx_exomol_run_nodes(hx_exomol* h, int first_node, int n_nodes) {
     const ExoBroad br = {h->n_broad, h->n_jidx, h->bx, h->btable};
     const ExoNode* nodes = h->nodes + first_node;
     const int nb = h->n_blocks, nt = h->n_tiles;
-    k_exomol_count<<<dim3(nb, n_nodes), EXO_B, 0, ctx->stream>>>(h->n_trans, in, nodes, s_min, nb, h->counts);
-    HX_LAUNCH_CHECK(ctx);
-    k_exomol_scan<<<n_nodes, EXO_B, 0, ctx->stream>>>(nb, h->counts, h->offsets, h->kept);
-    HX_LAUNCH_CHECK(ctx);
-    k_exomol_prepare<<<dim3(nb, n_nodes), EXO_B, 0, ctx->stream>>>(h->n_trans, stride, in, br, nodes, s_min, molar_mass, nb, h->offsets,
-                                                                  h->params);
-    HX_LAUNCH_CHECK(ctx);
-    k_exomol_ranges<<<dim3(hx_cdiv(nt, 256), n_nodes), 256, 0, ctx->stream>>>(nt, h->n_points, nu_first, dnu, h->common[5], stride,
-                                                                             h->params, h->kept, h->ranges);
-    HX_LAUNCH_CHECK(ctx);
+    if (h->sl_step > 0.0) {
+        const ExoCells cells = {h->n_cells, h->cell_first, h->cell_id, h->cell_of};
+        const int ncb = h->n_cblocks;
+        k_exomol_classify<<<dim3(nb, n_nodes), EXO_B, 0, ctx->stream>>>(h->n_trans, stride, in, nodes, s_min, h->sl_threshold, nb,
+                                                                       h->strength, h->sl_counts);
+        HX_LAUNCH_CHECK(ctx);
+        k_exomol_cells<<<dim3(ncb, n_nodes), EXO_B, 0, ctx->stream>>>(cells, stride, in, br, nodes, s_min, h->sl_threshold, h->strength,
+                                                                     ncb, h->cell_sums, h->cell_masks, h->cell_counts);
+        HX_LAUNCH_CHECK(ctx);
+        // rows (node, strong) and (node, weak): of the weak rows only the total is read, for "kept" and "superline_counts"; their
+        // offsets come with it from the one launch and nothing reads them
+        k_exomol_scan<<<2 * n_nodes, EXO_B, 0, ctx->stream>>>(nb, h->sl_counts, h->sl_offsets, h->sl_totals);
+        HX_LAUNCH_CHECK(ctx);
+        k_exomol_scan<<<n_nodes, EXO_B, 0, ctx->stream>>>(ncb, h->cell_counts, h->cell_offsets, h->n_super);
+        HX_LAUNCH_CHECK(ctx);
+        k_exomol_merge<<<dim3(nb, n_nodes), EXO_B, 0, ctx->stream>>>(h->n_trans, stride, in, br, cells, nodes, s_min, h->sl_threshold,
+                                                                     h->sl_step, molar_mass, h->strength, nb, h->sl_offsets, ncb,
+                                                                     h->cell_sums, h->cell_masks, h->cell_offsets, h->sl_totals,
+                                                                     h->n_super, h->list_len, h->params);
+        HX_LAUNCH_CHECK(ctx);
+        k_exomol_ranges<<<dim3(hx_cdiv(nt, 256), n_nodes), 256, 0, ctx->stream>>>(nt, h->n_points, nu_first, dnu, h->common[5], stride,
+                                                                                 h->params, h->list_len, h->ranges);
+        HX_LAUNCH_CHECK(ctx);
+    } else {
+        k_exomol_count<<<dim3(nb, n_nodes), EXO_B, 0, ctx->stream>>>(h->n_trans, in, nodes, s_min, nb, h->counts);
+        HX_LAUNCH_CHECK(ctx);
+        k_exomol_scan<<<n_nodes, EXO_B, 0, ctx->stream>>>(nb, h->counts, h->offsets, h->kept);
+        HX_LAUNCH_CHECK(ctx);
+        k_exomol_prepare<<<dim3(nb, n_nodes), EXO_B, 0, ctx->stream>>>(h->n_trans, stride, in, br, nodes, s_min, molar_mass, nb,
+                                                                      h->offsets, h->params);
+        HX_LAUNCH_CHECK(ctx);
+        k_exomol_ranges<<<dim3(hx_cdiv(nt, 256), n_nodes), 256, 0, ctx->stream>>>(nt, h->n_points, nu_first, dnu, h->common[5], stride,
+                                                                                 h->params, h->kept, h->ranges);
+        HX_LAUNCH_CHECK(ctx);
+    }
     rc = hx_stream_timer_stop(ctx, h->t_prepare);
     if (!rc) rc = hx_stream_timer_start(ctx, h->t_sum);
     if (rc) return rc;
@@ -479,10 +819,28 @@ int hx_exomol_get(hx_exomol* h, const char* name, void* out, size_t out_bytes) {
     int rc = exomol_settle(h);
     if (rc) return rc;
     const char* no_run = h->rows_run ? nullptr : "no nodes have been run (hx_exomol_run_nodes)";
+    const bool superlines = h->sl_step > 0.0;
+    if (superlines && (!strcmp(name, "kept") || !strcmp(name, "superline_counts"))) {
+        if (no_run) return hx_fail(ctx, HX_E_STATE, "hx_exomol_get: %s", no_run);
+        const bool three = name[0] == 's';
+        const size_t want = (size_t)h->rows_run * (three ? 3 : 1) * 4;
+        if (out_bytes != want) return hx_fail(ctx, HX_E_ARG, "hx_exomol_get(%s): %zu bytes expected, got %zu", name, want, out_bytes);
+        std::vector<int> counts;
+        rc = exomol_superline_counts(h, counts);
+        if (rc) return rc;
+        int* dst = (int*)out;
+        for (int r = 0; r < h->rows_run; r++) {
+            if (three) memcpy(dst + 3 * r, &counts[3 * r], 12);
+            else dst[r] = counts[3 * r] + counts[3 * r + 1];     // kept: strong + weak
+        }
+        return 0;
+    }
+    if (!strcmp(name, "superline_counts"))
+        return hx_fail(ctx, HX_E_STATE, "hx_exomol_get: no super-lines are set (hx_exomol_set_superlines)");
     if (!strcmp(name, "line_params")) {                          // row after row, [4][kept[row]] out of [4][trans_max]
         if (no_run) return hx_fail(ctx, HX_E_STATE, "hx_exomol_get: %s", no_run);
         std::vector<int> kept((size_t)h->rows_run);
-        rc = hx_d2h(ctx, kept.data(), h->kept, kept.size() * 4);
+        rc = hx_d2h(ctx, kept.data(), superlines ? h->list_len : h->kept, kept.size() * 4);    // the list's length per row
         if (rc) return rc;
         size_t total = 0;
         for (int k : kept) total += (size_t)k;

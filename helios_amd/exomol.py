@@ -37,13 +37,40 @@ The sum is lines.py's, unchanged, over the node's list: the inclusive cut-off |n
 kappa = sigma N_A / M rounded once to fp32 when written; lines_k and lines_sum_tile on the device, lines.voigt_k and
 lines.numpy_node on the host.  The tool prints per node how many transitions were kept.
 
-Not modelled: `.broad` codes other than `a0`, a pressure shift, a cut relative to the strongest line, super-lines, several
+Super-lines (`-superline_threshold S_sl`, `-superline_step d`; off unless given).  The strength cut buys time by deleting opacity;
+super-lines keep it: strong transitions keep their own profile, the weak ones are added up per small wavenumber cell at the
+node's temperature and each cell gets one profile.  fp64, nothing contracted, every statement left to right, as above.  S_sl
+[cm / molecule] and the cell width d [cm^-1] are shared by all nodes of a call.  Per node, S, gamma, a as above:
+    classes     dropped iff S < S_min (unchanged); strong iff S >= S_min and S >= S_sl; weak otherwise: S_min <= S < S_sl.
+    cell        c = floor(nu_0 / d), an integer from one fp64 division.  The cell grid starts at 0 cm^-1 whatever -numin or the
+                chunk is, so a chunked run forms the super-lines of a one-chunk run.  The list is sorted by nu_0: a cell is a
+                contiguous run of it, and cells do not depend on T (the device receives the occupied cells once per list).
+    super-line  one per node and cell that holds at least one weak transition at that node:
+                S_c = sum S_j and G_c = sum S_j * gamma_j over the cell's weak transitions in list order,
+                gamma_c = G_c / S_c if S_c > 0, else 0;  nu_c = (c + 0.5) * d;  alpha, a by the statements above from nu_c;
+                y = max(a * gamma_c, 1e-8);  s = S_c * a * (1 / sqrt pi).
+    the list    the strong transitions plus the super-lines, ordered by the integer key (cell, kind, position in the list), the
+                super-line (kind 0) before its cell's strong transitions (kind 1).  Every spectral point adds its terms in
+                ascending order of that list; the sum, the inclusive cut-off, K's regions and the fp32 rounding are unchanged.
+In this list nu ascends only from cell to cell: inside a cell nu_c may lie above a strong nu_0, by less than d.  The tile ranges
+are therefore widened by d on top of RANGE_WIDEN; a bisection over a list whose disorder is confined to a cell then still returns
+a superset of what the per-point test passes, and that test decides every term, as before.  (lines.numpy_node and count_pairs
+take each line's window from its own nu and assume no order.)  On the device the sums S_c, G_c are added lane-strided and by a
+butterfly, not one after the other: the super-lines' numbers are held to the tolerance of the tests, not to bits; they are the
+same bits in every run and in every launch.  With S_sl <= S_min no transition is weak and the result is the plain one bit for
+bit; S_sl = +inf makes every kept transition weak.  Refused, with the value: S_sl that is NaN or < 0; d that is not a finite
+number > 0; d greater than the cut-off; nu_0,max / d at or above 2^31; `-superline_step` without `-superline_threshold`.  The tool
+prints per node the strong, the weak and the super-lines next to the kept transitions.
+
+Not modelled: `.broad` codes other than `a0`, a pressure shift, a cut relative to the strongest line, several
 isotopologues per call; and what lines.py does not model either (no renormalisation for the cut wings, no sub-Lorentzian factor).
 
 `backend="device"`: per launch of up to `-nodes_per_launch` nodes, the node a grid dimension: k_exomol_count flags S >= S_min and
 counts per workgroup of COMPACT_BLOCK transitions, k_exomol_scan turns the counts into offsets, k_exomol_prepare writes nu_0, s, a,
 y of the kept transitions to their positions, k_exomol_ranges finds per tile of TILE_POINTS points the kept transitions within the
-cut-off by bisection in the compacted nu_0, k_exomol_sum is lines_sum_tile.  `backend="numpy"` computes the same contract on the
+cut-off by bisection in the compacted nu_0, k_exomol_sum is lines_sum_tile.  With super-lines k_exomol_classify (S once per
+transition, strong and weak counts), k_exomol_cells (a wavefront per occupied cell), two scans and k_exomol_merge take the place
+of count, scan and prepare.  `backend="numpy"` computes the same contract on the
 CPU: gather, strengths, cut, lines.numpy_node; the checker of the device path, and what a machine without a GPU gets.
 
 `-ktable yes`: as `lines.py -ktable yes`, word for word.  One chunk 0 ... numax; the kernel steps with the `-dnu` given and the
@@ -71,7 +98,8 @@ BAR = 1.0e6                           # dyne cm^-2
 DEFAULT_BROADENING = (0.07, 0.5)      # gamma [cm^-1 bar^-1 at 296 K], n
 COMPACT_BLOCK = 256                   # csrc/exomol.hip: EXO_B, the count kernel's block (tests/test_gpu_exomol.py derives its sizes)
 JIDX_MAX = 1 << 20
-RANGE_WIDEN = (1e-12, 1e-9)           # lines_tile_ranges: reach * (1 + 1e-12) + 1e-9
+RANGE_WIDEN = (1e-12, 1e-9)           # lines_tile_ranges: reach * (1 + 1e-12) + 1e-9 (super-lines: + d)
+CELL_LIMIT = 2.0 ** 31                # cells are numbered by an int
 
 
 # ---- the inputs --------------------------------------------------------------------------------------------------------
@@ -282,8 +310,13 @@ def strengths(states, trans, temp, q_t):
         return pre * np.exp(-c2 * states["E"][trans["low"]] / temp) * (-np.expm1(-c2 * nu0 / temp)) / q_t
 
 
-def node_params(states, trans, broadening, temp, press, q_t, molar_mass, s_min=0.0):
-    """([4][kept]: nu_0, s = S a / sqrt pi, a, y of the node's kept transitions in list order; their indices in the list)"""
+def node_params(states, trans, broadening, temp, press, q_t, molar_mass, s_min=0.0, superline_threshold=None, superline_step=None):
+    """([4][kept]: nu_0, s = S a / sqrt pi, a, y of the node's kept transitions in list order; their indices in the list).  With
+    super-lines the four numbers are those of the node's list (superline_node), the indices still those of the kept transitions"""
+    if superline_threshold is not None or superline_step is not None:
+        sl = check_superlines(superline_threshold, superline_step, np.inf, trans["nu0"][-1])
+        node = superline_node(states, trans, broadening, temp, press, q_t, molar_mass, s_min, sl[0], sl[1])
+        return node["params"], node["kept"]
     strength = strengths(states, trans, temp, q_t)
     kept = np.nonzero(strength >= s_min)[0]
     x, table = broadening
@@ -298,6 +331,98 @@ def node_params(states, trans, broadening, temp, press, q_t, molar_mass, s_min=0
     return np.stack([nu0, strength[kept] * a * INV_SQRT_PI, a, y]), kept
 
 
+# ---- super-lines ---------------------------------------------------------------------------------------------------------
+def check_superlines(superline_threshold, superline_step, cutoff, nu0_max, default_step=None):
+    """(S_sl, d) as floats, or None where super-lines are off (both arguments None); every refusal names the value"""
+    if superline_threshold is None:
+        if superline_step is not None:
+            raise ValueError("exomol: a super-line step (%r) without a super-line threshold" % (superline_step,))
+        return None
+    s_sl = float(superline_threshold)
+    if superline_step is None and default_step is None:
+        raise ValueError("exomol: the super-line threshold %r without a super-line step" % (s_sl,))
+    step = float(default_step if superline_step is None else superline_step)
+    if np.isnan(s_sl) or s_sl < 0:
+        raise ValueError("exomol: the super-line threshold %r is not a number >= 0 cm / molecule" % (s_sl,))
+    if not (np.isfinite(step) and step > 0):
+        raise ValueError("exomol: the super-line step %r is not a finite number > 0 cm^-1" % (step,))
+    if step > cutoff:
+        raise ValueError("exomol: the super-line step %r is greater than the cut-off %r cm^-1" % (step, float(cutoff)))
+    if not float(nu0_max) / step < CELL_LIMIT:
+        raise ValueError("exomol: the super-line step %r puts the largest nu_0 = %r into cell %r, cells are numbered below 2^31"
+                         % (step, float(nu0_max), float(np.floor(float(nu0_max) / step))))
+    return s_sl, step
+
+
+def _gamma(states, trans, broadening, index, temp, press):
+    x, table = broadening
+    jx = states["jidx"][trans["low"][index]]
+    total = np.zeros(len(index))
+    for b in range(len(x)):
+        total = total + x[b] * table[b, jx, 0] * (T_REF / temp) ** table[b, jx, 1]
+    return (press / BAR) * total
+
+
+def superline_node(states, trans, broadening, temp, press, q_t, molar_mass, s_min, s_sl, step):
+    """the node's list with super-lines, by the contract: {"params": [4][strong + super-lines] in the list's order; "kept",
+    "strong", "weak": indices in the transition list; "cells": the cell numbers of the super-lines, ascending; "S_c", "G_c":
+    their sums; "keys": [entries][cell, kind, position] of the list, kind 0 a super-line (position: its cell's first transition)
+    and 1 a strong transition"""
+    strength = strengths(states, trans, temp, q_t)
+    keep = strength >= s_min
+    is_strong = keep & (strength >= s_sl)
+    strong, weak = np.nonzero(is_strong)[0], np.nonzero(keep & ~is_strong)[0]
+    nu0 = trans["nu0"]
+    cell = np.floor(nu0 / step).astype(np.int64)
+    cells, slot = np.unique(cell[weak], return_inverse=True)
+    s_c = np.bincount(slot, weights=strength[weak], minlength=len(cells))            # one after the other, in list order
+    g_c = np.bincount(slot, weights=strength[weak] * _gamma(states, trans, broadening, weak, temp, press), minlength=len(cells))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        gamma_c = np.where(s_c > 0, g_c / np.where(s_c > 0, s_c, 1.0), 0.0)
+    nu_c = (cells.astype(np.float64) + 0.5) * step
+    first_of = np.searchsorted(cell, cells, side="left")
+    nu = np.concatenate([nu_c, nu0[strong]])
+    s = np.concatenate([s_c, strength[strong]])
+    gamma = np.concatenate([gamma_c, _gamma(states, trans, broadening, strong, temp, press)])
+    kind = np.concatenate([np.zeros(len(cells), np.int64), np.ones(len(strong), np.int64)])
+    keys = np.stack([np.concatenate([cells, cell[strong]]), kind, np.concatenate([first_of, strong])], axis=1)
+    order = np.lexsort((keys[:, 2], keys[:, 1], keys[:, 0]))
+    nu, s, gamma, keys = nu[order], s[order], gamma[order], keys[order]
+    alpha = (nu / pc.C) * np.sqrt(2.0 * LN2 * pc.N_A * pc.K_B * temp / molar_mass)
+    a = np.sqrt(LN2) / alpha
+    y = np.maximum(a * gamma, Y_MIN)
+    return {"params": np.stack([nu, s * a * INV_SQRT_PI, a, y]), "kept": np.nonzero(keep)[0], "strong": strong, "weak": weak,
+            "cells": cells, "S_c": s_c, "G_c": g_c, "keys": keys}
+
+
+def tile_ranges(nu, nu_first, dnu, n_points, cutoff, step=0.0):
+    """[tiles][first, one past the last] entry of the node's list a tile of TILE_POINTS points walks, as k_exomol_ranges finds them:
+    two bisections per tile with the reach cutoff * (1 + 1e-12) + 1e-9 + step.  With super-lines `nu` ascends only from cell to
+    cell, and `step` = d makes the result hold every entry within the cut-off of one of the tile's points all the same"""
+    nu = np.asarray(nu, np.float64)
+    widen = cutoff * (1.0 + RANGE_WIDEN[0]) + RANGE_WIDEN[1] + step
+    out = np.empty((-(-n_points // TILE_POINTS), 2), np.int32)
+    for t in range(len(out)):
+        first, last = t * TILE_POINTS, min((t + 1) * TILE_POINTS, n_points) - 1
+        lo, hi = nu_first + float(first) * dnu - widen, nu_first + float(last) * dnu + widen
+        a, b = 0, len(nu)
+        while a < b:                                             # the first index with nu >= lo
+            mid = a + (b - a) // 2
+            if nu[mid] < lo:
+                a = mid + 1
+            else:
+                b = mid
+        c, d = a, len(nu)
+        while c < d:                                             # the first index with nu > hi
+            mid = c + (d - c) // 2
+            if nu[mid] <= hi:
+                c = mid + 1
+            else:
+                d = mid
+        out[t] = a, c
+    return out
+
+
 # ---- device ------------------------------------------------------------------------------------------------------------
 class ExomolOpacity(DeviceObject):
     """hx_exomol: resident states, broadening table and sorted transitions; nodes of up to n_points_max spectral points,
@@ -309,6 +434,7 @@ class ExomolOpacity(DeviceObject):
         self.n_points_max, self.nodes_per_launch, self.n_nodes_max = int(n_points_max), int(nodes_per_launch), int(n_nodes_max)
         self.with_fp64 = bool(with_fp64)
         self.n_nodes = self.n_points = self.rows_run = self._params_len = 0
+        self.superlines = None
         self._create(ctx, int(n_states_max), int(n_trans_max), int(n_broadeners_max), self.n_points_max, self.nodes_per_launch,
                      self.n_nodes_max, int(self.with_fp64))
 
@@ -344,7 +470,17 @@ class ExomolOpacity(DeviceObject):
         a = np.ascontiguousarray(trans["A"], np.float64).reshape(-1)
         assert len(up) == len(low) == len(a)
         self.n_nodes = self.rows_run = 0
+        self.superlines = None                               # the library drops them with the list
         self._call("set_transitions", len(a), ip(up), ip(low), dp(a))
+
+    def set_superlines(self, threshold, step):
+        """S_sl and d for the list the handle holds; step = 0 (or None) turns super-lines off.  The nodes are set after it"""
+        step = 0.0 if step is None else float(step)
+        threshold = 0.0 if threshold is None else float(threshold)
+        self.n_nodes = self.rows_run = 0
+        self.superlines = None
+        self._call("set_superlines", threshold, step)
+        self.superlines = (threshold, step) if step > 0 else None
 
     def set_nodes(self, temps, pressures, q_t, molar_mass, cutoff, s_min, nu_first, dnu, n_points):
         """T, P and Q(T) per node, and what the nodes share"""
@@ -367,10 +503,13 @@ class ExomolOpacity(DeviceObject):
         return p
 
     def get(self, name):
-        """"line_params": a list of [4][kept[row]] per row of the last launch"""
+        """"line_params": a list of [4][kept[row]] per row of the last launch; with super-lines [4][strong + super-lines]"""
         if name != "line_params":
             return DeviceObject.get(self, name)
-        kept = DeviceObject.get(self, "kept")
+        if self.superlines is None:
+            kept = DeviceObject.get(self, "kept")
+        else:
+            kept = DeviceObject.get(self, "superline_counts")[:, [0, 2]].sum(axis=1).astype(np.int32)
         self._params_len = 4 * int(kept.sum())
         flat = DeviceObject.get(self, name)
         at = np.concatenate([[0], np.cumsum(4 * kept.astype(np.int64))])
@@ -379,7 +518,8 @@ class ExomolOpacity(DeviceObject):
     def _results(self):
         tiles = -(-self.n_points // TILE_POINTS)
         return {"slabs32": ((self.rows_run, self.n_points), np.float32), "kappa64": (self.rows_run, self.n_points),
-                "kept": ((self.rows_run,), np.int32), "tile_ranges": ((self.rows_run, tiles, 2), np.int32),
+                "kept": ((self.rows_run,), np.int32), "superline_counts": ((self.rows_run, 3), np.int32),
+                "tile_ranges": ((self.rows_run, tiles, 2), np.int32),
                 "line_params": self._params_len, "timing_ms": 2}
 
 
@@ -406,15 +546,19 @@ def _check_node_inputs(temps, pressures, nu_grid, molar_mass, cutoff, s_min):
 
 
 def exomol_opacity(states, trans, broadening, q_table, temps, pressures_cgs, nu_grid, molar_mass=None, cutoff=DEFAULT_CUTOFF,
-                   strength_cutoff=0.0, backend="device", ctx=None, nodes_per_launch=4, handle=None, timing=None):
+                   strength_cutoff=0.0, backend="device", ctx=None, nodes_per_launch=4, handle=None, timing=None,
+                   superline_threshold=None, superline_step=None):
     """kappa [T][P][nu] in cm^2 g^-1, fp64.  `states`: read_states' arrays; `trans`: sort_transitions' arrays; `broadening`:
     broadening_table's pair; `q_table`: (T, Q); `nu_grid`: (nu of point 0, dnu, points); `handle`: an ExomolOpacity with fp64 rows
     that already holds the three inputs.  `timing` receives prepare_ms, sum_ms and pairs, summed over the nodes, and `kept`, the
-    number of transitions kept per node [T][P]"""
+    number of transitions kept per node [T][P].  `superline_threshold`, `superline_step`: S_sl and d (d defaults to dnu); `timing`
+    then also receives `strong`, `weak` and `superlines` per node [T][P], and a `handle` given is set to them"""
     if backend not in ("device", "numpy"):
         raise ValueError("exomol: backend is device or numpy (got %r)" % (backend,))
     s_min = float(strength_cutoff)
     temps, pressures, (nu_first, dnu, n_points) = _check_node_inputs(temps, pressures_cgs, nu_grid, molar_mass, cutoff, s_min)
+    sl = check_superlines(superline_threshold, superline_step, cutoff, trans["nu0"][-1], dnu)
+    counts = np.zeros((len(temps), len(pressures), 3), np.int64)
     q_t = [partition_value(q_table, t) for t in temps]
     out = np.empty((len(temps), len(pressures), n_points))
     kept = np.zeros((len(temps), len(pressures)), np.int64)
@@ -422,7 +566,12 @@ def exomol_opacity(states, trans, broadening, q_table, temps, pressures_cgs, nu_
     if backend == "numpy":
         for it, t in enumerate(temps):
             for jp, p in enumerate(pressures):
-                prm, idx = node_params(states, trans, broadening, t, p, q_t[it], molar_mass, s_min)
+                if sl is None:
+                    prm, idx = node_params(states, trans, broadening, t, p, q_t[it], molar_mass, s_min)
+                else:
+                    node = superline_node(states, trans, broadening, t, p, q_t[it], molar_mass, s_min, sl[0], sl[1])
+                    prm, idx = node["params"], node["kept"]
+                    counts[it, jp] = len(node["strong"]), len(node["weak"]), len(node["cells"])
                 kept[it, jp] = len(idx)
                 out[it, jp] = numpy_node(prm, nu_first, dnu, n_points, cutoff, molar_mass)
                 if timing is not None:
@@ -438,8 +587,10 @@ def exomol_opacity(states, trans, broadening, q_table, temps, pressures_cgs, nu_
                 handle = ExomolOpacity.of(ctx, states, trans, broadening, n_points, max(1, min(int(nodes_per_launch), len(nodes))),
                                           len(nodes), True)
             try:
+                if handle.superlines != sl:                                  # a plain handle in a plain call stays untouched
+                    handle.set_superlines(*(sl or (0.0, 0.0)))
                 per = handle.nodes_per_launch
-                flat, flat_kept = out.reshape(len(nodes), n_points), kept.reshape(-1)
+                flat, flat_kept, flat_counts = out.reshape(len(nodes), n_points), kept.reshape(-1), counts.reshape(-1, 3)
                 for lo in range(0, len(nodes), handle.n_nodes_max):          # a handle made for fewer nodes takes them in turns
                     part = nodes[lo:lo + handle.n_nodes_max]
                     handle.set_nodes([n[0] for n in part], [n[1] for n in part], [n[2] for n in part], molar_mass, cutoff, s_min,
@@ -449,6 +600,8 @@ def exomol_opacity(states, trans, broadening, q_table, temps, pressures_cgs, nu_
                         handle.run_nodes(first, n)
                         flat[lo + first:lo + first + n] = handle.get("kappa64")
                         flat_kept[lo + first:lo + first + n] = handle.get("kept")
+                        if sl is not None:
+                            flat_counts[lo + first:lo + first + n] = handle.get("superline_counts")
                         if timing is not None:
                             pairs += sum(count_pairs(prm[0], nu_first, dnu, n_points, cutoff) for prm in handle.get("line_params"))
                     ms += handle.get("timing_ms")
@@ -463,6 +616,8 @@ def exomol_opacity(states, trans, broadening, q_table, temps, pressures_cgs, nu_
         timing["sum_ms"] = timing.get("sum_ms", 0.0) + float(ms[1])
         timing["pairs"] = timing.get("pairs", 0) + pairs
         timing["kept"] = kept
+        if sl is not None:
+            timing["strong"], timing["weak"], timing["superlines"] = counts[..., 0], counts[..., 1], counts[..., 2]
     return out
 
 
@@ -473,7 +628,9 @@ class ExomolSlabs(object):
     times and `kept` the transitions kept per node once the table is built"""
 
     def __init__(self, states, trans, broadening, q_table, temps, pressures, numax, dnu, n_points, molar_mass, cutoff, s_min,
-                 nodes_per_launch=4):
+                 nodes_per_launch=4, superline_threshold=None, superline_step=None):
+        self.superlines = check_superlines(superline_threshold, superline_step, cutoff, trans["nu0"][-1], dnu)
+        self.counts = []                                             # per node (strong, weak, super-lines), with super-lines
         self.states, self.trans, self.broadening = states, trans, broadening
         self.numax, self.dnu, self.n_points = int(numax), float(dnu), int(n_points)
         self.temps, self.press = sorted(set(temps)), sorted(set(pressures))
@@ -494,7 +651,14 @@ class ExomolSlabs(object):
         self._check(n_points)
         for it, t in enumerate(self.temps):
             for p in self.press:
-                prm, idx = node_params(self.states, self.trans, self.broadening, float(t), p, self.q_t[it], self.molar_mass, self.s_min)
+                if self.superlines is None:
+                    prm, idx = node_params(self.states, self.trans, self.broadening, float(t), p, self.q_t[it], self.molar_mass,
+                                           self.s_min)
+                else:
+                    node = superline_node(self.states, self.trans, self.broadening, float(t), p, self.q_t[it], self.molar_mass,
+                                          self.s_min, *self.superlines)
+                    prm, idx = node["params"], node["kept"]
+                    self.counts.append((len(node["strong"]), len(node["weak"]), len(node["cells"])))
                 self.kept.append(len(idx))
                 yield numpy_node(prm, 0.0, self.dnu, self.n_points, self.cutoff, self.molar_mass).astype(np.float32)
 
@@ -503,6 +667,8 @@ class ExomolSlabs(object):
         nodes = [(float(t), p, self.q_t[it]) for it, t in enumerate(self.temps) for p in self.press]
         per = min(self.nodes_per_launch, b.max_tp)
         self.handle = h = ExomolOpacity.of(b.ctx, self.states, self.trans, self.broadening, self.n_points, per, len(nodes))
+        if self.superlines is not None:
+            h.set_superlines(*self.superlines)
         h.set_nodes([n[0] for n in nodes], [n[1] for n in nodes], [n[2] for n in nodes], self.molar_mass, self.cutoff, self.s_min,
                     0.0, self.dnu, self.n_points)
         slabs = h.slab_pointer()
@@ -511,6 +677,8 @@ class ExomolSlabs(object):
             h.run_nodes(first, n)
             b.run_device(slabs, n, first)
             self.kept.extend(int(k) for k in h.get("kept"))        # after the launch's sort is queued: the counts are the tool's report
+            if self.superlines is not None:
+                self.counts.extend(tuple(int(v) for v in row) for row in h.get("superline_counts"))
 
     def close(self):
         h, self.handle = self.handle, None
@@ -523,11 +691,12 @@ class ExomolSlabs(object):
 
 def exomol_ktable(states, trans, broadening, q_table, temps, pressure_codes, numax, dnu, inter, n_gauss, molar_mass=None,
                   cutoff=DEFAULT_CUTOFF, strength_cutoff=0.0, target=None, backend="device", ctx=None, nodes_per_launch=4,
-                  lds_points=None, timing=None):
+                  lds_points=None, timing=None, superline_threshold=None, superline_step=None):
     """the data sets of `<name>_opac_kdistr` and, with `target` = (temperatures, pressures), of `<name>_opac_ip_kdistr`, as
     ktable.build_species returns them for the directory exomol.py would write for the same arguments -- to the bit -- without the
     files.  `temps`: integers in K; `pressure_codes`: keys of ktable.pressure_table(); the range is 0 ... numax in one chunk.
-    `timing` receives prepare_ms, sum_ms, kept (per node, node = p + np t) and build_table's entries"""
+    `timing` receives prepare_ms, sum_ms, kept (per node, node = p + np t) and build_table's entries; with super-lines
+    (`superline_threshold`, `superline_step`, which defaults to dnu) also strong, weak and superlines per node"""
     from . import ktable
     if backend not in ("device", "numpy"):
         raise ValueError("exomol: backend is device or numpy (got %r)" % (backend,))
@@ -544,11 +713,13 @@ def exomol_ktable(states, trans, broadening, q_table, temps, pressure_codes, num
     if n_points > MAX_TABLE_POINTS:
         raise IOError("exomol: %d spectral points, the k-table's kernel takes 1 ... %d" % (n_points, MAX_TABLE_POINTS))
     source = ExomolSlabs(states, trans, broadening, q_table, temps, pressures, numax, dnu, n_points, molar_mass, cutoff,
-                         strength_cutoff, nodes_per_launch)
+                         strength_cutoff, nodes_per_launch, superline_threshold, superline_step)
     out = ktable.build_table(source, inter, n_gauss, "hip" if backend == "device" else "numpy", ctx, source.nodes_per_launch,
                              ktable.LDS_POINTS if lds_points is None else lds_points, target, timing)
     if timing is not None:
         timing["prepare_ms"], timing["sum_ms"], timing["kept"] = float(source.ms[0]), float(source.ms[1]), list(source.kept)
+        if source.superlines is not None:
+            timing["strong"], timing["weak"], timing["superlines"] = ([c[k] for c in source.counts] for k in range(3))
     return out
 
 
@@ -562,6 +733,9 @@ def parse_args(argv=None):
     p.add_argument("-broadeners", default=None, help="name:fraction:file[:gamma_default:n_default], separated by blanks")
     p.add_argument("-default_broadening", default="%g %g" % DEFAULT_BROADENING, help="gamma [cm^-1 / bar at 296 K] and n")
     p.add_argument("-strength_cutoff", type=float, default=0.0, help="S_min in cm / molecule: per node, transitions below it are left out")
+    p.add_argument("-superline_threshold", type=float, default=None,
+                   help="S_sl in cm / molecule: per node, kept transitions below it are merged per cell into super-lines")
+    p.add_argument("-superline_step", type=float, default=None, help="the cell width d in cm^-1; -dnu unless given")
     p.add_argument("-temperatures", required=True, help="integers in K, separated by blanks")
     p.add_argument("-pressure_codes", required=True, help="HELIOS-K's codes, n800 ... p400, separated by blanks")
     p.add_argument("-numin", type=int, default=0)
@@ -610,9 +784,14 @@ def _refuse_with_ktable(opt):
         raise IOError("exomol: -nodes_per_launch is an integer >= 1")
 
 
-def _print_kept(kept, nodes, n_trans):
-    for (t, code), k in zip(nodes, kept):
-        print("exomol: %d K, %s: %d of %d transitions kept" % (t, code, int(k), n_trans))
+def _print_kept(kept, nodes, n_trans, timing=None):
+    """`timing` with super-lines: the three counts next to kept"""
+    classes = None
+    if timing is not None and "strong" in timing:
+        classes = [np.asarray(timing[k]).reshape(-1) for k in ("strong", "weak", "superlines")]
+    for i, ((t, code), k) in enumerate(zip(nodes, kept)):
+        more = "" if classes is None else ": %d strong, %d weak in %d super-lines" % tuple(int(c[i]) for c in classes)
+        print("exomol: %d K, %s: %d of %d transitions kept%s" % (t, code, int(k), n_trans, more))
 
 
 def _main_ktable(opt, states, trans, broadening, q_table, temps, codes, molar_mass, t0):
@@ -623,10 +802,10 @@ def _main_ktable(opt, states, trans, broadening, q_table, temps, codes, molar_ma
     timing = {}
     native, table_ip = exomol_ktable(states, trans, broadening, q_table, temps, codes, opt.numax, opt.dnu, inter,
                                      opt.number_of_gaussian_points, molar_mass, opt.cutoff, opt.strength_cutoff, target, opt.backend,
-                                     None, opt.nodes_per_launch, None, timing)
+                                     None, opt.nodes_per_launch, None, timing, opt.superline_threshold, opt.superline_step)
     table = ktable.pressure_table()
     by_pressure = sorted(set(codes), key=lambda c: table[c])
-    _print_kept(timing["kept"], [(t, c) for t in sorted(set(temps)) for c in by_pressure], len(trans["nu0"]))
+    _print_kept(timing["kept"], [(t, c) for t in sorted(set(temps)) for c in by_pressure], len(trans["nu0"]), timing)
     stem = os.path.join(opt.directory_with_individual_files, opt.name)
     written = [ktable.write_table("%s_opac_kdistr.%s" % (stem, opt.container), native)]
     if table_ip is not None:
@@ -652,6 +831,12 @@ def main(argv=None):
         raise IOError("exomol: -strength_cutoff %r is not a finite number >= 0 cm / molecule" % (opt.strength_cutoff,))
     if not (np.isfinite(opt.cutoff) and opt.cutoff > 0):
         raise IOError("exomol: -cutoff %r is not > 0 cm^-1" % (opt.cutoff,))
+    if opt.superline_step is not None and opt.superline_threshold is None:
+        raise IOError("exomol: -superline_step %r without -superline_threshold" % (opt.superline_step,))
+    try:                                                 # before the files are read; the largest nu_0 is checked with the list
+        check_superlines(opt.superline_threshold, opt.superline_step, opt.cutoff, 0.0, opt.dnu)
+    except ValueError as e:
+        raise IOError(str(e))
     molar_mass = opt.molar_mass
     if molar_mass is None:
         from .species_data import species_lib
@@ -674,6 +859,10 @@ def main(argv=None):
     print("exomol: %d states of %s (largest J %.17g), %d transitions of %s, %d with nu_0 <= 0 skipped, read and sorted in %.2f s"
           % (len(states["E"]), opt.states, float(states["J"].max()), n_trans, opt.trans, skipped, time.time() - t_parsed))
     broadening = broadening_table(entries, int(states["jidx"].max()), print)
+    try:
+        check_superlines(opt.superline_threshold, opt.superline_step, opt.cutoff, trans["nu0"][-1], opt.dnu)
+    except ValueError as e:
+        raise IOError(str(e))
     if opt.ktable == "yes":
         return _main_ktable(opt, states, trans, broadening, q_table, temps, codes, molar_mass, t0)
     if opt.numin != 0:
@@ -692,9 +881,11 @@ def main(argv=None):
                                       max(1, min(opt.nodes_per_launch, n_nodes)), n_nodes, True)
         for lo, hi, n in chunks:
             kappa = exomol_opacity(states, trans, broadening, q_table, temps, pressures, (float(lo), opt.dnu, n), molar_mass, opt.cutoff,
-                                   opt.strength_cutoff, opt.backend, ctx, opt.nodes_per_launch, handle, timing)
-            if (lo, hi, n) == chunks[0]:                # the cut does not depend on the chunk
-                _print_kept(timing["kept"].reshape(-1), [(t, c) for t in temps for c in codes], n_trans)
+                                   opt.strength_cutoff, opt.backend, ctx, opt.nodes_per_launch, handle, timing,
+                                   opt.superline_threshold, None if opt.superline_threshold is None else
+                                   opt.dnu if opt.superline_step is None else opt.superline_step)
+            if (lo, hi, n) == chunks[0]:                # neither the cut nor the cells depend on the chunk
+                _print_kept(timing["kept"].reshape(-1), [(t, c) for t in temps for c in codes], n_trans, timing)
             nu = float(lo) + np.arange(n, dtype=np.float64) * opt.dnu
             for it, t in enumerate(temps):
                 for jp, code in enumerate(codes):

@@ -812,6 +812,15 @@ int hx_cia_get(hx_cia* cia, const char* name, void* out, size_t out_bytes);
  * into offsets (one workgroup per node, no atomics), k_exomol_prepare writes the kept transitions to their positions,
  * k_exomol_ranges searches per tile the compacted nu_0 for the lines within the cut-off, k_exomol_sum adds.  The node is a grid
  * dimension of all five, and nothing goes through the host between them.
+ * Super-lines (hx_exomol_set_superlines; off unless set): a kept transition with S >= S_sl is strong and keeps its profile, one
+ * with S_min <= S < S_sl is weak; the weak ones of a cell c = floor(nu_0 / d) become one super-line with S_c = sum S, gamma_c =
+ * sum (S gamma) / S_c (0 where S_c = 0), nu_c = (c + 0.5) d and a, y, s by the statements above.  The node's list is the strong
+ * transitions and the super-lines by the key (cell, kind, position), a cell's super-line before its strong transitions, never
+ * longer than the kept list.  In place of count, scan and prepare: k_exomol_classify (S once per transition, strong and weak
+ * counts per workgroup), k_exomol_cells (a wavefront per occupied cell: lane-strided sums in list order, a butterfly of shuffles
+ * -- no atomics, one order in every launch -- and the mask of the cells that hold a weak transition), k_exomol_scan over the strong
+ * counts and over the cells' counts, k_exomol_merge (every strong transition and every super-line to its position), then
+ * k_exomol_ranges with a reach wider by d, since nu ascends only from cell to cell, and k_exomol_sum as it is.
  *
  *   hx_exomol_create          the largest number of states, transitions, broadeners and spectral points, the nodes per launch and
  *                             in all; want_fp64 != 0: the handle also keeps the rows before rounding.  Resident per launch row:
@@ -826,7 +835,14 @@ int hx_cia_get(hx_cia* cia, const char* name, void* out, size_t out_bytes);
  *   hx_exomol_set_transitions up, low (0-based) and A [s^-1], sorted by nu_0 (ties in any order the caller fixed); they stay
  *                             resident, 24 bytes per transition with nu_0.  Refused with HX_E_ARG and the index: an id outside
  *                             the table, A that is not finite or < 0, nu_0 <= 0, a list that is not sorted, more transitions than
- *                             the handle holds
+ *                             the handle holds.  Super-lines set before are dropped
+ *   hx_exomol_set_superlines  after hx_exomol_set_transitions: S_sl [cm / molecule, >= 0, +inf makes every kept transition weak] and
+ *                             the cell width d [cm^-1]; step = 0 turns super-lines off.  The host finds the occupied cells of the
+ *                             resident list once; the arrays of this mode (S per transition and launch row, the cells' sums,
+ *                             masks and counts) are allocated here, none without this call.  Nodes set before are dropped.
+ *                             Every refusal but that of a handle without transitions leaves super-lines off and the nodes dropped.
+ *                             Refused with the value: S_sl that is NaN or < 0, a step that is not finite or < 0, a largest
+ *                             nu_0 / d at or above 2^31; hx_exomol_set_nodes refuses a step greater than its cut-off
  *   hx_exomol_set_nodes       T, P [dyne cm^-2], Q(T) per node, and what the nodes share: the molar mass [g/mol], the cut-off
  *                             [cm^-1], S_min [cm / molecule, >= 0], nu of point 0, dnu, the number of points.  A refusal names the
  *                             node and the value
@@ -839,7 +855,10 @@ int hx_cia_get(hx_cia* cia, const char* name, void* out, size_t out_bytes);
  *                             rows before rounding; want_fp64 only), "kept" (int per row), "line_params" (row after row,
  *                             double[4][kept[row]]: nu_0, s, a, y of the kept transitions), "tile_ranges" (int [rows][tiles][2]:
  *                             first and one past the last kept transition a tile walks); "timing_ms" (double[2]: ms in count +
- *                             scan + prepare + ranges and in the sum, summed since hx_exomol_set_nodes)
+ *                             scan + prepare + ranges and in the sum, summed since hx_exomol_set_nodes).  With super-lines:
+ *                             "kept" is strong + weak, "superline_counts" (int [rows][3]: strong, weak, super-lines),
+ *                             "line_params" holds double[4][strong + super-lines] per row in the list's order, "tile_ranges"
+ *                             the widened ranges, and the new steps count into the first slot of "timing_ms"
  */
 typedef struct hx_exomol hx_exomol;
 int hx_exomol_create(hx_context* ctx, int n_states_max, int n_trans_max, int n_broadeners_max, int n_points_max,
@@ -848,6 +867,7 @@ int hx_exomol_destroy(hx_exomol* exomol);
 int hx_exomol_set_states(hx_exomol* exomol, int n_states, const double* energy, const double* g, const int* jidx);
 int hx_exomol_set_broadening(hx_exomol* exomol, int n_broadeners, int n_jidx, const double* fraction, const double* table);
 int hx_exomol_set_transitions(hx_exomol* exomol, int n_trans, const int* up, const int* low, const double* a);
+int hx_exomol_set_superlines(hx_exomol* exomol, double s_sl, double step);
 int hx_exomol_set_nodes(hx_exomol* exomol, int n_nodes, const double* temp, const double* press, const double* q_t, double molar_mass,
                         double cutoff, double s_min, double nu_first, double dnu, int n_points);
 int hx_exomol_run_nodes(hx_exomol* exomol, int first_node, int n_nodes);
