@@ -1,4 +1,4 @@
-// What the objects of the off-line tools (hx_ktable, hx_ktmix, hx_premix, hx_star, hx_mie, hx_lines, hx_cia) share around their kernels: the list
+// What the objects of the off-line tools (hx_ktable, hx_ktmix, hx_premix, hx_star, hx_mie, hx_lines, hx_cia, hx_exomol, hx_chem) share around their kernels: the list
 // of an object's device allocations, an event pair that times a stretch of the stream and is read later, the tail of hx_*_get,
 // the rows of the batch object's (hx_rt) named arrays, and the re-gridding of a table onto another (T, P) grid.  The kernels and the
 // state of the objects stay with the objects.

@@ -874,6 +874,37 @@ int hx_exomol_run_nodes(hx_exomol* exomol, int first_node, int n_nodes);
 int hx_exomol_device_ptr(hx_exomol* exomol, const char* name, void** out_dptr);
 int hx_exomol_get(hx_exomol* exomol, const char* name, void* out, size_t out_bytes);
 
+/* ---- (14) Equilibrium chemistry of the analytic C-H-O network (csrc/chem.hip; the contract and the host side are
+ * helios_amd/chem.py) --------------------------------------------------------------------------------------------------------------
+ * Per (chemistry, T, P) node: dG of the three net reactions linear in T between the rows of the table, K1 = exp(-dG1 / (R T)) / P / P,
+ * K2 = exp(-dG2 / (R T)), K3 = exp(-dG3 / (R T)) / P / P with P in bar, the quintic in x = n_CH4 with the coefficients of chem.py,
+ * its root in [x_min, 2 n_C] by bisection on the bit patterns of the ends, water from the oxygen balance, CO, CO2 and C2H2 from x and
+ * water, the seven volume mixing ratios and mu.  k_chem_nodes: a thread per node, the chemistry is blockIdx.y, the rows go through
+ * LDS once per workgroup, eight planes of results.  fp64, nothing contracted, no atomics.
+ *
+ *   hx_chem_create      the largest number of Gibbs rows (2 ... 1024, what the kernel stages in LDS), of nodes and of chemistries
+ *                       per launch.  The results' allocation, when the device does not give it, is refused with its byte count
+ *   hx_chem_set_table   T [K] strictly ascending and dG1, dG2, dG3 [J/mol] per row, and the gas constant [J/mol/K].  Refused with
+ *                       the row: a value that is not finite, T that does not ascend, fewer than 2 rows, more than the handle
+ *                       holds.  Nodes set before are dropped
+ *   hx_chem_set_nodes   T [K] and P [bar] per node.  Refused with the node and the value: T outside the table's rows, P that is
+ *                       not a finite number > 0, more nodes than the handle holds
+ *   hx_chem_run         queues k_chem_nodes for n_chem abundance pairs (n_O, n_C per chemistry), He/H and the seven molar weights
+ *                       (H2, He, H2O, CO, CH4, CO2, C2H2) on the context's stream.  Refused before any launch, with the value: an
+ *                       abundance that is not a finite number > 0, He/H < 0, more chemistries than the handle holds, no nodes.  A
+ *                       refused run leaves no result
+ *   hx_chem_get         "vmr" (double [n_chem of the last hx_chem_run][8][n_nodes]: H2, He, H2O, CO, CH4, CO2, C2H2, mu),
+ *                       "timing_ms" (double[2]: ms in k_chem_nodes and its launches, summed since hx_chem_set_nodes)
+ */
+typedef struct hx_chem hx_chem;
+int hx_chem_create(hx_context* ctx, int max_rows, int max_nodes, int max_chem, hx_chem** out_chem);
+int hx_chem_destroy(hx_chem* chem);
+int hx_chem_set_table(hx_chem* chem, int n_rows, const double* temp, const double* dg1, const double* dg2, const double* dg3,
+                      double gas_constant);
+int hx_chem_set_nodes(hx_chem* chem, int n_nodes, const double* temp, const double* press_bar);
+int hx_chem_run(hx_chem* chem, int n_chem, const double* o_abund, const double* c_abund, double he_to_h, const double* weights);
+int hx_chem_get(hx_chem* chem, const char* name, void* out, size_t out_bytes);
+
 #ifdef __cplusplus
 }
 #endif
