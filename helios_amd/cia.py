@@ -37,17 +37,17 @@ and the device equals it bit for bit, in the fp64 rows and in the fp32 slabs.
 sorts them on the same stream.  The containers are the ones `cia.py` followed by `ktable.py` writes, to the bit: one chunk
 0 ... numax, the nodes sorted ascending and de-duplicated (node = p + np t), the kernel's step the `-dnu` given and the k-table's
 axis numax / points.  Refused with `-ktable yes`: `-numin` other than 0, `-chunk_width`, `-output_format text`, `-output_directory`.
+
+The frame around the reader and the contract is _nodes.py's, shared with lines.py and exomol.py.
 """
 import argparse
-import ctypes
-import os
 import time
 
 import numpy as np
 
+from . import _nodes
 from . import phys_const as pc
-from ._tool import DeviceObject, dp, ip
-from .lines import MAX_TABLE_POINTS, chunk_limits, file_name, parse_pressure_codes, parse_temperatures, write_file
+from ._tool import dp, ip
 
 HEADER_MIN = 54
 _HEADER = (("numin", 20, 30), ("numax", 30, 40), ("points", 40, 47), ("temperature", 47, 54))
@@ -56,6 +56,7 @@ THREADS = 256
 POINTS_PER_THREAD = 4
 TILE_POINTS = THREADS * POINTS_PER_THREAD
 WINDOW = 256
+GRID_TOOL = "lines"                   # the refusals of the grid and of the node lists came from lines.py with its word, and keep it
 
 
 # ---- the input -----------------------------------------------------------------------------------------------------------
@@ -273,7 +274,7 @@ def numpy_node(bands, temp, press, nu_first, dnu, n_points, partner_mass, sigma=
 
 
 # ---- device ------------------------------------------------------------------------------------------------------------
-class CiaOpacity(DeviceObject):
+class CiaOpacity(_nodes.NodeOpacity):
     """hx_cia: the resident blocks of the selected bands, nodes of up to n_points_max spectral points, nodes_per_launch per
     launch into fp32 slabs that stay on the device; `with_fp64`: the rows before rounding as well"""
 
@@ -295,27 +296,16 @@ class CiaOpacity(DeviceObject):
         off, first = np.ascontiguousarray(block_off, np.int32), np.ascontiguousarray(band_first, np.int32)
         a = [np.ascontiguousarray(v, np.float64).reshape(-1) for v in (nu, k, block_temp, band_numin, band_numax)]
         assert len(a[0]) == len(a[1]) and len(off) == len(a[2]) + 1 and len(first) == len(a[3]) + 1 == len(a[4]) + 1
-        self.n_nodes = self.rows_run = 0
+        self._reset_nodes()
         self._call("set_blocks", len(a[2]), ip(off), dp(a[0]), dp(a[1]), dp(a[2]), len(a[3]), ip(first), dp(a[3]), dp(a[4]))
 
     def set_nodes(self, temps, pressures, partner_mass, nu_first, dnu, n_points):
         """T and P per node and what the nodes share"""
         arr = [np.ascontiguousarray(a, np.float64).reshape(-1) for a in (temps, pressures)]
         assert len(arr[0]) == len(arr[1])
-        self.n_nodes = self.rows_run = 0
+        self._reset_nodes()
         self._call("set_nodes", len(arr[0]), dp(arr[0]), dp(arr[1]), float(partner_mass), float(nu_first), float(dnu), int(n_points))
         self.n_nodes, self.n_points = len(arr[0]), int(n_points)
-
-    def run_nodes(self, first, n):
-        """queues nodes first ... first + n - 1 into rows 0 ... n - 1; returns at once"""
-        self._call("run_nodes", int(first), int(n))
-        self.rows_run = int(n)
-
-    def slab_pointer(self):
-        """device address of the fp32 slabs [nodes_per_launch][...], rows of the last run_nodes with the stride n_points"""
-        p = ctypes.c_void_p()
-        self._call("device_ptr", b"slabs32", ctypes.byref(p))
-        return p
 
     def _results(self):
         return {"slabs32": ((self.rows_run, self.n_points), np.float32), "kappa64": (self.rows_run, self.n_points), "timing_ms": 2}
@@ -323,28 +313,14 @@ class CiaOpacity(DeviceObject):
 
 # ---- the library functions -----------------------------------------------------------------------------------------------
 def _check_node_inputs(temps, pressures, nu_grid, partner_mass):
-    temps = np.asarray(temps, np.float64).reshape(-1)
-    pressures = np.asarray(pressures, np.float64).reshape(-1)
-    if len(temps) == 0 or not np.all(np.isfinite(temps) & (temps > 0)):
-        raise ValueError("cia: every temperature is a finite number > 0 (got %r)" % (temps.tolist(),))
-    if len(pressures) == 0 or not np.all(np.isfinite(pressures) & (pressures > 0)):
-        raise ValueError("cia: every pressure is a finite number > 0 dyne cm^-2 (got %r)" % (pressures.tolist(),))
-    nu_first, dnu, n_points = float(nu_grid[0]), float(nu_grid[1]), int(nu_grid[2])
-    if not (np.isfinite(dnu) and dnu > 0):
-        raise ValueError("cia: dnu = %r is not > 0" % (dnu,))
-    if n_points < 1 or not np.isfinite(nu_first):
-        raise ValueError("cia: the grid (nu_first, dnu, points) = %r needs a finite start and at least one point" % (tuple(nu_grid),))
-    if partner_mass is None or not (np.isfinite(partner_mass) and partner_mass > 0):
-        raise ValueError("cia: no partner mass (got %r): give one > 0 g/mol" % (partner_mass,))
-    return temps, pressures, (nu_first, dnu, n_points)
+    return _nodes.check_node_inputs("cia", temps, pressures, nu_grid, partner_mass, "partner")
 
 
 def cia_opacity(blocks, temps, pressures_cgs, nu_grid, partner_mass, backend="device", ctx=None, nodes_per_launch=4, handle=None,
                 timing=None):
     """kappa [T][P][nu] in cm^2 per gram of the partner, fp64.  `blocks`: the Blocks of the bands to take; `nu_grid`: (nu of point
     0, dnu, points); `handle`: a CiaOpacity with fp64 rows that already holds the blocks.  `timing` receives nodes_ms, summed"""
-    if backend not in ("device", "numpy"):
-        raise ValueError("cia: backend is device or numpy (got %r)" % (backend,))
+    _nodes.check_backend("cia", backend)
     temps, pressures, (nu_first, dnu, n_points) = _check_node_inputs(temps, pressures_cgs, nu_grid, partner_mass)
     bands = bands_of(blocks) if handle is None or backend == "numpy" else None
     out = np.empty((len(temps), len(pressures), n_points))
@@ -356,84 +332,39 @@ def cia_opacity(blocks, temps, pressures_cgs, nu_grid, partner_mass, backend="de
             for jp, p in enumerate(pressures):
                 out[it, jp] = numpy_node(bands, t, p, nu_first, dnu, n_points, partner_mass, sigma)
     else:
-        own_ctx, own_handle = ctx is None and handle is None, handle is None
-        if own_ctx:
-            from .device import Context
-            ctx = Context(int(os.environ.get("HELIOS_DEVICE", "0")))
-        try:
-            nodes = [(t, p) for t in temps for p in pressures]
-            if own_handle:
-                handle = CiaOpacity(ctx, bands, n_points, max(1, min(int(nodes_per_launch), len(nodes))), len(nodes), True)
-            try:
-                per = handle.nodes_per_launch
-                flat = out.reshape(len(nodes), n_points)
-                for lo in range(0, len(nodes), handle.n_nodes_max):          # a handle made for fewer nodes takes them in turns
-                    part = nodes[lo:lo + handle.n_nodes_max]
-                    handle.set_nodes([n[0] for n in part], [n[1] for n in part], partner_mass, nu_first, dnu, n_points)
-                    for first in range(0, len(part), per):
-                        n = min(per, len(part) - first)
-                        handle.run_nodes(first, n)
-                        flat[lo + first:lo + first + n] = handle.get("kappa64")
-                    ms += float(handle.get("timing_ms")[0])
-            finally:
-                if own_handle:
-                    handle.close()
-        finally:
-            if own_ctx:
-                ctx.close()
+        nodes = [(t, p) for t in temps for p in pressures]
+        flat = out.reshape(len(nodes), n_points)
+
+        def collect(h, rows):
+            flat[rows] = h.get("kappa64")
+        ms = float(_nodes.nodes_in_turns(
+            ctx, handle, lambda c: CiaOpacity(c, bands, n_points, max(1, min(int(nodes_per_launch), len(nodes))), len(nodes), True), nodes,
+            lambda h, part: h.set_nodes([n[0] for n in part], [n[1] for n in part], partner_mass, nu_first, dnu, n_points), collect)[0])
     if timing is not None:
         timing["nodes_ms"] = timing.get("nodes_ms", 0.0) + ms
     return out
 
 
 # ---- from the file to the k-table ------------------------------------------------------------------------------------------
-class CiaSlabs(object):
-    """ktable.build_table's slabs from the blocks of a CIA file: one chunk 0 ... numax of `n_points` points, the nodes sorted
-    ascending and de-duplicated as ktable.SpeciesFiles does (node = p + np * t).  On the device the slabs never leave it; `ms`
-    holds the kernel's time once the table is built"""
+class CiaSlabs(_nodes.NodeSlabs):
+    """ktable.build_table's slabs from the blocks of a CIA file (_nodes.NodeSlabs); `ms` holds the kernel's time once the table is
+    built"""
+
+    TOOL, KERNEL = "cia", "kernel's"
 
     def __init__(self, bands, temps, pressures, numax, dnu, n_points, partner_mass, nodes_per_launch=4):
-        self.bands, self.numax, self.dnu, self.n_points = bands, int(numax), float(dnu), int(n_points)
-        self.temps, self.press = sorted(set(temps)), sorted(set(pressures))
-        self.partner_mass = partner_mass
-        self.nodes_per_launch = max(1, int(nodes_per_launch))
-        self.handle, self.ms = None, 0.0
+        _nodes.NodeSlabs.__init__(self, temps, pressures, numax, dnu, n_points, nodes_per_launch)
+        self.bands, self.partner_mass = bands, partner_mass
+        self._sigma = (None, None)                                   # (it, numpy_sigma of temps[it]): the pressures of a T share it
 
-    def axis(self):
-        return 0, self.numax, self.numax / self.n_points           # ktable.SpeciesFiles.resolution() of the file not written
+    def host_slab(self, it, t, p):
+        if self._sigma[0] != it:
+            self._sigma = (it, numpy_sigma(self.bands, t, 0.0 + np.arange(self.n_points, dtype=np.float64) * self.dnu))
+        return numpy_node(self.bands, t, p, 0.0, self.dnu, self.n_points, self.partner_mass, self._sigma[1])
 
-    def _check(self, n_points):
-        if n_points != self.n_points:
-            raise IOError("cia: the k-table's axis 0 ... %d cm^-1 at %.17g cm^-1 has %d points, the kernel's grid at -dnu %.17g has "
-                          "%d" % (self.numax, self.numax / self.n_points, n_points, self.dnu, self.n_points))
-
-    def host_slabs(self, pool, n_points):
-        self._check(n_points)
-        nu = 0.0 + np.arange(self.n_points, dtype=np.float64) * self.dnu
-        for t in self.temps:
-            sigma = numpy_sigma(self.bands, float(t), nu)
-            for p in self.press:
-                yield numpy_node(self.bands, float(t), p, 0.0, self.dnu, self.n_points, self.partner_mass, sigma).astype(np.float32)
-
-    def feed(self, b, pool, n_points):
-        self._check(n_points)
-        nodes = [(float(t), p) for t in self.temps for p in self.press]
-        per = min(self.nodes_per_launch, b.max_tp)
-        self.handle = h = CiaOpacity(b.ctx, self.bands, self.n_points, per, len(nodes))
-        h.set_nodes([n[0] for n in nodes], [n[1] for n in nodes], self.partner_mass, 0.0, self.dnu, self.n_points)
-        slabs = h.slab_pointer()
-        for first in range(0, len(nodes), per):
-            n = min(per, len(nodes) - first)
-            h.run_nodes(first, n)
-            b.run_device(slabs, n, first)
-
-    def close(self):
-        h, self.handle = self.handle, None
-        if h is not None:
-            try:
-                self.ms = float(h.get("timing_ms")[0])
-            finally:
-                h.close()
+    def open_handle(self, ctx, per, nodes):
+        self.handle = h = CiaOpacity(ctx, self.bands, self.n_points, per, len(nodes))
+        h.set_nodes([n[1] for n in nodes], [n[2] for n in nodes], self.partner_mass, 0.0, self.dnu, self.n_points)
 
 
 def cia_ktable(blocks, temps, pressure_codes, numax, dnu, inter, n_gauss, partner_mass, target=None, backend="device", ctx=None,
@@ -442,26 +373,12 @@ def cia_ktable(blocks, temps, pressure_codes, numax, dnu, inter, n_gauss, partne
     ktable.build_species returns them for the directory cia.py would write for the same arguments -- to the bit -- without the
     files.  `temps`: integers in K; `pressure_codes`: keys of ktable.pressure_table(); the range is 0 ... numax in one chunk.
     `timing` receives nodes_ms and build_table's entries"""
-    from . import ktable
-    if backend not in ("device", "numpy"):
-        raise ValueError("cia: backend is device or numpy (got %r)" % (backend,))
-    table = ktable.pressure_table()
-    for c in pressure_codes:
-        if c not in table:
-            raise IOError("cia: pressure code %r is not in the table (n800 ... p400)" % (c,))
-    for t in temps:
-        if int(t) != t:
-            raise IOError("cia: the temperature %r is not an integer in K" % (t,))
-    temps, pressures = [int(t) for t in temps], [table[c] for c in pressure_codes]
-    n_points = chunk_limits(0, int(numax), dnu)[0][2]
-    _check_node_inputs(temps, pressures, (0.0, dnu, n_points), partner_mass)
-    if n_points > MAX_TABLE_POINTS:
-        raise IOError("cia: %d spectral points, the k-table's kernel takes 1 ... %d" % (n_points, MAX_TABLE_POINTS))
-    source = CiaSlabs(bands_of(blocks), temps, pressures, numax, dnu, n_points, partner_mass, nodes_per_launch)
-    out = ktable.build_table(source, inter, n_gauss, "hip" if backend == "device" else "numpy", ctx, source.nodes_per_launch,
-                             ktable.LDS_POINTS if lds_points is None else lds_points, target, timing)
+    out, source = _nodes.node_ktable(
+        "cia", backend, temps, pressure_codes, numax, dnu, lambda t, p, nu_grid: _check_node_inputs(t, p, nu_grid, partner_mass),
+        lambda t, p, n_points: CiaSlabs(bands_of(blocks), t, p, numax, dnu, n_points, partner_mass, nodes_per_launch),
+        inter, n_gauss, target, ctx, lds_points, timing, GRID_TOOL)
     if timing is not None:
-        timing["nodes_ms"] = source.ms
+        timing["nodes_ms"] = float(source.ms[0])
     return out
 
 
@@ -470,52 +387,11 @@ def parse_args(argv=None):
     p = argparse.ArgumentParser(prog="cia.py", description="collision-induced absorption of a pair from a HITRAN CIA file")
     p.add_argument("-name", required=True, help="of the species, as in species_data.py: CIA_H2H2, CIA_H2He, ...")
     p.add_argument("-cia_file", required=True)
-    p.add_argument("-temperatures", required=True, help="integers in K, separated by blanks")
-    p.add_argument("-pressure_codes", required=True, help="HELIOS-K's codes, n800 ... p400, separated by blanks")
-    p.add_argument("-numin", type=int, default=0)
-    p.add_argument("-numax", type=int, required=True)
-    p.add_argument("-dnu", type=float, required=True)
-    p.add_argument("-output_directory", default=None, help="of the files; required without -ktable yes")
-    p.add_argument("-chunk_width", type=int, default=None)
-    p.add_argument("-output_format", default="binary", choices=("binary", "text"))
+    _nodes.add_node_options(p)
     p.add_argument("-partner_mass", type=float, default=None, help="g/mol; by default the weight of -name in species_data.py")
     p.add_argument("-bands", default=None, help="indices in the printed list of the bands to take, separated by blanks")
-    p.add_argument("-backend", default="device", choices=("device", "numpy"))
-    p.add_argument("-ktable", default="no", choices=("yes", "no"),
-                   help="the species' k-table in place of the files; the options below are ktable.py's")
-    p.add_argument("-grid_format", default="fixed_resolution")
-    p.add_argument("-wavelength_grid", default="50 0.34 200")
-    p.add_argument("-path_to_grid_file", default=None)
-    p.add_argument("-number_of_gaussian_points", type=int, default=20)
-    p.add_argument("-directory_with_individual_files", default="./output/")
-    p.add_argument("-interpolate", default="yes", choices=("yes", "no"))
-    p.add_argument("-temperature_grid", default=None)
-    p.add_argument("-pressure_grid", default=None)
-    p.add_argument("-container", default="h5", choices=("h5", "npz"))
-    p.add_argument("-nodes_per_launch", type=int, default=4)
-    opt = p.parse_args(argv)
-    if opt.ktable == "no" and opt.output_directory is None:
-        p.error("the following arguments are required: -output_directory")
-    return opt
-
-
-def _refuse_with_ktable(opt):
-    if opt.numin != 0:
-        raise IOError("cia: -ktable yes with -numin %d: the k-table's wavelength axis starts at 0 cm^-1, and ktable.py refuses a "
-                      "directory whose first chunk does not" % opt.numin)
-    if opt.chunk_width is not None:
-        raise IOError("cia: -ktable yes with -chunk_width %d: the table is built from the one chunk 0 ... numax; a chunk's points "
-                      "are lo + i dnu, which are other bits than 0 + i dnu" % opt.chunk_width)
-    if opt.output_format != "binary":
-        raise IOError("cia: -ktable yes with -output_format %s: no opacity file is written, the fp32 opacities stay on the device"
-                      % opt.output_format)
-    if opt.output_directory is not None:
-        raise IOError("cia: -ktable yes with -output_directory %s: a call writes the files or the table, not both; the table goes "
-                      "to -directory_with_individual_files" % opt.output_directory)
-    if opt.number_of_gaussian_points < 1:
-        raise IOError("cia: -number_of_gaussian_points is an integer >= 1")
-    if opt.nodes_per_launch < 1:
-        raise IOError("cia: -nodes_per_launch is an integer >= 1")
+    _nodes.add_ktable_options(p)
+    return _nodes.parse_node_args(p, argv)
 
 
 def parse_bands(text):
@@ -527,44 +403,16 @@ def parse_bands(text):
         raise IOError("cia: -bands %r: indices in the printed list, separated by blanks" % (text,))
 
 
-def _main_ktable(opt, bands, temps, codes, partner_mass, t0):
-    """-ktable yes: `<name>_opac_kdistr` and, with -interpolate yes, `<name>_opac_ip_kdistr`"""
-    from . import ktable
-    inter = ktable.wavelength_grid(opt.grid_format, opt.wavelength_grid.split(), opt.path_to_grid_file)
-    target = ktable.target_grid(opt.temperature_grid, opt.pressure_grid) if opt.interpolate == "yes" else None
-    timing = {}
-    blocks = [b for band in bands for b in band.blocks]
-    native, table_ip = cia_ktable(blocks, temps, codes, opt.numax, opt.dnu, inter, opt.number_of_gaussian_points, partner_mass, target,
-                                  opt.backend, None, opt.nodes_per_launch, None, timing)
-    stem = os.path.join(opt.directory_with_individual_files, opt.name)
-    written = [ktable.write_table("%s_opac_kdistr.%s" % (stem, opt.container), native)]
-    if table_ip is not None:
-        written.append(ktable.write_table("%s_opac_ip_kdistr.%s" % (stem, opt.container), table_ip))
-    how = "numpy" if opt.backend == "numpy" else "k_cia_nodes %.1f ms, k_ktable_bins %.1f ms" % (timing["nodes_ms"],
-                                                                                               timing["device_ms"][0])
-    print("cia: %d nodes of %d points into %d bins x %d Gauss points, %s, %.2f s -> %s" % (
-        timing["points"], chunk_limits(0, opt.numax, opt.dnu)[0][2], len(inter) - 1, opt.number_of_gaussian_points, how,
-        time.time() - t0, ", ".join(written)))
-    return written
-
-
 def main(argv=None):
     """cia.py: the directory of one pair, or with -ktable yes its k-table; returns the paths written"""
     opt = parse_args(argv)
     t0 = time.time()
-    temps = parse_temperatures(opt.temperatures)
-    codes, pressures = parse_pressure_codes(opt.pressure_codes)
+    temps = _nodes.parse_temperatures(GRID_TOOL, opt.temperatures)
+    codes, pressures = _nodes.parse_pressure_codes(GRID_TOOL, opt.pressure_codes)
     if opt.ktable == "yes":
-        _refuse_with_ktable(opt)
-    chunks = chunk_limits(opt.numin, opt.numax, opt.dnu, opt.chunk_width)
-    partner_mass = opt.partner_mass
-    if partner_mass is None:
-        from .species_data import species_lib
-        if opt.name not in species_lib:
-            raise IOError("cia: no partner mass: %r is not in species_data.py, give -partner_mass" % (opt.name,))
-        partner_mass = species_lib[opt.name].weight
-    if not (np.isfinite(partner_mass) and partner_mass > 0):
-        raise IOError("cia: no partner mass: -partner_mass %r is not > 0 g/mol" % (partner_mass,))
+        _nodes.refuse_with_ktable("cia", opt)
+    chunks = _nodes.chunk_limits(GRID_TOOL, opt.numin, opt.numax, opt.dnu, opt.chunk_width)
+    partner_mass = _nodes.mass_of("cia", opt.name, opt.partner_mass, "partner")
     wanted = parse_bands(opt.bands)
     blocks, negatives = read_cia_file(opt.cia_file)
     listed = group_bands(blocks)
@@ -577,36 +425,17 @@ def main(argv=None):
         if n:
             print("cia: %d of the %d node temperatures lie outside %.17g ... %.17g K of band %d: the band is constant in T there"
                   % (n, len(temps), band.blocks[0].temp, band.blocks[-1].temp, listed.index(band)))
-    if opt.ktable == "yes":
-        return _main_ktable(opt, bands, temps, codes, partner_mass, t0)
-    if opt.numin != 0:
-        print("cia: -numin %d is not 0: ktable.py will refuse the directory" % opt.numin)
-    directory = os.path.join(str(opt.output_directory), "")
-    os.makedirs(directory, exist_ok=True)
-    ending = ".bin" if opt.output_format == "binary" else ".dat"
     kept = [b for band in bands for b in band.blocks]
+    if opt.ktable == "yes":
+        return _nodes.main_ktable(
+            "cia", opt,
+            lambda inter, target, timing: cia_ktable(kept, temps, codes, opt.numax, opt.dnu, inter, opt.number_of_gaussian_points,
+                                                     partner_mass, target, opt.backend, None, opt.nodes_per_launch, None, timing),
+            lambda timing: "k_cia_nodes %.1f ms, k_ktable_bins %.1f ms" % (timing["nodes_ms"], timing["device_ms"][0]), t0)
     n_nodes = len(temps) * len(codes)
-    ctx = handle = None
-    timing, written = {}, []
-    try:
-        if opt.backend == "device":
-            from .device import Context
-            ctx = Context(int(os.environ.get("HELIOS_DEVICE", "0")))
-            handle = CiaOpacity(ctx, bands, max(c[2] for c in chunks), max(1, min(opt.nodes_per_launch, n_nodes)), n_nodes, True)
-        for lo, hi, n in chunks:
-            kappa = cia_opacity(kept, temps, pressures, (float(lo), opt.dnu, n), partner_mass, opt.backend, ctx, opt.nodes_per_launch,
-                                handle, timing)
-            nu = float(lo) + np.arange(n, dtype=np.float64) * opt.dnu
-            for it, t in enumerate(temps):
-                for jp, code in enumerate(codes):
-                    written.append(directory + file_name(opt.name, lo, hi, t, code, ending))
-                    write_file(written[-1], nu, kappa[it, jp], opt.output_format)
-    finally:
-        if handle is not None:
-            handle.close()
-        if ctx is not None:
-            ctx.close()
-    how = "numpy" if opt.backend == "numpy" else "k_cia_nodes %.1f ms" % timing["nodes_ms"]
-    print("cia: %d nodes x %d chunks, %s, %.2f s -> %d files in %s" % (n_nodes, len(chunks), how, time.time() - t0, len(written),
-                                                                       directory))
-    return written
+    return _nodes.main_files(
+        "cia", opt, chunks, temps, codes,
+        lambda ctx, n_points_max: CiaOpacity(ctx, bands, n_points_max, max(1, min(opt.nodes_per_launch, n_nodes)), n_nodes, True),
+        lambda nu_grid, ctx, handle, timing: cia_opacity(kept, temps, pressures, nu_grid, partner_mass, opt.backend, ctx,
+                                                         opt.nodes_per_launch, handle, timing),
+        lambda timing: "k_cia_nodes %.1f ms" % timing["nodes_ms"], t0)

@@ -78,21 +78,21 @@ k-table's axis with numax / points; the nodes sorted ascending and de-duplicated
 limit of 2^28 points stand before the first launch; the fp32 slabs stay on the device for k_ktable_bins.  The containers are the
 ones `exomol.py` followed by `ktable.py` writes, to the bit.  Refused with `-ktable yes`: `-numin` other than 0, `-chunk_width`,
 `-output_format text`, `-output_directory`.
+
+The frame around the readers and the contract is _nodes.py's, shared with lines.py and cia.py.
 """
 import argparse
 import bz2
-import ctypes
-import os
 import time
 import warnings
 
 import numpy as np
 
+from . import _nodes
 from . import phys_const as pc
 from ._tool import DeviceObject, dp, ip
-from .lines import (DEFAULT_CUTOFF, INV_SQRT_PI, LDS_BLOCK, LN2, MAX_TABLE_POINTS, TILE_POINTS, T_REF, WAVEFRONT, Y_MIN, chunk_limits,
-                    count_pairs, file_name, numpy_node, parse_pressure_codes, parse_temperatures, partition_value,
-                    read_partition_function, write_file)
+from .lines import (DEFAULT_CUTOFF, INV_SQRT_PI, LDS_BLOCK, LN2, TILE_POINTS, T_REF, WAVEFRONT, Y_MIN, count_pairs, numpy_node,
+                    partition_value, read_partition_function)
 
 BAR = 1.0e6                           # dyne cm^-2
 DEFAULT_BROADENING = (0.07, 0.5)      # gamma [cm^-1 bar^-1 at 296 K], n
@@ -100,6 +100,7 @@ COMPACT_BLOCK = 256                   # csrc/exomol.hip: EXO_B, the count kernel
 JIDX_MAX = 1 << 20
 RANGE_WIDEN = (1e-12, 1e-9)           # lines_tile_ranges: reach * (1 + 1e-12) + 1e-9 (super-lines: + d)
 CELL_LIMIT = 2.0 ** 31                # cells are numbered by an int
+GRID_TOOL = "lines"                   # the refusals of the grid and of the node lists came from lines.py with its word, and keep it
 
 
 # ---- the inputs --------------------------------------------------------------------------------------------------------
@@ -319,12 +320,7 @@ def node_params(states, trans, broadening, temp, press, q_t, molar_mass, s_min=0
         return node["params"], node["kept"]
     strength = strengths(states, trans, temp, q_t)
     kept = np.nonzero(strength >= s_min)[0]
-    x, table = broadening
-    nu0, jx = trans["nu0"][kept], states["jidx"][trans["low"][kept]]
-    total = np.zeros(len(kept))
-    for b in range(len(x)):
-        total = total + x[b] * table[b, jx, 0] * (T_REF / temp) ** table[b, jx, 1]
-    gamma = (press / BAR) * total
+    nu0, gamma = trans["nu0"][kept], _gamma(states, trans, broadening, kept, temp, press)
     alpha = (nu0 / pc.C) * np.sqrt(2.0 * LN2 * pc.N_A * pc.K_B * temp / molar_mass)
     a = np.sqrt(LN2) / alpha
     y = np.maximum(a * gamma, Y_MIN)
@@ -424,7 +420,7 @@ def tile_ranges(nu, nu_first, dnu, n_points, cutoff, step=0.0):
 
 
 # ---- device ------------------------------------------------------------------------------------------------------------
-class ExomolOpacity(DeviceObject):
+class ExomolOpacity(_nodes.NodeOpacity):
     """hx_exomol: resident states, broadening table and sorted transitions; nodes of up to n_points_max spectral points,
     nodes_per_launch per launch into fp32 slabs that stay on the device; `with_fp64`: the rows before rounding as well"""
 
@@ -455,21 +451,21 @@ class ExomolOpacity(DeviceObject):
         e, g = (np.ascontiguousarray(states[k], np.float64).reshape(-1) for k in ("E", "g"))
         jidx = np.ascontiguousarray(states["jidx"], np.int32).reshape(-1)
         assert len(e) == len(g) == len(jidx)
-        self.n_nodes = self.rows_run = 0
+        self._reset_nodes()
         self._call("set_states", len(e), dp(e), dp(g), ip(jidx))
 
     def set_broadening(self, fractions, table):
         x = np.ascontiguousarray(fractions, np.float64).reshape(-1)
         t = np.ascontiguousarray(table, np.float64)
         assert t.ndim == 3 and t.shape[0] == len(x) and t.shape[2] == 2
-        self.n_nodes = self.rows_run = 0
+        self._reset_nodes()
         self._call("set_broadening", len(x), t.shape[1], dp(x), dp(t.reshape(-1)))
 
     def set_transitions(self, trans):
         up, low = (np.ascontiguousarray(trans[k], np.int32).reshape(-1) for k in ("up", "low"))
         a = np.ascontiguousarray(trans["A"], np.float64).reshape(-1)
         assert len(up) == len(low) == len(a)
-        self.n_nodes = self.rows_run = 0
+        self._reset_nodes()
         self.superlines = None                               # the library drops them with the list
         self._call("set_transitions", len(a), ip(up), ip(low), dp(a))
 
@@ -477,7 +473,7 @@ class ExomolOpacity(DeviceObject):
         """S_sl and d for the list the handle holds; step = 0 (or None) turns super-lines off.  The nodes are set after it"""
         step = 0.0 if step is None else float(step)
         threshold = 0.0 if threshold is None else float(threshold)
-        self.n_nodes = self.rows_run = 0
+        self._reset_nodes()
         self.superlines = None
         self._call("set_superlines", threshold, step)
         self.superlines = (threshold, step) if step > 0 else None
@@ -486,21 +482,10 @@ class ExomolOpacity(DeviceObject):
         """T, P and Q(T) per node, and what the nodes share"""
         arr = [np.ascontiguousarray(a, np.float64).reshape(-1) for a in (temps, pressures, q_t)]
         assert len(arr[0]) == len(arr[1]) == len(arr[2])
-        self.n_nodes = self.rows_run = 0
+        self._reset_nodes()
         self._call("set_nodes", len(arr[0]), dp(arr[0]), dp(arr[1]), dp(arr[2]), float(molar_mass), float(cutoff), float(s_min),
                    float(nu_first), float(dnu), int(n_points))
         self.n_nodes, self.n_points = len(arr[0]), int(n_points)
-
-    def run_nodes(self, first, n):
-        """queues nodes first ... first + n - 1 into rows 0 ... n - 1; returns at once"""
-        self._call("run_nodes", int(first), int(n))
-        self.rows_run = int(n)
-
-    def slab_pointer(self):
-        """device address of the fp32 slabs [nodes_per_launch][...], rows of the last run_nodes with the stride n_points"""
-        p = ctypes.c_void_p()
-        self._call("device_ptr", b"slabs32", ctypes.byref(p))
-        return p
 
     def get(self, name):
         """"line_params": a list of [4][kept[row]] per row of the last launch; with super-lines [4][strong + super-lines]"""
@@ -525,24 +510,12 @@ class ExomolOpacity(DeviceObject):
 
 # ---- the library functions -----------------------------------------------------------------------------------------------
 def _check_node_inputs(temps, pressures, nu_grid, molar_mass, cutoff, s_min):
-    temps = np.asarray(temps, np.float64).reshape(-1)
-    pressures = np.asarray(pressures, np.float64).reshape(-1)
-    if len(temps) == 0 or not np.all(np.isfinite(temps) & (temps > 0)):
-        raise ValueError("exomol: every temperature is a finite number > 0 (got %r)" % (temps.tolist(),))
-    if len(pressures) == 0 or not np.all(np.isfinite(pressures) & (pressures > 0)):
-        raise ValueError("exomol: every pressure is a finite number > 0 dyne cm^-2 (got %r)" % (pressures.tolist(),))
-    nu_first, dnu, n_points = float(nu_grid[0]), float(nu_grid[1]), int(nu_grid[2])
-    if not (np.isfinite(dnu) and dnu > 0):
-        raise ValueError("exomol: dnu = %r is not > 0" % (dnu,))
-    if n_points < 1 or not np.isfinite(nu_first):
-        raise ValueError("exomol: the grid (nu_first, dnu, points) = %r needs a finite start and at least one point" % (tuple(nu_grid),))
-    if molar_mass is None or not (np.isfinite(molar_mass) and molar_mass > 0):
-        raise ValueError("exomol: no molar mass (got %r): give one > 0 g/mol" % (molar_mass,))
+    out = _nodes.check_node_inputs("exomol", temps, pressures, nu_grid, molar_mass)
     if not (np.isfinite(cutoff) and cutoff > 0):
         raise ValueError("exomol: the cut-off %r is not > 0 cm^-1" % (cutoff,))
     if not (np.isfinite(s_min) and s_min >= 0):
         raise ValueError("exomol: the strength cut-off %r is not a finite number >= 0 cm / molecule" % (s_min,))
-    return temps, pressures, (nu_first, dnu, n_points)
+    return out
 
 
 def exomol_opacity(states, trans, broadening, q_table, temps, pressures_cgs, nu_grid, molar_mass=None, cutoff=DEFAULT_CUTOFF,
@@ -553,8 +526,7 @@ def exomol_opacity(states, trans, broadening, q_table, temps, pressures_cgs, nu_
     that already holds the three inputs.  `timing` receives prepare_ms, sum_ms and pairs, summed over the nodes, and `kept`, the
     number of transitions kept per node [T][P].  `superline_threshold`, `superline_step`: S_sl and d (d defaults to dnu); `timing`
     then also receives `strong`, `weak` and `superlines` per node [T][P], and a `handle` given is set to them"""
-    if backend not in ("device", "numpy"):
-        raise ValueError("exomol: backend is device or numpy (got %r)" % (backend,))
+    _nodes.check_backend("exomol", backend)
     s_min = float(strength_cutoff)
     temps, pressures, (nu_first, dnu, n_points) = _check_node_inputs(temps, pressures_cgs, nu_grid, molar_mass, cutoff, s_min)
     sl = check_superlines(superline_threshold, superline_step, cutoff, trans["nu0"][-1], dnu)
@@ -577,40 +549,25 @@ def exomol_opacity(states, trans, broadening, q_table, temps, pressures_cgs, nu_
                 if timing is not None:
                     pairs += count_pairs(prm[0], nu_first, dnu, n_points, cutoff)
     else:
-        own_ctx, own_handle = ctx is None and handle is None, handle is None
-        if own_ctx:
-            from .device import Context
-            ctx = Context(int(os.environ.get("HELIOS_DEVICE", "0")))
-        try:
-            nodes = [(t, p, q_t[it]) for it, t in enumerate(temps) for p in pressures]
-            if own_handle:
-                handle = ExomolOpacity.of(ctx, states, trans, broadening, n_points, max(1, min(int(nodes_per_launch), len(nodes))),
-                                          len(nodes), True)
-            try:
-                if handle.superlines != sl:                                  # a plain handle in a plain call stays untouched
-                    handle.set_superlines(*(sl or (0.0, 0.0)))
-                per = handle.nodes_per_launch
-                flat, flat_kept, flat_counts = out.reshape(len(nodes), n_points), kept.reshape(-1), counts.reshape(-1, 3)
-                for lo in range(0, len(nodes), handle.n_nodes_max):          # a handle made for fewer nodes takes them in turns
-                    part = nodes[lo:lo + handle.n_nodes_max]
-                    handle.set_nodes([n[0] for n in part], [n[1] for n in part], [n[2] for n in part], molar_mass, cutoff, s_min,
-                                     nu_first, dnu, n_points)
-                    for first in range(0, len(part), per):
-                        n = min(per, len(part) - first)
-                        handle.run_nodes(first, n)
-                        flat[lo + first:lo + first + n] = handle.get("kappa64")
-                        flat_kept[lo + first:lo + first + n] = handle.get("kept")
-                        if sl is not None:
-                            flat_counts[lo + first:lo + first + n] = handle.get("superline_counts")
-                        if timing is not None:
-                            pairs += sum(count_pairs(prm[0], nu_first, dnu, n_points, cutoff) for prm in handle.get("line_params"))
-                    ms += handle.get("timing_ms")
-            finally:
-                if own_handle:
-                    handle.close()
-        finally:
-            if own_ctx:
-                ctx.close()
+        nodes = [(t, p, q_t[it]) for it, t in enumerate(temps) for p in pressures]
+        flat, flat_kept, flat_counts = out.reshape(len(nodes), n_points), kept.reshape(-1), counts.reshape(-1, 3)
+
+        def set_nodes(h, part):
+            if h.superlines != sl:                                           # a plain handle in a plain call stays untouched
+                h.set_superlines(*(sl or (0.0, 0.0)))
+            h.set_nodes([n[0] for n in part], [n[1] for n in part], [n[2] for n in part], molar_mass, cutoff, s_min, nu_first, dnu,
+                        n_points)
+
+        def collect(h, rows):
+            nonlocal pairs
+            flat[rows], flat_kept[rows] = h.get("kappa64"), h.get("kept")
+            if sl is not None:
+                flat_counts[rows] = h.get("superline_counts")
+            if timing is not None:
+                pairs += sum(count_pairs(prm[0], nu_first, dnu, n_points, cutoff) for prm in h.get("line_params"))
+        ms = _nodes.nodes_in_turns(
+            ctx, handle, lambda c: ExomolOpacity.of(c, states, trans, broadening, n_points, max(1, min(int(nodes_per_launch), len(nodes))),
+                                                    len(nodes), True), nodes, set_nodes, collect)
     if timing is not None:
         timing["prepare_ms"] = timing.get("prepare_ms", 0.0) + float(ms[0])
         timing["sum_ms"] = timing.get("sum_ms", 0.0) + float(ms[1])
@@ -622,71 +579,44 @@ def exomol_opacity(states, trans, broadening, q_table, temps, pressures_cgs, nu_
 
 
 # ---- from the line list to the k-table -----------------------------------------------------------------------------------
-class ExomolSlabs(object):
-    """ktable.build_table's slabs from an ExoMol list: one chunk 0 ... numax of `n_points` points, the nodes sorted ascending and
-    de-duplicated as ktable.SpeciesFiles does (node = p + np * t).  On the device the slabs never leave it; `ms` holds the kernel
-    times and `kept` the transitions kept per node once the table is built"""
+class ExomolSlabs(_nodes.NodeSlabs):
+    """ktable.build_table's slabs from an ExoMol list (_nodes.NodeSlabs); `ms` holds the kernel times and `kept` the transitions
+    kept per node once the table is built"""
+
+    TOOL = "exomol"
 
     def __init__(self, states, trans, broadening, q_table, temps, pressures, numax, dnu, n_points, molar_mass, cutoff, s_min,
                  nodes_per_launch=4, superline_threshold=None, superline_step=None):
         self.superlines = check_superlines(superline_threshold, superline_step, cutoff, trans["nu0"][-1], dnu)
         self.counts = []                                             # per node (strong, weak, super-lines), with super-lines
+        _nodes.NodeSlabs.__init__(self, temps, pressures, numax, dnu, n_points, nodes_per_launch)
         self.states, self.trans, self.broadening = states, trans, broadening
-        self.numax, self.dnu, self.n_points = int(numax), float(dnu), int(n_points)
-        self.temps, self.press = sorted(set(temps)), sorted(set(pressures))
         self.molar_mass, self.cutoff, self.s_min = molar_mass, cutoff, float(s_min)
         self.q_t = [partition_value(q_table, t) for t in self.temps]
-        self.nodes_per_launch = max(1, int(nodes_per_launch))
-        self.handle, self.ms, self.kept = None, np.zeros(2), []
+        self.kept = []
 
-    def axis(self):
-        return 0, self.numax, self.numax / self.n_points           # ktable.SpeciesFiles.resolution() of the file not written
+    def host_slab(self, it, t, p):
+        if self.superlines is None:
+            prm, idx = node_params(self.states, self.trans, self.broadening, t, p, self.q_t[it], self.molar_mass, self.s_min)
+        else:
+            node = superline_node(self.states, self.trans, self.broadening, t, p, self.q_t[it], self.molar_mass, self.s_min,
+                                  *self.superlines)
+            prm, idx = node["params"], node["kept"]
+            self.counts.append((len(node["strong"]), len(node["weak"]), len(node["cells"])))
+        self.kept.append(len(idx))
+        return numpy_node(prm, 0.0, self.dnu, self.n_points, self.cutoff, self.molar_mass)
 
-    def _check(self, n_points):
-        if n_points != self.n_points:
-            raise IOError("exomol: the k-table's axis 0 ... %d cm^-1 at %.17g cm^-1 has %d points, the line kernel's grid at "
-                          "-dnu %.17g has %d" % (self.numax, self.numax / self.n_points, n_points, self.dnu, self.n_points))
-
-    def host_slabs(self, pool, n_points):
-        self._check(n_points)
-        for it, t in enumerate(self.temps):
-            for p in self.press:
-                if self.superlines is None:
-                    prm, idx = node_params(self.states, self.trans, self.broadening, float(t), p, self.q_t[it], self.molar_mass,
-                                           self.s_min)
-                else:
-                    node = superline_node(self.states, self.trans, self.broadening, float(t), p, self.q_t[it], self.molar_mass,
-                                          self.s_min, *self.superlines)
-                    prm, idx = node["params"], node["kept"]
-                    self.counts.append((len(node["strong"]), len(node["weak"]), len(node["cells"])))
-                self.kept.append(len(idx))
-                yield numpy_node(prm, 0.0, self.dnu, self.n_points, self.cutoff, self.molar_mass).astype(np.float32)
-
-    def feed(self, b, pool, n_points):
-        self._check(n_points)
-        nodes = [(float(t), p, self.q_t[it]) for it, t in enumerate(self.temps) for p in self.press]
-        per = min(self.nodes_per_launch, b.max_tp)
-        self.handle = h = ExomolOpacity.of(b.ctx, self.states, self.trans, self.broadening, self.n_points, per, len(nodes))
+    def open_handle(self, ctx, per, nodes):
+        self.handle = h = ExomolOpacity.of(ctx, self.states, self.trans, self.broadening, self.n_points, per, len(nodes))
         if self.superlines is not None:
             h.set_superlines(*self.superlines)
-        h.set_nodes([n[0] for n in nodes], [n[1] for n in nodes], [n[2] for n in nodes], self.molar_mass, self.cutoff, self.s_min,
-                    0.0, self.dnu, self.n_points)
-        slabs = h.slab_pointer()
-        for first in range(0, len(nodes), per):
-            n = min(per, len(nodes) - first)
-            h.run_nodes(first, n)
-            b.run_device(slabs, n, first)
-            self.kept.extend(int(k) for k in h.get("kept"))        # after the launch's sort is queued: the counts are the tool's report
-            if self.superlines is not None:
-                self.counts.extend(tuple(int(v) for v in row) for row in h.get("superline_counts"))
+        h.set_nodes([n[1] for n in nodes], [n[2] for n in nodes], [self.q_t[n[0]] for n in nodes], self.molar_mass, self.cutoff,
+                    self.s_min, 0.0, self.dnu, self.n_points)
 
-    def close(self):
-        h, self.handle = self.handle, None
-        if h is not None:
-            try:
-                self.ms = h.get("timing_ms")
-            finally:
-                h.close()
+    def after_launch(self, h):
+        self.kept.extend(int(k) for k in h.get("kept"))            # after the launch's sort is queued: the counts are the tool's report
+        if self.superlines is not None:
+            self.counts.extend(tuple(int(v) for v in row) for row in h.get("superline_counts"))
 
 
 def exomol_ktable(states, trans, broadening, q_table, temps, pressure_codes, numax, dnu, inter, n_gauss, molar_mass=None,
@@ -697,25 +627,12 @@ def exomol_ktable(states, trans, broadening, q_table, temps, pressure_codes, num
     files.  `temps`: integers in K; `pressure_codes`: keys of ktable.pressure_table(); the range is 0 ... numax in one chunk.
     `timing` receives prepare_ms, sum_ms, kept (per node, node = p + np t) and build_table's entries; with super-lines
     (`superline_threshold`, `superline_step`, which defaults to dnu) also strong, weak and superlines per node"""
-    from . import ktable
-    if backend not in ("device", "numpy"):
-        raise ValueError("exomol: backend is device or numpy (got %r)" % (backend,))
-    table = ktable.pressure_table()
-    for c in pressure_codes:
-        if c not in table:
-            raise IOError("exomol: pressure code %r is not in the table (n800 ... p400)" % (c,))
-    for t in temps:
-        if int(t) != t:
-            raise IOError("exomol: the temperature %r is not an integer in K" % (t,))
-    temps, pressures = [int(t) for t in temps], [table[c] for c in pressure_codes]
-    n_points = chunk_limits(0, int(numax), dnu)[0][2]
-    _check_node_inputs(temps, pressures, (0.0, dnu, n_points), molar_mass, cutoff, float(strength_cutoff))
-    if n_points > MAX_TABLE_POINTS:
-        raise IOError("exomol: %d spectral points, the k-table's kernel takes 1 ... %d" % (n_points, MAX_TABLE_POINTS))
-    source = ExomolSlabs(states, trans, broadening, q_table, temps, pressures, numax, dnu, n_points, molar_mass, cutoff,
-                         strength_cutoff, nodes_per_launch, superline_threshold, superline_step)
-    out = ktable.build_table(source, inter, n_gauss, "hip" if backend == "device" else "numpy", ctx, source.nodes_per_launch,
-                             ktable.LDS_POINTS if lds_points is None else lds_points, target, timing)
+    out, source = _nodes.node_ktable(
+        "exomol", backend, temps, pressure_codes, numax, dnu,
+        lambda t, p, nu_grid: _check_node_inputs(t, p, nu_grid, molar_mass, cutoff, float(strength_cutoff)),
+        lambda t, p, n_points: ExomolSlabs(states, trans, broadening, q_table, t, p, numax, dnu, n_points, molar_mass, cutoff,
+                                           strength_cutoff, nodes_per_launch, superline_threshold, superline_step),
+        inter, n_gauss, target, ctx, lds_points, timing, GRID_TOOL)
     if timing is not None:
         timing["prepare_ms"], timing["sum_ms"], timing["kept"] = float(source.ms[0]), float(source.ms[1]), list(source.kept)
         if source.superlines is not None:
@@ -736,52 +653,11 @@ def parse_args(argv=None):
     p.add_argument("-superline_threshold", type=float, default=None,
                    help="S_sl in cm / molecule: per node, kept transitions below it are merged per cell into super-lines")
     p.add_argument("-superline_step", type=float, default=None, help="the cell width d in cm^-1; -dnu unless given")
-    p.add_argument("-temperatures", required=True, help="integers in K, separated by blanks")
-    p.add_argument("-pressure_codes", required=True, help="HELIOS-K's codes, n800 ... p400, separated by blanks")
-    p.add_argument("-numin", type=int, default=0)
-    p.add_argument("-numax", type=int, required=True)
-    p.add_argument("-dnu", type=float, required=True)
-    p.add_argument("-output_directory", default=None, help="of the files; required without -ktable yes")
-    p.add_argument("-chunk_width", type=int, default=None)
-    p.add_argument("-output_format", default="binary", choices=("binary", "text"))
+    _nodes.add_node_options(p)
     p.add_argument("-molar_mass", type=float, default=None)
     p.add_argument("-cutoff", type=float, default=DEFAULT_CUTOFF)
-    p.add_argument("-backend", default="device", choices=("device", "numpy"))
-    p.add_argument("-ktable", default="no", choices=("yes", "no"),
-                   help="the species' k-table in place of the files; the options below are ktable.py's")
-    p.add_argument("-grid_format", default="fixed_resolution")
-    p.add_argument("-wavelength_grid", default="50 0.34 200")
-    p.add_argument("-path_to_grid_file", default=None)
-    p.add_argument("-number_of_gaussian_points", type=int, default=20)
-    p.add_argument("-directory_with_individual_files", default="./output/")
-    p.add_argument("-interpolate", default="yes", choices=("yes", "no"))
-    p.add_argument("-temperature_grid", default=None)
-    p.add_argument("-pressure_grid", default=None)
-    p.add_argument("-container", default="h5", choices=("h5", "npz"))
-    p.add_argument("-nodes_per_launch", type=int, default=4)
-    opt = p.parse_args(argv)
-    if opt.ktable == "no" and opt.output_directory is None:
-        p.error("the following arguments are required: -output_directory")
-    return opt
-
-
-def _refuse_with_ktable(opt):
-    if opt.numin != 0:
-        raise IOError("exomol: -ktable yes with -numin %d: the k-table's wavelength axis starts at 0 cm^-1, and ktable.py refuses "
-                      "a directory whose first chunk does not" % opt.numin)
-    if opt.chunk_width is not None:
-        raise IOError("exomol: -ktable yes with -chunk_width %d: the table is built from the one chunk 0 ... numax; a chunk's "
-                      "points are lo + i dnu, which are other bits than 0 + i dnu" % opt.chunk_width)
-    if opt.output_format != "binary":
-        raise IOError("exomol: -ktable yes with -output_format %s: no opacity file is written, the fp32 opacities stay on the "
-                      "device" % opt.output_format)
-    if opt.output_directory is not None:
-        raise IOError("exomol: -ktable yes with -output_directory %s: a call writes the files or the table, not both; the table "
-                      "goes to -directory_with_individual_files" % opt.output_directory)
-    if opt.number_of_gaussian_points < 1:
-        raise IOError("exomol: -number_of_gaussian_points is an integer >= 1")
-    if opt.nodes_per_launch < 1:
-        raise IOError("exomol: -nodes_per_launch is an integer >= 1")
+    _nodes.add_ktable_options(p)
+    return _nodes.parse_node_args(p, argv)
 
 
 def _print_kept(kept, nodes, n_trans, timing=None):
@@ -794,39 +670,15 @@ def _print_kept(kept, nodes, n_trans, timing=None):
         print("exomol: %d K, %s: %d of %d transitions kept%s" % (t, code, int(k), n_trans, more))
 
 
-def _main_ktable(opt, states, trans, broadening, q_table, temps, codes, molar_mass, t0):
-    """-ktable yes: `<name>_opac_kdistr` and, with -interpolate yes, `<name>_opac_ip_kdistr`"""
-    from . import ktable
-    inter = ktable.wavelength_grid(opt.grid_format, opt.wavelength_grid.split(), opt.path_to_grid_file)
-    target = ktable.target_grid(opt.temperature_grid, opt.pressure_grid) if opt.interpolate == "yes" else None
-    timing = {}
-    native, table_ip = exomol_ktable(states, trans, broadening, q_table, temps, codes, opt.numax, opt.dnu, inter,
-                                     opt.number_of_gaussian_points, molar_mass, opt.cutoff, opt.strength_cutoff, target, opt.backend,
-                                     None, opt.nodes_per_launch, None, timing, opt.superline_threshold, opt.superline_step)
-    table = ktable.pressure_table()
-    by_pressure = sorted(set(codes), key=lambda c: table[c])
-    _print_kept(timing["kept"], [(t, c) for t in sorted(set(temps)) for c in by_pressure], len(trans["nu0"]), timing)
-    stem = os.path.join(opt.directory_with_individual_files, opt.name)
-    written = [ktable.write_table("%s_opac_kdistr.%s" % (stem, opt.container), native)]
-    if table_ip is not None:
-        written.append(ktable.write_table("%s_opac_ip_kdistr.%s" % (stem, opt.container), table_ip))
-    how = "numpy" if opt.backend == "numpy" else "count to ranges %.1f ms, k_exomol_sum %.1f ms, k_ktable_bins %.1f ms" % (
-        timing["prepare_ms"], timing["sum_ms"], timing["device_ms"][0])
-    print("exomol: %d nodes of %d points into %d bins x %d Gauss points, %s, %.2f s -> %s" % (
-        timing["points"], chunk_limits(0, opt.numax, opt.dnu)[0][2], len(inter) - 1, opt.number_of_gaussian_points, how,
-        time.time() - t0, ", ".join(written)))
-    return written
-
-
 def main(argv=None):
     """exomol.py: the directory of one species, or with -ktable yes its k-table; returns the paths written"""
     opt = parse_args(argv)
     t0 = time.time()
-    temps = parse_temperatures(opt.temperatures)
-    codes, pressures = parse_pressure_codes(opt.pressure_codes)
+    temps = _nodes.parse_temperatures(GRID_TOOL, opt.temperatures)
+    codes, pressures = _nodes.parse_pressure_codes(GRID_TOOL, opt.pressure_codes)
     if opt.ktable == "yes":
-        _refuse_with_ktable(opt)
-    chunks = chunk_limits(opt.numin, opt.numax, opt.dnu, opt.chunk_width)
+        _nodes.refuse_with_ktable("exomol", opt)
+    chunks = _nodes.chunk_limits(GRID_TOOL, opt.numin, opt.numax, opt.dnu, opt.chunk_width)
     if not (np.isfinite(opt.strength_cutoff) and opt.strength_cutoff >= 0):
         raise IOError("exomol: -strength_cutoff %r is not a finite number >= 0 cm / molecule" % (opt.strength_cutoff,))
     if not (np.isfinite(opt.cutoff) and opt.cutoff > 0):
@@ -837,21 +689,14 @@ def main(argv=None):
         check_superlines(opt.superline_threshold, opt.superline_step, opt.cutoff, 0.0, opt.dnu)
     except ValueError as e:
         raise IOError(str(e))
-    molar_mass = opt.molar_mass
-    if molar_mass is None:
-        from .species_data import species_lib
-        if opt.name not in species_lib:
-            raise IOError("exomol: no molar mass: %r is not in species_data.py, give -molar_mass" % (opt.name,))
-        molar_mass = species_lib[opt.name].weight
-    if not (np.isfinite(molar_mass) and molar_mass > 0):
-        raise IOError("exomol: no molar mass: -molar_mass %r is not > 0 g/mol" % (molar_mass,))
+    molar_mass = _nodes.mass_of("exomol", opt.name, opt.molar_mass)
     entries = parse_broadeners(opt.broadeners, parse_default_broadening(opt.default_broadening))
     q_table = read_partition_function(opt.partition_function)
     try:
         for t in temps:
-            partition_value(q_table, t)
+            partition_value(q_table, t, "exomol")
     except ValueError as e:
-        raise IOError(str(e).replace("lines:", "exomol:", 1))
+        raise IOError(str(e))
     states = read_states(opt.states)
     t_parsed = time.time()
     trans, skipped = read_transitions(opt.trans.split(), states)
@@ -864,39 +709,27 @@ def main(argv=None):
     except ValueError as e:
         raise IOError(str(e))
     if opt.ktable == "yes":
-        return _main_ktable(opt, states, trans, broadening, q_table, temps, codes, molar_mass, t0)
-    if opt.numin != 0:
-        print("exomol: -numin %d is not 0: ktable.py will refuse the directory" % opt.numin)
-    directory = os.path.join(str(opt.output_directory), "")
-    os.makedirs(directory, exist_ok=True)
-    ending = ".bin" if opt.output_format == "binary" else ".dat"
+        def build(inter, target, timing):
+            out = exomol_ktable(states, trans, broadening, q_table, temps, codes, opt.numax, opt.dnu, inter, opt.number_of_gaussian_points,
+                                molar_mass, opt.cutoff, opt.strength_cutoff, target, opt.backend, None, opt.nodes_per_launch, None, timing,
+                                opt.superline_threshold, opt.superline_step)
+            by_pressure = sorted(set(codes), key=lambda c: pressures[codes.index(c)])
+            _print_kept(timing["kept"], [(t, c) for t in sorted(set(temps)) for c in by_pressure], n_trans, timing)
+            return out
+        return _nodes.main_ktable(
+            "exomol", opt, build, lambda timing: "count to ranges %.1f ms, k_exomol_sum %.1f ms, k_ktable_bins %.1f ms" % (
+                timing["prepare_ms"], timing["sum_ms"], timing["device_ms"][0]), t0)
     n_nodes = len(temps) * len(codes)
-    ctx = handle = None
-    timing, written = {}, []
-    try:
-        if opt.backend == "device":
-            from .device import Context
-            ctx = Context(int(os.environ.get("HELIOS_DEVICE", "0")))
-            handle = ExomolOpacity.of(ctx, states, trans, broadening, max(c[2] for c in chunks),
-                                      max(1, min(opt.nodes_per_launch, n_nodes)), n_nodes, True)
-        for lo, hi, n in chunks:
-            kappa = exomol_opacity(states, trans, broadening, q_table, temps, pressures, (float(lo), opt.dnu, n), molar_mass, opt.cutoff,
-                                   opt.strength_cutoff, opt.backend, ctx, opt.nodes_per_launch, handle, timing,
-                                   opt.superline_threshold, None if opt.superline_threshold is None else
-                                   opt.dnu if opt.superline_step is None else opt.superline_step)
-            if (lo, hi, n) == chunks[0]:                # neither the cut nor the cells depend on the chunk
-                _print_kept(timing["kept"].reshape(-1), [(t, c) for t in temps for c in codes], n_trans, timing)
-            nu = float(lo) + np.arange(n, dtype=np.float64) * opt.dnu
-            for it, t in enumerate(temps):
-                for jp, code in enumerate(codes):
-                    written.append(directory + file_name(opt.name, lo, hi, t, code, ending))
-                    write_file(written[-1], nu, kappa[it, jp], opt.output_format)
-    finally:
-        if handle is not None:
-            handle.close()
-        if ctx is not None:
-            ctx.close()
-    how = "numpy" if opt.backend == "numpy" else "count to ranges %.1f ms, k_exomol_sum %.1f ms" % (timing["prepare_ms"], timing["sum_ms"])
-    print("exomol: %d nodes x %d chunks, %d pairs, %s, %.2f s -> %d files in %s" % (
-        n_nodes, len(chunks), timing["pairs"], how, time.time() - t0, len(written), directory))
-    return written
+
+    def opacity(nu_grid, ctx, handle, timing):
+        kappa = exomol_opacity(states, trans, broadening, q_table, temps, pressures, nu_grid, molar_mass, opt.cutoff, opt.strength_cutoff,
+                               opt.backend, ctx, opt.nodes_per_launch, handle, timing, opt.superline_threshold,
+                               None if opt.superline_threshold is None else opt.dnu if opt.superline_step is None else opt.superline_step)
+        if nu_grid[0] == chunks[0][0]:                  # neither the cut nor the cells depend on the chunk
+            _print_kept(timing["kept"].reshape(-1), [(t, c) for t in temps for c in codes], n_trans, timing)
+        return kappa
+    return _nodes.main_files(
+        "exomol", opt, chunks, temps, codes,
+        lambda ctx, n_points_max: ExomolOpacity.of(ctx, states, trans, broadening, n_points_max, max(1, min(opt.nodes_per_launch, n_nodes)),
+                                                   n_nodes, True),
+        opacity, lambda timing: "count to ranges %.1f ms, k_exomol_sum %.1f ms" % (timing["prepare_ms"], timing["sum_ms"]), t0, pairs=True)

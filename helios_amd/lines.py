@@ -60,16 +60,18 @@ axis with numax / points, which is what ktable.py computes from a file's length 
 side keeps its own; temperatures and pressures are sorted ascending and de-duplicated as ktable.SpeciesFiles does, node = p + np t;
 ktable.check_empty_bins and the limit of 2^28 points stand before the first launch.  Refused with `-ktable yes`: `-numin` other
 than 0, `-chunk_width`, `-output_format text`, `-output_directory` (files or table, one per call).
+
+The frame -- chunks and file names, the checks of the nodes, the handle's node launches, the slab source and the front of
+ktable.build_table, the common options and both ends of main -- is _nodes.py's, which cia.py and exomol.py share.
 """
 import argparse
-import ctypes
-import os
 import time
 
 import numpy as np
 
+from . import _nodes
 from . import phys_const as pc
-from ._tool import DeviceObject, dp
+from ._tool import dp
 from .lines_data import WEIDEMAN_A, WEIDEMAN_L
 
 T_REF = 296.0
@@ -193,8 +195,8 @@ def sort_lines(lines):
     return dict((k, np.ascontiguousarray(arr[k][order])) for k in FIELDS)
 
 
-def read_partition_function(path):
-    """(T, Q) of a two-column text file"""
+def read_partition_function(path, tool="lines"):
+    """(T, Q) of a two-column text file; `tool`: the word of the caller's messages"""
     t, q = [], []
     with open(path) as f:
         for nr, line in enumerate(f, 1):
@@ -207,21 +209,21 @@ def read_partition_function(path):
             except ValueError:
                 v = []
             if len(v) < 2 or not np.all(np.isfinite(v)):
-                raise IOError("lines: %s does not hold the finite numbers T and Q(T)" % where)
+                raise IOError("%s: %s does not hold the finite numbers T and Q(T)" % (tool, where))
             if t and not v[0] > t[-1]:
-                raise IOError("lines: %s: the temperatures strictly ascend" % where)
+                raise IOError("%s: %s: the temperatures strictly ascend" % (tool, where))
             t.append(v[0]); q.append(v[1])
     if len(t) < 2:
-        raise IOError("lines: %s holds fewer than two rows of T and Q(T)" % path)
+        raise IOError("%s: %s holds fewer than two rows of T and Q(T)" % (tool, path))
     return np.array(t), np.array(q)
 
 
-def partition_value(q_table, temp):
-    """Q(temp), linear in T between the file's rows"""
+def partition_value(q_table, temp, tool="lines"):
+    """Q(temp), linear in T between the file's rows; `tool`: the word of the caller's messages"""
     t, q = (np.asarray(a, np.float64) for a in q_table)
     temp = float(temp)
     if not (t[0] <= temp <= t[-1]):
-        raise ValueError("lines: T = %.17g K lies outside the partition function's %.17g ... %.17g K" % (temp, t[0], t[-1]))
+        raise ValueError("%s: T = %.17g K lies outside the partition function's %.17g ... %.17g K" % (tool, temp, t[0], t[-1]))
     j = min(int(np.searchsorted(t, temp, side="right")) - 1, len(t) - 2)
     if temp == t[j]:
         return float(q[j])
@@ -287,7 +289,7 @@ def count_pairs(nu0p, nu_first, dnu, n_points, cutoff):
 
 
 # ---- device ------------------------------------------------------------------------------------------------------------
-class LineOpacity(DeviceObject):
+class LineOpacity(_nodes.NodeOpacity):
     """hx_lines: a resident line list of up to n_lines_max lines, nodes of up to n_points_max spectral points"""
 
     PREFIX = "hx_lines"
@@ -319,21 +321,10 @@ class LineOpacity(DeviceObject):
         """T, P and Q(T) per node, and what the nodes share; the tiles' line ranges go to the device once, here"""
         arr = [np.ascontiguousarray(a, np.float64).reshape(-1) for a in (temps, pressures, q_t)]
         assert len(arr[0]) == len(arr[1]) == len(arr[2])
-        self.n_nodes = self.rows_run = 0
+        self._reset_nodes()
         self._call("set_nodes", len(arr[0]), dp(arr[0]), dp(arr[1]), dp(arr[2]), float(q_ref), float(molar_mass),
                    float(self_fraction), float(cutoff), float(nu_first), float(dnu), int(n_points))
         self.n_nodes, self.node_points = len(arr[0]), int(n_points)
-
-    def run_nodes(self, first, n):
-        """queues nodes first ... first + n - 1 into slab rows 0 ... n - 1; returns at once"""
-        self._call("run_nodes", int(first), int(n))
-        self.rows_run = int(n)
-
-    def slab_pointer(self):
-        """device address of the fp32 slabs [nodes_per_launch][...], rows of the last run_nodes with the stride n_points"""
-        p = ctypes.c_void_p()
-        self._call("device_ptr", b"slabs32", ctypes.byref(p))
-        return p
 
     def _results(self):
         return {"kappa64": self.n_points, "kappa32": (self.n_points, np.float32), "line_params": (4, self.n_lines),
@@ -352,24 +343,19 @@ def device_voigt(ctx, x, y):
 
 # ---- the library function ----------------------------------------------------------------------------------------------
 def _check_node_inputs(temps, pressures, nu_grid, molar_mass, self_fraction, cutoff):
-    temps = np.asarray(temps, np.float64).reshape(-1)
-    pressures = np.asarray(pressures, np.float64).reshape(-1)
-    if len(temps) == 0 or not np.all(np.isfinite(temps) & (temps > 0)):
-        raise ValueError("lines: every temperature is a finite number > 0 (got %r)" % (temps.tolist(),))
-    if len(pressures) == 0 or not np.all(np.isfinite(pressures) & (pressures > 0)):
-        raise ValueError("lines: every pressure is a finite number > 0 dyne cm^-2 (got %r)" % (pressures.tolist(),))
-    nu_first, dnu, n_points = float(nu_grid[0]), float(nu_grid[1]), int(nu_grid[2])
-    if not (np.isfinite(dnu) and dnu > 0):
-        raise ValueError("lines: dnu = %r is not > 0" % (dnu,))
-    if n_points < 1 or not np.isfinite(nu_first):
-        raise ValueError("lines: the grid (nu_first, dnu, points) = %r needs a finite start and at least one point" % (tuple(nu_grid),))
-    if molar_mass is None or not (np.isfinite(molar_mass) and molar_mass > 0):
-        raise ValueError("lines: no molar mass (got %r): give one > 0 g/mol" % (molar_mass,))
+    out = _nodes.check_node_inputs("lines", temps, pressures, nu_grid, molar_mass)
     if not 0.0 <= self_fraction <= 1.0:
         raise ValueError("lines: the self-broadening fraction %r lies outside [0, 1]" % (self_fraction,))
     if not (np.isfinite(cutoff) and cutoff > 0):
         raise ValueError("lines: the cut-off %r is not > 0 cm^-1" % (cutoff,))
-    return temps, pressures, (nu_first, dnu, n_points)
+    return out
+
+
+def _holding(ctx, lines, n_points_max):
+    """a handle that holds the list"""
+    handle = LineOpacity(ctx, len(lines["nu0"]), n_points_max)
+    handle.set_lines(lines)
+    return handle
 
 
 def line_opacity(lines, q_table, temps, pressures_cgs, nu_grid, molar_mass=None, self_fraction=0.0, cutoff=DEFAULT_CUTOFF,
@@ -377,8 +363,7 @@ def line_opacity(lines, q_table, temps, pressures_cgs, nu_grid, molar_mass=None,
     """kappa [T][P][nu] in cm^2 g^-1, fp64.  `lines`: the seven arrays of FIELDS (sorted here); `q_table`: (T, Q); `nu_grid`:
     (nu of point 0, dnu, points); `handle`: a LineOpacity that already holds the list.  `timing` receives prepare_ms, sum_ms and
     pairs, summed over the nodes, and from the numpy backend pairs_by_region [4]"""
-    if backend not in ("device", "numpy"):
-        raise ValueError("lines: backend is device or numpy (got %r)" % (backend,))
+    _nodes.check_backend("lines", backend)
     temps, pressures, (nu_first, dnu, n_points) = _check_node_inputs(temps, pressures_cgs, nu_grid, molar_mass, self_fraction, cutoff)
     if handle is None:
         lines = sort_lines(lines)
@@ -394,28 +379,14 @@ def line_opacity(lines, q_table, temps, pressures_cgs, nu_grid, molar_mass=None,
                 out[it, ip] = numpy_node(prm, nu_first, dnu, n_points, cutoff, molar_mass, by_region if timing is not None else None)
         pairs = int(by_region.sum())
     else:
-        own_ctx, own_handle = ctx is None and handle is None, handle is None
-        if own_ctx:
-            from .device import Context
-            ctx = Context(int(os.environ.get("HELIOS_DEVICE", "0")))
-        try:
-            if own_handle:
-                handle = LineOpacity(ctx, len(lines["nu0"]), n_points)
-                handle.set_lines(lines)
-            try:
-                for it, t in enumerate(temps):
-                    for ip, p in enumerate(pressures):
-                        handle.run(t, p, q_t[it], q_ref, molar_mass, self_fraction, cutoff, nu_first, dnu, n_points)
-                        out[it, ip] = handle.get("kappa64")
-                        if timing is not None:
-                            ms += handle.get("timing_ms")
-                            pairs += count_pairs(handle.get("line_params")[0], nu_first, dnu, n_points, cutoff)
-            finally:
-                if own_handle:
-                    handle.close()
-        finally:
-            if own_ctx:
-                ctx.close()
+        with _nodes.opened(ctx, handle, lambda c: _holding(c, lines, n_points)) as h:
+            for it, t in enumerate(temps):
+                for ip, p in enumerate(pressures):
+                    h.run(t, p, q_t[it], q_ref, molar_mass, self_fraction, cutoff, nu_first, dnu, n_points)
+                    out[it, ip] = h.get("kappa64")
+                    if timing is not None:
+                        ms += h.get("timing_ms")
+                        pairs += count_pairs(h.get("line_params")[0], nu_first, dnu, n_points, cutoff)
     if timing is not None:
         timing["prepare_ms"] = timing.get("prepare_ms", 0.0) + float(ms[0])
         timing["sum_ms"] = timing.get("sum_ms", 0.0) + float(ms[1])
@@ -425,101 +396,42 @@ def line_opacity(lines, q_table, temps, pressures_cgs, nu_grid, molar_mass=None,
     return out
 
 
-# ---- files -------------------------------------------------------------------------------------------------------------
-def file_name(name, numin, numax, temp, code, ending=".bin"):
-    return "Out_%s_%05d_%05d_%05d_%s%s" % (name, numin, numax, temp, code, ending)
-
-
-def chunk_limits(numin, numax, dnu, chunk_width=None):
-    """[(numin, numax, points)] of the files"""
-    if not (np.isfinite(dnu) and dnu > 0):
-        raise IOError("lines: -dnu %r is not > 0" % (dnu,))
-    if numax <= numin:
-        raise IOError("lines: -numax %d is not above -numin %d" % (numax, numin))
-    width = numax - numin if chunk_width is None else int(chunk_width)
-    if width <= 0:
-        raise IOError("lines: -chunk_width %r is not > 0" % (chunk_width,))
-    out = []
-    for lo in range(numin, numax, width):
-        hi = min(lo + width, numax)
-        n = (hi - lo) / dnu
-        if abs(n - round(n)) > 1e-9 * max(n, 1.0) or round(n) < 1:
-            raise IOError("lines: dnu = %.17g does not divide the chunk %d ... %d cm^-1 into a whole number of points (%.17g)"
-                          % (dnu, lo, hi, n))
-        out.append((lo, hi, int(round(n))))
-    return out
-
-
-def write_file(path, nu, kappa64, output_format):
-    k32 = np.asarray(kappa64).astype(np.float32)
-    if output_format == "binary":
-        k32.astype("<f4").tofile(path)
-    else:
-        with open(path, "w") as f:
-            for row in zip(nu, k32):
-                f.write("%.12g %.9g\n" % row)
-
-
 # ---- from the line list to the k-table -----------------------------------------------------------------------------------
-MAX_TABLE_POINTS = 1 << 28            # hx_ktable_create
+class LineSlabs(_nodes.NodeSlabs):
+    """ktable.build_table's slabs from a line list (_nodes.NodeSlabs); `ms` and `pairs` hold the kernel times and the pairs
+    evaluated once the table is built"""
 
-
-class LineSlabs(object):
-    """ktable.build_table's slabs from a line list: one chunk 0 ... numax of `n_points` points, the nodes sorted ascending and
-    de-duplicated as ktable.SpeciesFiles does (node = p + np * t).  On the device the slabs never leave it; `ms` and `pairs`
-    hold the kernel times and the pairs evaluated once the table is built"""
+    TOOL = "lines"
 
     def __init__(self, lines, q_table, temps, pressures, numax, dnu, n_points, molar_mass, self_fraction, cutoff,
                  nodes_per_launch=4, count=True):
-        self.lines, self.numax, self.dnu, self.n_points = lines, int(numax), float(dnu), int(n_points)
-        self.temps, self.press = sorted(set(temps)), sorted(set(pressures))
-        self.molar_mass, self.self_fraction, self.cutoff = molar_mass, self_fraction, cutoff
+        _nodes.NodeSlabs.__init__(self, temps, pressures, numax, dnu, n_points, nodes_per_launch)
+        self.lines, self.molar_mass, self.self_fraction, self.cutoff = lines, molar_mass, self_fraction, cutoff
         self.q_ref = partition_value(q_table, T_REF)
         self.q_t = [partition_value(q_table, t) for t in self.temps]
-        self.nodes_per_launch, self.count = max(1, int(nodes_per_launch)), count
-        self.handle, self.ms, self.pairs, self.by_region = None, np.zeros(2), 0, np.zeros(4, np.int64)
+        self.count, self.pairs, self.by_region = count, 0, np.zeros(4, np.int64)
 
-    def axis(self):
-        return 0, self.numax, self.numax / self.n_points           # ktable.SpeciesFiles.resolution() of the file not written
-
-    def _check(self, n_points):
-        if n_points != self.n_points:
-            raise IOError("lines: the k-table's axis 0 ... %d cm^-1 at %.17g cm^-1 has %d points, the line kernel's grid at "
-                          "-dnu %.17g has %d" % (self.numax, self.numax / self.n_points, n_points, self.dnu, self.n_points))
+    def host_slab(self, it, t, p):
+        prm = line_params(self.lines, t, p, self.q_t[it], self.q_ref, self.molar_mass, self.self_fraction)
+        return numpy_node(prm, 0.0, self.dnu, self.n_points, self.cutoff, self.molar_mass, self.by_region if self.count else None)
 
     def host_slabs(self, pool, n_points):
-        self._check(n_points)
-        for it, t in enumerate(self.temps):
-            for p in self.press:
-                prm = line_params(self.lines, float(t), p, self.q_t[it], self.q_ref, self.molar_mass, self.self_fraction)
-                yield numpy_node(prm, 0.0, self.dnu, self.n_points, self.cutoff, self.molar_mass,
-                                 self.by_region if self.count else None).astype(np.float32)
+        for slab in _nodes.NodeSlabs.host_slabs(self, pool, n_points):
+            yield slab
         self.pairs = int(self.by_region.sum())
 
-    def feed(self, b, pool, n_points):
-        self._check(n_points)
-        nodes = [(float(t), p, self.q_t[it]) for it, t in enumerate(self.temps) for p in self.press]
-        per = min(self.nodes_per_launch, b.max_tp)
-        self.handle = h = LineOpacity(b.ctx, len(self.lines["nu0"]), self.n_points, per, len(nodes))
+    def open_handle(self, ctx, per, nodes):
+        self.handle = h = LineOpacity(ctx, len(self.lines["nu0"]), self.n_points, per, len(nodes))
         h.set_lines(self.lines)
-        h.set_nodes([n[0] for n in nodes], [n[1] for n in nodes], [n[2] for n in nodes], self.q_ref, self.molar_mass,
+        h.set_nodes([n[1] for n in nodes], [n[2] for n in nodes], [self.q_t[n[0]] for n in nodes], self.q_ref, self.molar_mass,
                     self.self_fraction, self.cutoff, 0.0, self.dnu, self.n_points)
-        slabs = h.slab_pointer()
-        for first in range(0, len(nodes), per):
-            n = min(per, len(nodes) - first)
-            h.run_nodes(first, n)
-            b.run_device(slabs, n, first)
 
     def close(self):
-        h, self.handle = self.handle, None
-        if h is not None:
-            try:
-                self.ms = h.get("timing_ms")
-            finally:
-                h.close()
-            if self.count:                          # nu_0' depends on P alone
-                self.pairs = len(self.temps) * sum(count_pairs(self.lines["nu0"] + self.lines["delta_air"] * (p / ATM), 0.0,
-                                                               self.dnu, self.n_points, self.cutoff) for p in self.press)
+        counted = self.count and self.handle is not None
+        _nodes.NodeSlabs.close(self)
+        if counted:                                 # nu_0' depends on P alone
+            self.pairs = len(self.temps) * sum(count_pairs(self.lines["nu0"] + self.lines["delta_air"] * (p / ATM), 0.0,
+                                                           self.dnu, self.n_points, self.cutoff) for p in self.press)
 
 
 def line_ktable(lines, q_table, temps, pressure_codes, numax, dnu, inter, n_gauss, molar_mass=None, self_fraction=0.0,
@@ -528,25 +440,12 @@ def line_ktable(lines, q_table, temps, pressure_codes, numax, dnu, inter, n_gaus
     ktable.build_species returns them for the directory lines.py would write for the same arguments -- to the bit -- without the
     files.  `temps`: integers in K; `pressure_codes`: keys of ktable.pressure_table(); the range is 0 ... numax in one chunk.
     `timing` receives prepare_ms, sum_ms, pairs and build_table's entries"""
-    from . import ktable
-    if backend not in ("device", "numpy"):
-        raise ValueError("lines: backend is device or numpy (got %r)" % (backend,))
-    table = ktable.pressure_table()
-    for c in pressure_codes:
-        if c not in table:
-            raise IOError("lines: pressure code %r is not in the table (n800 ... p400)" % (c,))
-    for t in temps:
-        if int(t) != t:
-            raise IOError("lines: the temperature %r is not an integer in K" % (t,))
-    temps, pressures = [int(t) for t in temps], [table[c] for c in pressure_codes]
-    n_points = chunk_limits(0, int(numax), dnu)[0][2]
-    _check_node_inputs(temps, pressures, (0.0, dnu, n_points), molar_mass, self_fraction, cutoff)
-    if n_points > MAX_TABLE_POINTS:
-        raise IOError("lines: %d spectral points, the k-table's kernel takes 1 ... %d" % (n_points, MAX_TABLE_POINTS))
-    source = LineSlabs(sort_lines(lines), q_table, temps, pressures, numax, dnu, n_points, molar_mass, self_fraction, cutoff,
-                       nodes_per_launch, count=timing is not None)
-    out = ktable.build_table(source, inter, n_gauss, "hip" if backend == "device" else "numpy", ctx, source.nodes_per_launch,
-                             ktable.LDS_POINTS if lds_points is None else lds_points, target, timing)
+    out, source = _nodes.node_ktable(
+        "lines", backend, temps, pressure_codes, numax, dnu,
+        lambda t, p, nu_grid: _check_node_inputs(t, p, nu_grid, molar_mass, self_fraction, cutoff),
+        lambda t, p, n_points: LineSlabs(sort_lines(lines), q_table, t, p, numax, dnu, n_points, molar_mass, self_fraction, cutoff,
+                                         nodes_per_launch, count=timing is not None),
+        inter, n_gauss, target, ctx, lds_points, timing)
     if timing is not None:
         timing["prepare_ms"], timing["sum_ms"], timing["pairs"] = float(source.ms[0]), float(source.ms[1]), source.pairs
     return out
@@ -558,122 +457,27 @@ def parse_args(argv=None):
     p.add_argument("-name", required=True)
     p.add_argument("-line_list", required=True)
     p.add_argument("-partition_function", required=True)
-    p.add_argument("-temperatures", required=True, help="integers in K, separated by blanks")
-    p.add_argument("-pressure_codes", required=True, help="HELIOS-K's codes, n800 ... p400, separated by blanks")
-    p.add_argument("-numin", type=int, default=0)
-    p.add_argument("-numax", type=int, required=True)
-    p.add_argument("-dnu", type=float, required=True)
-    p.add_argument("-output_directory", default=None, help="of the files; required without -ktable yes")
-    p.add_argument("-chunk_width", type=int, default=None)
-    p.add_argument("-output_format", default="binary", choices=("binary", "text"))
+    _nodes.add_node_options(p)
     p.add_argument("-isotopologue", default="1")
     p.add_argument("-molar_mass", type=float, default=None)
     p.add_argument("-self_fraction", type=float, default=0.0)
     p.add_argument("-cutoff", type=float, default=DEFAULT_CUTOFF)
-    p.add_argument("-backend", default="device", choices=("device", "numpy"))
-    p.add_argument("-ktable", default="no", choices=("yes", "no"),
-                   help="the species' k-table in place of the files; the options below are ktable.py's")
-    p.add_argument("-grid_format", default="fixed_resolution")
-    p.add_argument("-wavelength_grid", default="50 0.34 200")
-    p.add_argument("-path_to_grid_file", default=None)
-    p.add_argument("-number_of_gaussian_points", type=int, default=20)
-    p.add_argument("-directory_with_individual_files", default="./output/")
-    p.add_argument("-interpolate", default="yes", choices=("yes", "no"))
-    p.add_argument("-temperature_grid", default=None)
-    p.add_argument("-pressure_grid", default=None)
-    p.add_argument("-container", default="h5", choices=("h5", "npz"))
-    p.add_argument("-nodes_per_launch", type=int, default=4)
-    opt = p.parse_args(argv)
-    if opt.ktable == "no" and opt.output_directory is None:
-        p.error("the following arguments are required: -output_directory")
-    return opt
-
-
-def parse_temperatures(text):
-    out = []
-    for word in str(text).split():
-        try:
-            t = int(word)
-        except ValueError:
-            raise IOError("lines: the temperature %r is not an integer in K (the file name carries it)" % (word,))
-        if t <= 0:
-            raise IOError("lines: the temperature %r is not > 0 K" % (word,))
-        out.append(t)
-    if not out:
-        raise IOError("lines: -temperatures holds no temperature")
-    return out
-
-
-def parse_pressure_codes(text):
-    from .ktable import pressure_table
-    table = pressure_table()
-    codes = str(text).split()
-    for c in codes:
-        if c not in table:
-            raise IOError("lines: pressure code %r is not in the table (n800 ... p400)" % (c,))
-    if not codes:
-        raise IOError("lines: -pressure_codes holds no code")
-    return codes, [table[c] for c in codes]
-
-
-def _refuse_with_ktable(opt):
-    if opt.numin != 0:
-        raise IOError("lines: -ktable yes with -numin %d: the k-table's wavelength axis starts at 0 cm^-1, and ktable.py refuses "
-                      "a directory whose first chunk does not" % opt.numin)
-    if opt.chunk_width is not None:
-        raise IOError("lines: -ktable yes with -chunk_width %d: the table is built from the one chunk 0 ... numax; a chunk's "
-                      "points are lo + i dnu, which are other bits than 0 + i dnu" % opt.chunk_width)
-    if opt.output_format != "binary":
-        raise IOError("lines: -ktable yes with -output_format %s: no opacity file is written, the fp32 opacities stay on the "
-                      "device" % opt.output_format)
-    if opt.output_directory is not None:
-        raise IOError("lines: -ktable yes with -output_directory %s: a call writes the files or the table, not both; the table "
-                      "goes to -directory_with_individual_files" % opt.output_directory)
-    if opt.number_of_gaussian_points < 1:
-        raise IOError("lines: -number_of_gaussian_points is an integer >= 1")
-    if opt.nodes_per_launch < 1:
-        raise IOError("lines: -nodes_per_launch is an integer >= 1")
-
-
-def _main_ktable(opt, lines, q_table, temps, codes, molar_mass, t0):
-    """-ktable yes: `<name>_opac_kdistr` and, with -interpolate yes, `<name>_opac_ip_kdistr`"""
-    from . import ktable
-    inter = ktable.wavelength_grid(opt.grid_format, opt.wavelength_grid.split(), opt.path_to_grid_file)
-    target = ktable.target_grid(opt.temperature_grid, opt.pressure_grid) if opt.interpolate == "yes" else None
-    timing = {}
-    native, ip = line_ktable(lines, q_table, temps, codes, opt.numax, opt.dnu, inter, opt.number_of_gaussian_points, molar_mass,
-                             opt.self_fraction, opt.cutoff, target, opt.backend, None, opt.nodes_per_launch, None, timing)
-    stem = os.path.join(opt.directory_with_individual_files, opt.name)
-    written = [ktable.write_table("%s_opac_kdistr.%s" % (stem, opt.container), native)]
-    if ip is not None:
-        written.append(ktable.write_table("%s_opac_ip_kdistr.%s" % (stem, opt.container), ip))
-    how = "numpy" if opt.backend == "numpy" else "k_lines_prepare_nodes %.1f ms, k_lines_sum_nodes %.1f ms, k_ktable_bins %.1f ms" % (
-        timing["prepare_ms"], timing["sum_ms"], timing["device_ms"][0])
-    print("lines: %d nodes of %d points into %d bins x %d Gauss points, %d pairs, %s, %.2f s -> %s" % (
-        timing["points"], chunk_limits(0, opt.numax, opt.dnu)[0][2], len(inter) - 1,
-        opt.number_of_gaussian_points, timing["pairs"], how, time.time() - t0, ", ".join(written)))
-    return written
+    _nodes.add_ktable_options(p)
+    return _nodes.parse_node_args(p, argv)
 
 
 def main(argv=None):
     """lines.py: the directory of one species, or with -ktable yes its k-table; returns the paths written"""
     opt = parse_args(argv)
     t0 = time.time()
-    temps = parse_temperatures(opt.temperatures)
-    codes, pressures = parse_pressure_codes(opt.pressure_codes)
+    temps = _nodes.parse_temperatures("lines", opt.temperatures)
+    codes, pressures = _nodes.parse_pressure_codes("lines", opt.pressure_codes)
     if opt.ktable == "yes":
-        _refuse_with_ktable(opt)
-    chunks = chunk_limits(opt.numin, opt.numax, opt.dnu, opt.chunk_width)
+        _nodes.refuse_with_ktable("lines", opt)
+    chunks = _nodes.chunk_limits("lines", opt.numin, opt.numax, opt.dnu, opt.chunk_width)
     if not 0.0 <= opt.self_fraction <= 1.0:
         raise IOError("lines: -self_fraction %r lies outside [0, 1]" % (opt.self_fraction,))
-    molar_mass = opt.molar_mass
-    if molar_mass is None:
-        from .species_data import species_lib
-        if opt.name not in species_lib:
-            raise IOError("lines: no molar mass: %r is not in species_data.py, give -molar_mass" % (opt.name,))
-        molar_mass = species_lib[opt.name].weight
-    if not (np.isfinite(molar_mass) and molar_mass > 0):
-        raise IOError("lines: no molar mass: -molar_mass %r is not > 0 g/mol" % (molar_mass,))
+    molar_mass = _nodes.mass_of("lines", opt.name, opt.molar_mass)
     q_table = read_partition_function(opt.partition_function)
     try:
         for t in [T_REF] + temps:
@@ -681,39 +485,18 @@ def main(argv=None):
     except ValueError as e:
         raise IOError(str(e))
     lines, skipped = read_line_list(opt.line_list, opt.isotopologue)
-    n_lines = len(lines["nu0"])
-    print("lines: %d lines of isotopologue %s of %s, %d lines of other isotopologues skipped" % (n_lines, opt.isotopologue,
+    print("lines: %d lines of isotopologue %s of %s, %d lines of other isotopologues skipped" % (len(lines["nu0"]), opt.isotopologue,
                                                                                                  opt.line_list, skipped))
     if opt.ktable == "yes":
-        return _main_ktable(opt, lines, q_table, temps, codes, molar_mass, t0)
-    if opt.numin != 0:
-        print("lines: -numin %d is not 0: ktable.py will refuse the directory" % opt.numin)
-    directory = os.path.join(str(opt.output_directory), "")
-    os.makedirs(directory, exist_ok=True)
-    ending = ".bin" if opt.output_format == "binary" else ".dat"
-    ctx = handle = None
-    timing, written = {}, []
-    try:
-        if opt.backend == "device":
-            from .device import Context
-            ctx = Context(int(os.environ.get("HELIOS_DEVICE", "0")))
-            handle = LineOpacity(ctx, n_lines, max(c[2] for c in chunks))
-            handle.set_lines(lines)
-        for lo, hi, n in chunks:
-            kappa = line_opacity(lines, q_table, temps, pressures, (float(lo), opt.dnu, n), molar_mass, opt.self_fraction,
-                                 opt.cutoff, opt.backend, ctx, handle, timing)
-            nu = float(lo) + np.arange(n, dtype=np.float64) * opt.dnu
-            for it, t in enumerate(temps):
-                for ip, code in enumerate(codes):
-                    written.append(directory + file_name(opt.name, lo, hi, t, code, ending))
-                    write_file(written[-1], nu, kappa[it, ip], opt.output_format)
-    finally:
-        if handle is not None:
-            handle.close()
-        if ctx is not None:
-            ctx.close()
-    how = "numpy" if opt.backend == "numpy" else "k_lines_prepare %.1f ms, k_lines_sum %.1f ms" % (timing["prepare_ms"],
-                                                                                                   timing["sum_ms"])
-    print("lines: %d nodes x %d chunks, %d pairs, %s, %.2f s -> %d files in %s" % (
-        len(temps) * len(codes), len(chunks), timing["pairs"], how, time.time() - t0, len(written), directory))
-    return written
+        return _nodes.main_ktable(
+            "lines", opt,
+            lambda inter, target, timing: line_ktable(lines, q_table, temps, codes, opt.numax, opt.dnu, inter,
+                                                      opt.number_of_gaussian_points, molar_mass, opt.self_fraction, opt.cutoff, target,
+                                                      opt.backend, None, opt.nodes_per_launch, None, timing),
+            lambda timing: "k_lines_prepare_nodes %.1f ms, k_lines_sum_nodes %.1f ms, k_ktable_bins %.1f ms" % (
+                timing["prepare_ms"], timing["sum_ms"], timing["device_ms"][0]), t0, pairs=True)
+    return _nodes.main_files(
+        "lines", opt, chunks, temps, codes, lambda ctx, n_points_max: _holding(ctx, lines, n_points_max),
+        lambda nu_grid, ctx, handle, timing: line_opacity(lines, q_table, temps, pressures, nu_grid, molar_mass, opt.self_fraction,
+                                                          opt.cutoff, opt.backend, ctx, handle, timing),
+        lambda timing: "k_lines_prepare %.1f ms, k_lines_sum %.1f ms" % (timing["prepare_ms"], timing["sum_ms"]), t0, pairs=True)

@@ -189,6 +189,25 @@ def test_cia_opacity_on_the_device_equals_the_numpy_backend(ctx):
     same_bits(dev, host, "cia_opacity")
 
 
+def test_a_handle_made_for_fewer_nodes_takes_them_in_turns(ctx):
+    """three nodes through a handle made for two, two per launch: turns of 2 + 1 and a short last launch, on one full tile and
+    one point of the edge table's band a.  Bit for bit what the same call gives with a handle of its own, which takes the three
+    in one turn; the handle given stays open"""
+    temps, press, grid = [250.0, 350.0, 450.0], [1e5], (30.0, 0.173, TILE + 1)
+    own, turns = {}, {}
+    want = cia.cia_opacity(cc.edge_blocks(), temps, press, grid, cc.M_H2, backend="device", ctx=ctx, timing=own)
+    h = cia.CiaOpacity(ctx, cia.bands_of(cc.edge_blocks()), TILE + 1, 2, 2, True)
+    try:
+        got = cia.cia_opacity(cc.edge_blocks(), temps, press, grid, cc.M_H2, backend="device", ctx=ctx, handle=h, timing=turns)
+        assert h.handle and h.n_nodes == 1 and h.rows_run == 1               # left open, after the turn of one node
+    finally:
+        h.close()
+    assert got.shape == (3, 1, TILE + 1) and np.all(np.count_nonzero(got, axis=2) > TILE - 10)
+    assert len({row.tobytes() for row in got[:, 0]}) == 3
+    same_bits(got, want, "in turns")
+    assert own["nodes_ms"] > 0 and turns["nodes_ms"] > 0
+
+
 # ---- from the file to the k-table and into a run ------------------------------------------------------------------------------
 def test_the_fused_containers_equal_the_two_step_routes_on_the_device(tmp_path):
     """`cia.py` then `ktable.py` against `cia.py -ktable yes`, all on the device, four nodes in launches of 3 and 1"""

@@ -187,6 +187,39 @@ def test_the_library_function_on_the_device_equals_the_numpy_backend_under_the_r
             ec.check_rule(host[it, jp], r["ld"], r["f64"], "numpy at %g K, %g" % (t, p))
 
 
+@pytest.mark.parametrize("superlines", [None, (1e-22, 0.25)])
+def test_a_handle_made_for_fewer_nodes_takes_them_in_turns(ctx, superlines):
+    """three nodes through a handle made for two, two per launch: turns of 2 + 1 and a short last launch, on ec.GRID's one full
+    tile and one point.  Bit for bit what the same call gives with a handle of its own, which takes the three in one turn, and
+    the same counts per node; the handle given stays open and is set to the call's super-lines.  The list is the smallest of
+    the cases that the cut divides: 63 transitions, 32 of them kept at 700 K and all of them in the hotter nodes; under
+    S_sl = 1e-22 every node has strong and weak transitions, and a cell that merges two"""
+    case = ec.make("count: 63")
+    assert case.grid == ec.GRID and case.grid[2] == TILE + 1
+    more = {} if superlines is None else {"superline_threshold": superlines[0], "superline_step": superlines[1]}
+    args = (case.states, case.trans, case.broadening, ec.q_table(), [700.0, 1500.0, 2500.0], [1e5], case.grid, case.molar_mass,
+            case.cutoff, case.s_min)
+    own, turns = {}, {}
+    want = exomol.exomol_opacity(*args, backend="device", ctx=ctx, timing=own, **more)
+    h = exomol.ExomolOpacity.of(ctx, case.states, case.trans, case.broadening, TILE + 1, 2, 2, True)
+    try:
+        got = exomol.exomol_opacity(*args, backend="device", ctx=ctx, handle=h, timing=turns, **more)
+        assert h.handle and h.n_nodes == 1 and h.rows_run == 1 and h.superlines == superlines
+    finally:
+        h.close()
+    assert got.shape == (3, 1, TILE + 1) and np.all(np.count_nonzero(got, axis=2) > 400)
+    assert np.array_equal(got.view(np.uint64), want.view(np.uint64))
+    assert turns["kept"].reshape(-1).tolist() == own["kept"].reshape(-1).tolist() == [32, 63, 63]
+    assert turns["pairs"] == own["pairs"] > 0 and turns["sum_ms"] > 0 and own["sum_ms"] > 0
+    if superlines is None:
+        assert "weak" not in turns and "weak" not in own
+    else:
+        for k in ("strong", "weak", "superlines"):
+            assert np.array_equal(turns[k], own[k]), k
+        assert np.all(turns["strong"] > 0) and np.all(turns["superlines"] > 0) and np.any(turns["weak"] > turns["superlines"])
+        assert np.array_equal(turns["strong"] + turns["weak"], turns["kept"])
+
+
 # ---- the handle -----------------------------------------------------------------------------------------------------------------
 def test_refusals_name_the_counts_and_leave_the_handle_usable(ctx):
     case = ec.make("count: 65")

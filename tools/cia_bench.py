@@ -59,9 +59,9 @@ def stats(a):
 
 def main(argv):
     import cia_cases as cc
-    from helios_amd import cia, ktable
+    from helios_amd import _nodes, cia, ktable
     from helios_amd.device import Context
-    n_points = cia.chunk_limits(0, NUMAX, DNU)[0][2]
+    n_points = _nodes.chunk_limits("cia", 0, NUMAX, DNU)[0][2]
     temps, codes = [int(t) for t in TEMPS.split()], CODES.split()
     press = sorted(ktable.pressure_table()[c] for c in codes)
     n_nodes = len(temps) * len(codes)
@@ -155,7 +155,7 @@ def main(argv):
         host = cia.cia_opacity([b_ for band in bands for b_ in band.blocks], temps, press, (0.0, DNU, n_points), cc.M_H2, backend="numpy")
         out["numpy_backend_seconds"] = time.time() - t0
         out["numpy_backend_ms_per_node"] = out["numpy_backend_seconds"] * 1e3 / n_nodes
-        got = np.fromfile(os.path.join(wd, "opac", cia.file_name("CIA_H2H2", 0, NUMAX, temps[1], codes[2])), np.float32)
+        got = np.fromfile(os.path.join(wd, "opac", _nodes.file_name("CIA_H2H2", 0, NUMAX, temps[1], codes[2])), np.float32)
         with np.errstate(under="ignore"):
             want = host[sorted(temps).index(temps[1]), press.index(ktable.pressure_table()[codes[2]])].astype(np.float32)
         out["a_device_file_equals_the_numpy_backend_to_the_bit"] = bool(got.tobytes() == want.tobytes())

@@ -43,10 +43,10 @@ def quiet(fn, argv):
 def main(argv):
     import lines_cases as lc
     from lines_bench import synthetic_list
-    from helios_amd import ktable, lines
+    from helios_amd import _nodes, ktable, lines
     from helios_amd.device import Context
     n_lines = int(argv[argv.index("--lines") + 1]) if "--lines" in argv else 100000
-    n_points = lines.chunk_limits(0, NUMAX, DNU)[0][2]
+    n_points = _nodes.chunk_limits("lines", 0, NUMAX, DNU)[0][2]
     temps, codes = [int(t) for t in TEMPS.split()], CODES.split()
     n_nodes = len(temps) * len(codes)
     inter = ktable.wavelength_grid("fixed_resolution", GRID.split())
