@@ -191,19 +191,15 @@ __global__ __launch_bounds__(CIA_THREADS) void k_cia_nodes(CiaTable t, const Cia
 
 }  // namespace
 
-struct hx_cia {
+struct hx_cia : hx_node_rows {
     hx_context* ctx;
-    int values_max, blocks_max, points_max, per_launch, nodes_max;
-    bool with_fp64;
+    int values_max, blocks_max;
     int n_values, n_blocks, n_bands;                 // of the last set_blocks
-    int n_nodes, n_points, rows_run;                 // of the last set_nodes; rows the last run_nodes filled
     double *nu, *k;                                  // values_max
     double *band_numin, *band_numax;                 // blocks_max
     double* node_factor;                             // nodes_max
     CiaNodeBand* node_bands;                         // [n_nodes][n_bands], grown by set_nodes
     size_t node_bands_bytes;
-    float* slabs32;                                  // [per_launch][points_max], rows run with the stride n_points
-    double* kappa64;                                 // the same rows before rounding; null without with_fp64
     double common[3];                                // partner mass, nu_first, dnu of set_nodes
     std::vector<int> h_block_off, h_band_first;      // where the blocks stand and which a band holds: set_nodes finds a node's
     std::vector<double> h_block_temp;                // blocks in them
@@ -219,30 +215,21 @@ int hx_cia_create(hx_context* ctx, int n_values_max, int n_blocks_max, int n_poi
     if (!ctx || !out_cia) return HX_E_ARG;
     HX_REQUIRE(ctx, n_values_max >= 2 && n_values_max <= (1 << 28), HX_E_ARG, "2 ... 2^28 tabulated values");
     HX_REQUIRE(ctx, n_blocks_max >= 1 && n_blocks_max <= n_values_max / 2, HX_E_ARG, "1 ... n_values_max / 2 blocks");
-    HX_REQUIRE(ctx, n_points_max >= 1 && n_points_max <= (1 << 30), HX_E_ARG, "1 ... 2^30 spectral points");
-    HX_REQUIRE(ctx, nodes_per_launch >= 1 && nodes_per_launch <= 65535, HX_E_ARG, "1 ... 65535 nodes per launch");
-    HX_REQUIRE(ctx, n_nodes_max >= 1 && n_nodes_max <= (1 << 24), HX_E_ARG, "1 ... 2^24 nodes");
-    hx_cia* h = new (std::nothrow) hx_cia();
+    hx_node_rows rows;
+    int rc = hx_node_rows_init(ctx, __func__, rows, n_points_max, nodes_per_launch, n_nodes_max, with_fp64);
+    if (rc) return rc;
+    hx_cia* h = new (std::nothrow) hx_cia{rows};
     if (!h) return hx_fail(ctx, HX_E_ARG, "no host memory");
     h->ctx = ctx;
     h->values_max = n_values_max;
     h->blocks_max = n_blocks_max;
-    h->points_max = n_points_max;
-    h->per_launch = nodes_per_launch;
-    h->nodes_max = n_nodes_max;
-    h->with_fp64 = with_fp64 != 0;
-    const size_t nv = (size_t)n_values_max, nb = (size_t)n_blocks_max, rows = (size_t)nodes_per_launch * (size_t)n_points_max;
-    int rc = hx_owned_alloc(ctx, h->owned, nv * 8, &h->nu);
+    const size_t nv = (size_t)n_values_max, nb = (size_t)n_blocks_max;
+    rc = hx_owned_alloc(ctx, h->owned, nv * 8, &h->nu);
     if (!rc) rc = hx_owned_alloc(ctx, h->owned, nv * 8, &h->k);
     if (!rc) rc = hx_owned_alloc(ctx, h->owned, nb * 8, &h->band_numin);
     if (!rc) rc = hx_owned_alloc(ctx, h->owned, nb * 8, &h->band_numax);
     if (!rc) rc = hx_owned_alloc(ctx, h->owned, (size_t)n_nodes_max * 8, &h->node_factor);
-    if (!rc && hx_owned_alloc(ctx, h->owned, rows * 4, &h->slabs32))
-        rc = hx_fail(ctx, HX_E_ARG, "hx_cia_create: the fp32 slabs of %d nodes per launch need %zu bytes, which the device does not give",
-                     nodes_per_launch, rows * 4);
-    if (!rc && h->with_fp64 && hx_owned_alloc(ctx, h->owned, rows * 8, &h->kappa64))
-        rc = hx_fail(ctx, HX_E_ARG, "hx_cia_create: the fp64 rows of %d nodes per launch need %zu bytes, which the device does not give",
-                     nodes_per_launch, rows * 8);
+    if (!rc) rc = hx_node_rows_alloc(ctx, __func__, h->owned, *h);
     if (!rc) rc = hx_stream_timer_create(ctx, h->timer);
     if (rc) {
         (void)hipGetLastError();         // a refused hipMalloc is not the next launch's error
@@ -325,21 +312,12 @@ int hx_cia_set_nodes(hx_cia* h, int n_nodes, const double* temp, const double* p
     hx_context* ctx = h->ctx;
     if (h->n_blocks < 1) return hx_fail(ctx, HX_E_STATE, "hx_cia_set_nodes: no blocks (hx_cia_set_blocks)");
     HX_REQUIRE(ctx, temp && press, HX_E_ARG, "null array");
-    if (n_nodes < 1 || n_nodes > h->nodes_max)
-        return hx_fail(ctx, HX_E_ARG, "hx_cia_set_nodes: %d nodes, the handle holds 1 ... %d", n_nodes, h->nodes_max);
-    if (n_points < 1 || n_points > h->points_max)
-        return hx_fail(ctx, HX_E_ARG, "hx_cia_set_nodes: %d spectral points, the handle holds 1 ... %d", n_points, h->points_max);
-    const struct { const char* name; double v; } positive[] = {{"M", partner_mass}, {"dnu", dnu}};
-    for (const auto& p : positive)
-        if (!(p.v > 0.0) || !std::isfinite(p.v))
-            return hx_fail(ctx, HX_E_ARG, "hx_cia_set_nodes: %s = %g is not a finite number > 0", p.name, p.v);
+    int rc = hx_node_rows_counts(ctx, __func__, *h, n_nodes, n_points);
+    if (!rc) rc = hx_require_positive(ctx, __func__, -1, {{"M", partner_mass}, {"dnu", dnu}});
+    if (rc) return rc;
     if (!std::isfinite(nu_first)) return hx_fail(ctx, HX_E_ARG, "hx_cia_set_nodes: nu of point 0 = %g is not finite", nu_first);
-    for (int n = 0; n < n_nodes; n++) {
-        const struct { const char* name; double v; } node[] = {{"T", temp[n]}, {"P", press[n]}};
-        for (const auto& p : node)
-            if (!(p.v > 0.0) || !std::isfinite(p.v))
-                return hx_fail(ctx, HX_E_ARG, "hx_cia_set_nodes: node %d: %s = %g is not a finite number > 0", n, p.name, p.v);
-    }
+    for (int n = 0; n < n_nodes && !rc; n++) rc = hx_require_positive(ctx, __func__, n, {{"T", temp[n]}, {"P", press[n]}});
+    if (rc) return rc;
     // per node and band: constant beyond the band's temperatures, else the two blocks around T with weights from differences
     std::vector<CiaNodeBand> bands((size_t)n_nodes * h->n_bands);
     std::vector<double> factor((size_t)n_nodes);
@@ -372,7 +350,7 @@ int hx_cia_set_nodes(hx_cia* h, int n_nodes, const double* temp, const double* p
         }
     }
     h->n_nodes = h->rows_run = 0;        // until the new records are there
-    int rc = hx_stream_timer_settle(ctx, h->timer, &h->timing[0]);
+    rc = hx_stream_timer_settle(ctx, h->timer, &h->timing[0]);
     const size_t bytes = bands.size() * sizeof(CiaNodeBand);
     if (!rc && bytes > h->node_bands_bytes) {
         rc = hx_owned_free(ctx, h->owned, h->node_bands);
@@ -401,19 +379,13 @@ int hx_cia_set_nodes(hx_cia* h, int n_nodes, const double* temp, const double* p
 int hx_cia_run_nodes(hx_cia* h, int first_node, int n_nodes) {
     if (!h) return HX_E_ARG;
     hx_context* ctx = h->ctx;
-    if (h->n_nodes < 1) return hx_fail(ctx, HX_E_STATE, "hx_cia_run_nodes: no nodes (hx_cia_set_nodes)");
-    if (n_nodes < 1 || n_nodes > h->per_launch)
-        return hx_fail(ctx, HX_E_ARG, "hx_cia_run_nodes: %d nodes in one call, the handle holds 1 ... %d per launch", n_nodes,
-                       h->per_launch);
-    if (first_node < 0 || first_node > h->n_nodes - n_nodes)
-        return hx_fail(ctx, HX_E_ARG, "hx_cia_run_nodes: nodes %d ... %d, hx_cia_set_nodes gave 0 ... %d", first_node,
-                       first_node + n_nodes - 1, h->n_nodes - 1);
-    int rc = hx_stream_timer_settle(ctx, h->timer, &h->timing[0]);
+    int rc = hx_node_rows_check_run(ctx, __func__, "hx_cia_set_nodes", *h, first_node, n_nodes);
+    if (!rc) rc = hx_stream_timer_settle(ctx, h->timer, &h->timing[0]);
     if (!rc) rc = hx_stream_timer_start(ctx, h->timer);
     if (rc) return rc;
     const CiaTable t = {h->nu, h->k, h->band_numin, h->band_numax, h->n_bands};
     const dim3 grid(hx_cdiv(h->n_points, CIA_TILE), n_nodes);
-    if (h->with_fp64)
+    if (h->want_fp64)
         k_cia_nodes<true><<<grid, CIA_THREADS, 0, ctx->stream>>>(t, h->node_bands, h->node_factor, first_node, h->n_points, h->common[1],
                                                                  h->common[2], h->common[0], h->slabs32, h->kappa64);
     else
@@ -429,9 +401,7 @@ int hx_cia_run_nodes(hx_cia* h, int first_node, int n_nodes) {
 
 int hx_cia_device_ptr(hx_cia* h, const char* name, void** out_dptr) {
     if (!h || !name || !out_dptr) return HX_E_ARG;
-    if (strcmp(name, "slabs32") != 0) return hx_fail(h->ctx, HX_E_ARG, "hx_cia_device_ptr: unknown name '%s'", name);
-    *out_dptr = h->slabs32;
-    return 0;
+    return hx_node_rows_device_ptr(h->ctx, __func__, *h, name, out_dptr);
 }
 
 int hx_cia_get(hx_cia* h, const char* name, void* out, size_t out_bytes) {
@@ -440,10 +410,8 @@ int hx_cia_get(hx_cia* h, const char* name, void* out, size_t out_bytes) {
     int rc = hx_stream_timer_settle(ctx, h->timer, &h->timing[0]);
     if (rc) return rc;
     const char* no_run = h->rows_run ? nullptr : "no nodes have been run (hx_cia_run_nodes)";
-    const size_t n = (size_t)h->rows_run * h->n_points;
-    const hx_result rows[] = {{"slabs32", h->slabs32, n * 4, true, no_run},
-                              {"kappa64", h->kappa64, n * 8, true,
-                               h->with_fp64 ? no_run : "the handle keeps no fp64 rows (hx_cia_create, with_fp64)"},
+    const hx_result rows[] = {hx_node_rows_slabs32(*h, no_run),
+                              hx_node_rows_kappa64(*h, no_run, "the handle keeps no fp64 rows (hx_cia_create, with_fp64)"),
                               {"timing_ms", h->timing, sizeof h->timing, false, nullptr}};
     return hx_get_result(ctx, __func__, rows, 3, name, out, out_bytes);
 }

@@ -13,7 +13,7 @@
 //                     kept transitions in list order.
 //   k_exomol_ranges   one thread per tile: lower and upper bound of the tile's reach in the node's compacted nu_0 (ascending,
 //                     there is no pressure shift), widened as lines_tile_ranges widens.
-//   k_exomol_sum      lines_sum_tile (lines_device.h) over the node's own ranges: the bits of k_lines_sum for the same four numbers.
+//   k_exomol_sum      lines_sum_tile (lines_device.h) over the node's own ranges: the bits of k_lines_sum_nodes for the same four numbers.
 // With super-lines (hx_exomol_set_superlines) count, scan and prepare give way to:
 //   k_exomol_classify S once per transition into the launch row's strengths; strong (S >= S_min and S >= S_sl) and weak (S_min <=
 //                     S < S_sl) counted per workgroup.
@@ -378,12 +378,10 @@ __global__ __launch_bounds__(EXO_B) void k_exomol_merge(int n, size_t stride, Ex
 
 }  // namespace
 
-struct hx_exomol {
+struct hx_exomol : hx_node_rows {
     hx_context* ctx;
-    int states_max, trans_max, broad_max, points_max, per_launch, nodes_max, blocks_max, tiles_max;
-    bool want_fp64;
-    int n_states, max_jidx, n_trans, n_blocks, n_broad, n_jidx;
-    int n_nodes, n_points, n_tiles, rows_run;
+    int states_max, trans_max, broad_max, blocks_max, tiles_max;
+    int n_states, max_jidx, n_trans, n_blocks, n_broad, n_jidx, n_tiles;
     double *e, *g;                     // states_max
     int* jidx;
     int *up, *low;                     // trans_max, sorted by (nu_0, position)
@@ -396,8 +394,6 @@ struct hx_exomol {
     int *counts, *offsets;             // [per_launch][blocks_max]
     int* kept;                         // per_launch
     int2* ranges;                      // [per_launch][tiles_max], rows run with the stride n_tiles
-    float* slabs32;                    // [per_launch][points_max], rows run with the stride n_points
-    double* kappa64;                   // the same, want_fp64 only
     std::vector<double> host_e;        // set_transitions takes nu_0 = E[up] - E[low] from it
     double common[6];                  // molar_mass, cutoff, s_min, nu_first, dnu, widen of set_nodes
     hx_owned owned;
@@ -449,21 +445,17 @@ int hx_exomol_create(hx_context* ctx, int n_states_max, int n_trans_max, int n_b
     HX_REQUIRE(ctx, n_states_max >= 1 && n_states_max <= (1 << 27), HX_E_ARG, "1 ... 2^27 states");
     HX_REQUIRE(ctx, n_trans_max >= 1 && n_trans_max <= (1 << 27), HX_E_ARG, "1 ... 2^27 transitions");
     HX_REQUIRE(ctx, n_broadeners_max >= 1 && n_broadeners_max <= 64, HX_E_ARG, "1 ... 64 broadeners");
-    HX_REQUIRE(ctx, n_points_max >= 1 && n_points_max <= (1 << 30), HX_E_ARG, "1 ... 2^30 spectral points");
-    HX_REQUIRE(ctx, nodes_per_launch >= 1 && nodes_per_launch <= 65535, HX_E_ARG, "1 ... 65535 nodes per launch");
-    HX_REQUIRE(ctx, n_nodes_max >= 1 && n_nodes_max <= (1 << 24), HX_E_ARG, "1 ... 2^24 nodes");
-    hx_exomol* h = new (std::nothrow) hx_exomol();
+    hx_node_rows rows;
+    int rc = hx_node_rows_init(ctx, __func__, rows, n_points_max, nodes_per_launch, n_nodes_max, want_fp64);
+    if (rc) return rc;
+    hx_exomol* h = new (std::nothrow) hx_exomol{rows};
     if (!h) return hx_fail(ctx, HX_E_ARG, "no host memory");
     h->ctx = ctx;
     h->states_max = n_states_max;
     h->trans_max = n_trans_max;
     h->broad_max = n_broadeners_max;
-    h->points_max = n_points_max;
-    h->per_launch = nodes_per_launch;
-    h->nodes_max = n_nodes_max;
     h->blocks_max = hx_cdiv(n_trans_max, EXO_B);
     h->tiles_max = hx_cdiv(n_points_max, LINES_TILE);
-    h->want_fp64 = want_fp64 != 0;
     const size_t ns = (size_t)n_states_max, nt = (size_t)n_trans_max, np = (size_t)n_points_max, npl = (size_t)nodes_per_launch;
     const size_t nb = (size_t)h->blocks_max;
     const struct { const char* what; size_t bytes; void** where; } want[] = {
@@ -476,7 +468,6 @@ int hx_exomol_create(hx_context* ctx, int n_states_max, int n_trans_max, int n_b
         {"block offsets", npl * nb * 4, (void**)&h->offsets}, {"kept counts", npl * 4, (void**)&h->kept},
         {"tile ranges", npl * (size_t)h->tiles_max * sizeof(int2), (void**)&h->ranges}, {"fp32 slabs", npl * np * 4, (void**)&h->slabs32},
         {"fp64 rows", h->want_fp64 ? npl * np * 8 : 0, (void**)&h->kappa64}};
-    int rc = 0;
     for (const auto& w : want) {
         if (rc || !w.bytes) continue;
         if (hx_owned_alloc(ctx, h->owned, w.bytes, w.where))
@@ -699,14 +690,9 @@ int hx_exomol_set_nodes(hx_exomol* h, int n_nodes, const double* temp, const dou
     if (h->n_trans < 1) return hx_fail(ctx, HX_E_STATE, "hx_exomol_set_nodes: no transitions (hx_exomol_set_transitions)");
     if (h->n_broad < 1) return hx_fail(ctx, HX_E_STATE, "hx_exomol_set_nodes: no broadening table (hx_exomol_set_broadening)");
     HX_REQUIRE(ctx, temp && press && q_t, HX_E_ARG, "null array");
-    if (n_nodes < 1 || n_nodes > h->nodes_max)
-        return hx_fail(ctx, HX_E_ARG, "hx_exomol_set_nodes: %d nodes, the handle holds 1 ... %d", n_nodes, h->nodes_max);
-    if (n_points < 1 || n_points > h->points_max)
-        return hx_fail(ctx, HX_E_ARG, "hx_exomol_set_nodes: %d spectral points, the handle holds 1 ... %d", n_points, h->points_max);
-    const struct { const char* name; double v; } positive[] = {{"M", molar_mass}, {"cutoff", cutoff}, {"dnu", dnu}};
-    for (const auto& p : positive)
-        if (!(p.v > 0.0) || !std::isfinite(p.v))
-            return hx_fail(ctx, HX_E_ARG, "hx_exomol_set_nodes: %s = %g is not a finite number > 0", p.name, p.v);
+    int rc = hx_node_rows_counts(ctx, __func__, *h, n_nodes, n_points);
+    if (!rc) rc = hx_require_positive(ctx, __func__, -1, {{"M", molar_mass}, {"cutoff", cutoff}, {"dnu", dnu}});
+    if (rc) return rc;
     if (!(s_min >= 0.0) || !std::isfinite(s_min))
         return hx_fail(ctx, HX_E_ARG, "hx_exomol_set_nodes: S_min = %g is not a finite number >= 0", s_min);
     if (!std::isfinite(nu_first)) return hx_fail(ctx, HX_E_ARG, "hx_exomol_set_nodes: nu of point 0 = %g is not finite", nu_first);
@@ -714,15 +700,13 @@ int hx_exomol_set_nodes(hx_exomol* h, int n_nodes, const double* temp, const dou
         return hx_fail(ctx, HX_E_ARG, "hx_exomol_set_nodes: the super-line step %.17g is greater than the cut-off %.17g", h->sl_step,
                        cutoff);
     std::vector<ExoNode> nodes((size_t)n_nodes);
-    for (int k = 0; k < n_nodes; k++) {
-        const struct { const char* name; double v; } node[] = {{"T", temp[k]}, {"P", press[k]}, {"Q(T)", q_t[k]}};
-        for (const auto& p : node)
-            if (!(p.v > 0.0) || !std::isfinite(p.v))
-                return hx_fail(ctx, HX_E_ARG, "hx_exomol_set_nodes: node %d: %s = %g is not a finite number > 0", k, p.name, p.v);
+    for (int k = 0; k < n_nodes && !rc; k++) {
+        rc = hx_require_positive(ctx, __func__, k, {{"T", temp[k]}, {"P", press[k]}, {"Q(T)", q_t[k]}});
         nodes[k] = {temp[k], press[k], q_t[k]};
     }
+    if (rc) return rc;
     h->n_nodes = h->rows_run = 0;        // until the new records are there
-    int rc = exomol_settle(h);
+    rc = exomol_settle(h);
     // hx_h2d waits for the stream: node runs still queued have read the records they were queued with
     if (!rc) rc = hx_h2d(ctx, h->nodes, nodes.data(), nodes.size() * sizeof(ExoNode));
     if (rc) return rc;
@@ -739,14 +723,8 @@ int hx_exomol_set_nodes(hx_exomol* h, int n_nodes, const double* temp, const dou
 int hx_exomol_run_nodes(hx_exomol* h, int first_node, int n_nodes) {
     if (!h) return HX_E_ARG;
     hx_context* ctx = h->ctx;
-    if (h->n_nodes < 1) return hx_fail(ctx, HX_E_STATE, "hx_exomol_run_nodes: no nodes (hx_exomol_set_nodes)");
-    if (n_nodes < 1 || n_nodes > h->per_launch)
-        return hx_fail(ctx, HX_E_ARG, "hx_exomol_run_nodes: %d nodes in one call, the handle holds 1 ... %d per launch", n_nodes,
-                       h->per_launch);
-    if (first_node < 0 || first_node > h->n_nodes - n_nodes)
-        return hx_fail(ctx, HX_E_ARG, "hx_exomol_run_nodes: nodes %d ... %d, hx_exomol_set_nodes gave 0 ... %d", first_node,
-                       first_node + n_nodes - 1, h->n_nodes - 1);
-    int rc = exomol_settle(h);
+    int rc = hx_node_rows_check_run(ctx, __func__, "hx_exomol_set_nodes", *h, first_node, n_nodes);
+    if (!rc) rc = exomol_settle(h);
     if (!rc) rc = hx_stream_timer_start(ctx, h->t_prepare);
     if (rc) return rc;
     const size_t stride = (size_t)h->trans_max;
@@ -808,9 +786,7 @@ int hx_exomol_run_nodes(hx_exomol* h, int first_node, int n_nodes) {
 
 int hx_exomol_device_ptr(hx_exomol* h, const char* name, void** out_dptr) {
     if (!h || !name || !out_dptr) return HX_E_ARG;
-    if (strcmp(name, "slabs32") != 0) return hx_fail(h->ctx, HX_E_ARG, "hx_exomol_device_ptr: unknown name '%s'", name);
-    *out_dptr = h->slabs32;
-    return 0;
+    return hx_node_rows_device_ptr(h->ctx, __func__, *h, name, out_dptr);
 }
 
 int hx_exomol_get(hx_exomol* h, const char* name, void* out, size_t out_bytes) {
@@ -857,9 +833,8 @@ int hx_exomol_get(hx_exomol* h, const char* name, void* out, size_t out_bytes) {
     }
     const size_t rows = (size_t)h->rows_run;
     const hx_result results[] = {
-        {"slabs32", h->slabs32, rows * h->n_points * 4, true, no_run},
-        {"kappa64", h->kappa64, rows * h->n_points * 8, true,
-         h->want_fp64 ? no_run : "the handle keeps no fp64 rows (want_fp64 of hx_exomol_create)"},
+        hx_node_rows_slabs32(*h, no_run),
+        hx_node_rows_kappa64(*h, no_run, "the handle keeps no fp64 rows (want_fp64 of hx_exomol_create)"),
         {"kept", h->kept, rows * 4, true, no_run},
         {"tile_ranges", h->ranges, rows * h->n_tiles * sizeof(int2), true, no_run},
         {"timing_ms", h->timing, sizeof h->timing, false, nullptr}};

@@ -46,14 +46,14 @@ nu_i = numin + i * dnu, i = 0 ... (numax - numin) / dnu - 1, which ktable.Specie
 `-output_format text` writes the two columns nu and kappa (`.dat`, ktable.read_text_file).  Temperatures are integers in K
 because the file name carries them; pressure codes are the keys of ktable.pressure_table().
 
-`backend="device"`: k_lines_prepare writes the four numbers of every line for the node, k_lines_sum gives a workgroup a tile of
-TILE_POINTS consecutive points and walks the lines that can reach it, LDS_BLOCK at a time, in order, without atomics.
-`backend="numpy"` computes the same contract on the CPU, line after line over the points in reach: the checker of the device
-path, and what a machine without a GPU gets when it asks for it.
+`backend="device"`: a launch takes `nodes_per_launch` nodes.  k_lines_prepare_nodes writes the four numbers of every line per
+node, k_lines_sum_nodes gives a workgroup a tile of TILE_POINTS consecutive points of a node's row and walks the lines that can
+reach it, LDS_BLOCK at a time, in order, without atomics; the fp32 slabs stay on the device, and a handle made `with_fp64` keeps the
+rows before rounding as well (line_opacity).  `backend="numpy"` computes the same contract on the CPU, line after line over the
+points in reach: the checker of the device path, and what a machine without a GPU gets when it asks for it.
 
-`-ktable yes`: from the line list to the species' k-table without the files (line_ktable).  k_lines_prepare_nodes and
-k_lines_sum_nodes take `-nodes_per_launch` nodes per launch and leave their fp32 slabs on the device, where k_ktable_bins
-(ktable.KTableBuilder.run_device) sorts them on the same stream; nothing but the table comes back.  The containers are the ones
+`-ktable yes`: from the line list to the species' k-table without the files (line_ktable): k_ktable_bins
+(ktable.KTableBuilder.run_device) sorts the slabs on the same stream, and nothing but the table comes back.  The containers are those
 `lines.py` followed by `ktable.py` writes, to the bit, and what makes them so is part of the contract: the range is the one chunk
 0 ... numax (a chunk's nu is lo + i dnu, so chunks have other bits); the line kernel steps with the `-dnu` given, the k-table's
 axis with numax / points, which is what ktable.py computes from a file's length -- the two are not always the same double, and each
@@ -290,32 +290,34 @@ def count_pairs(nu0p, nu_first, dnu, n_points, cutoff):
 
 # ---- device ------------------------------------------------------------------------------------------------------------
 class LineOpacity(_nodes.NodeOpacity):
-    """hx_lines: a resident line list of up to n_lines_max lines, nodes of up to n_points_max spectral points"""
+    """hx_lines: a resident line list of up to n_lines_max lines, nodes of up to n_points_max spectral points, nodes_per_launch
+    per launch into fp32 slabs that stay on the device; `with_fp64`: the rows before rounding as well"""
 
     PREFIX = "hx_lines"
 
-    def __init__(self, ctx, n_lines_max, n_points_max, nodes_per_launch=0, n_nodes_max=0):
-        """`nodes_per_launch` > 0: the handle also runs up to that many of n_nodes_max nodes per launch into fp32 slabs that
-        stay on the device (set_nodes, run_nodes, slab_pointer)"""
+    def __init__(self, ctx, n_lines_max, n_points_max, nodes_per_launch, n_nodes_max, with_fp64=False):
         self.n_lines_max, self.n_points_max = int(n_lines_max), int(n_points_max)
-        self.nodes_per_launch, self.n_nodes_max = int(nodes_per_launch), int(n_nodes_max)
-        self.n_lines = self.n_points = self.n_nodes = self.node_points = self.rows_run = 0
-        if self.nodes_per_launch > 0:
-            self._create(ctx, self.n_lines_max, self.n_points_max, self.nodes_per_launch, self.n_nodes_max,
-                         constructor="create_nodes")
-        else:
-            self._create(ctx, self.n_lines_max, self.n_points_max)
+        self.nodes_per_launch, self.n_nodes_max, self.with_fp64 = int(nodes_per_launch), int(n_nodes_max), bool(with_fp64)
+        self.n_lines = self.n_nodes = self.n_points = self.rows_run = 0
+        self._create(ctx, self.n_lines_max, self.n_points_max, self.nodes_per_launch, self.n_nodes_max, int(self.with_fp64))
+
+    @classmethod
+    def of(cls, ctx, lines, n_points_max, nodes_per_launch, n_nodes_max, with_fp64=False):
+        """a handle that holds the list"""
+        h = cls(ctx, len(lines["nu0"]), n_points_max, nodes_per_launch, n_nodes_max, with_fp64)
+        try:
+            h.set_lines(lines)
+        except Exception:
+            h.close()
+            raise
+        return h
 
     def set_lines(self, lines):
         arr = [np.ascontiguousarray(lines[k], np.float64).reshape(-1) for k in FIELDS]
         assert all(len(a) == len(arr[0]) for a in arr)
+        self._reset_nodes()
         self._call("set_lines", len(arr[0]), *[dp(a) for a in arr])
         self.n_lines = len(arr[0])
-
-    def run(self, temp, press, q_t, q_ref, molar_mass, self_fraction, cutoff, nu_first, dnu, n_points):
-        self._call("run", float(temp), float(press), float(q_t), float(q_ref), float(molar_mass), float(self_fraction),
-                   float(cutoff), float(nu_first), float(dnu), int(n_points))
-        self.n_points = int(n_points)
 
     def set_nodes(self, temps, pressures, q_t, q_ref, molar_mass, self_fraction, cutoff, nu_first, dnu, n_points):
         """T, P and Q(T) per node, and what the nodes share; the tiles' line ranges go to the device once, here"""
@@ -324,15 +326,15 @@ class LineOpacity(_nodes.NodeOpacity):
         self._reset_nodes()
         self._call("set_nodes", len(arr[0]), dp(arr[0]), dp(arr[1]), dp(arr[2]), float(q_ref), float(molar_mass),
                    float(self_fraction), float(cutoff), float(nu_first), float(dnu), int(n_points))
-        self.n_nodes, self.node_points = len(arr[0]), int(n_points)
+        self.n_nodes, self.n_points = len(arr[0]), int(n_points)
 
     def _results(self):
-        return {"kappa64": self.n_points, "kappa32": (self.n_points, np.float32), "line_params": (4, self.n_lines),
-                "slabs32": ((self.rows_run, self.node_points), np.float32), "timing_ms": 2}
+        return {"slabs32": ((self.rows_run, self.n_points), np.float32), "kappa64": (self.rows_run, self.n_points),
+                "line_params": (self.rows_run, 4, self.n_lines), "timing_ms": 2}
 
 
 def device_voigt(ctx, x, y):
-    """k_lines_sum's own K at pairs (x, y)"""
+    """the sum kernels' own K at pairs (x, y)"""
     from . import _lib
     x, y = (np.ascontiguousarray(a, np.float64).reshape(-1) for a in (x, y))
     assert len(x) == len(y)
@@ -351,18 +353,11 @@ def _check_node_inputs(temps, pressures, nu_grid, molar_mass, self_fraction, cut
     return out
 
 
-def _holding(ctx, lines, n_points_max):
-    """a handle that holds the list"""
-    handle = LineOpacity(ctx, len(lines["nu0"]), n_points_max)
-    handle.set_lines(lines)
-    return handle
-
-
 def line_opacity(lines, q_table, temps, pressures_cgs, nu_grid, molar_mass=None, self_fraction=0.0, cutoff=DEFAULT_CUTOFF,
-                 backend="device", ctx=None, handle=None, timing=None):
+                 backend="device", ctx=None, nodes_per_launch=4, handle=None, timing=None):
     """kappa [T][P][nu] in cm^2 g^-1, fp64.  `lines`: the seven arrays of FIELDS (sorted here); `q_table`: (T, Q); `nu_grid`:
-    (nu of point 0, dnu, points); `handle`: a LineOpacity that already holds the list.  `timing` receives prepare_ms, sum_ms and
-    pairs, summed over the nodes, and from the numpy backend pairs_by_region [4]"""
+    (nu of point 0, dnu, points); `handle`: a LineOpacity with fp64 rows that already holds the list.  `timing` receives
+    prepare_ms, sum_ms and pairs, summed over the nodes, and from the numpy backend pairs_by_region [4]"""
     _nodes.check_backend("lines", backend)
     temps, pressures, (nu_first, dnu, n_points) = _check_node_inputs(temps, pressures_cgs, nu_grid, molar_mass, self_fraction, cutoff)
     if handle is None:
@@ -379,14 +374,21 @@ def line_opacity(lines, q_table, temps, pressures_cgs, nu_grid, molar_mass=None,
                 out[it, ip] = numpy_node(prm, nu_first, dnu, n_points, cutoff, molar_mass, by_region if timing is not None else None)
         pairs = int(by_region.sum())
     else:
-        with _nodes.opened(ctx, handle, lambda c: _holding(c, lines, n_points)) as h:
-            for it, t in enumerate(temps):
-                for ip, p in enumerate(pressures):
-                    h.run(t, p, q_t[it], q_ref, molar_mass, self_fraction, cutoff, nu_first, dnu, n_points)
-                    out[it, ip] = h.get("kappa64")
-                    if timing is not None:
-                        ms += h.get("timing_ms")
-                        pairs += count_pairs(h.get("line_params")[0], nu_first, dnu, n_points, cutoff)
+        nodes = [(t, p, q_t[it]) for it, t in enumerate(temps) for p in pressures]
+        flat = out.reshape(len(nodes), n_points)
+
+        def set_nodes(h, part):
+            h.set_nodes([n[0] for n in part], [n[1] for n in part], [n[2] for n in part], q_ref, molar_mass, self_fraction, cutoff,
+                        nu_first, dnu, n_points)
+
+        def collect(h, rows):
+            nonlocal pairs
+            flat[rows] = h.get("kappa64")
+            if timing is not None:
+                pairs += sum(count_pairs(prm[0], nu_first, dnu, n_points, cutoff) for prm in h.get("line_params"))
+        ms = _nodes.nodes_in_turns(
+            ctx, handle, lambda c: LineOpacity.of(c, lines, n_points, max(1, min(int(nodes_per_launch), len(nodes))), len(nodes), True),
+            nodes, set_nodes, collect)
     if timing is not None:
         timing["prepare_ms"] = timing.get("prepare_ms", 0.0) + float(ms[0])
         timing["sum_ms"] = timing.get("sum_ms", 0.0) + float(ms[1])
@@ -421,8 +423,7 @@ class LineSlabs(_nodes.NodeSlabs):
         self.pairs = int(self.by_region.sum())
 
     def open_handle(self, ctx, per, nodes):
-        self.handle = h = LineOpacity(ctx, len(self.lines["nu0"]), self.n_points, per, len(nodes))
-        h.set_lines(self.lines)
+        self.handle = h = LineOpacity.of(ctx, self.lines, self.n_points, per, len(nodes))
         h.set_nodes([n[1] for n in nodes], [n[2] for n in nodes], [self.q_t[n[0]] for n in nodes], self.q_ref, self.molar_mass,
                     self.self_fraction, self.cutoff, 0.0, self.dnu, self.n_points)
 
@@ -495,8 +496,11 @@ def main(argv=None):
                                                       opt.backend, None, opt.nodes_per_launch, None, timing),
             lambda timing: "k_lines_prepare_nodes %.1f ms, k_lines_sum_nodes %.1f ms, k_ktable_bins %.1f ms" % (
                 timing["prepare_ms"], timing["sum_ms"], timing["device_ms"][0]), t0, pairs=True)
+    n_nodes = len(temps) * len(pressures)
     return _nodes.main_files(
-        "lines", opt, chunks, temps, codes, lambda ctx, n_points_max: _holding(ctx, lines, n_points_max),
+        "lines", opt, chunks, temps, codes,
+        lambda ctx, n_points_max: LineOpacity.of(ctx, lines, n_points_max, max(1, min(opt.nodes_per_launch, n_nodes)), n_nodes, True),
         lambda nu_grid, ctx, handle, timing: line_opacity(lines, q_table, temps, pressures, nu_grid, molar_mass, opt.self_fraction,
-                                                          opt.cutoff, opt.backend, ctx, handle, timing),
-        lambda timing: "k_lines_prepare %.1f ms, k_lines_sum %.1f ms" % (timing["prepare_ms"], timing["sum_ms"]), t0, pairs=True)
+                                                          opt.cutoff, opt.backend, ctx, opt.nodes_per_launch, handle, timing),
+        lambda timing: "k_lines_prepare_nodes %.1f ms, k_lines_sum_nodes_fp64 %.1f ms" % (timing["prepare_ms"], timing["sum_ms"]), t0,
+        pairs=True)

@@ -712,56 +712,47 @@ int hx_mie_get(hx_mie* mie, const char* name, void* out, size_t out_bytes);
 
 /* ---- (11) Line-by-line opacities of a line list on a spectral grid (csrc/lines.hip; the contract and the host side are
  * helios_amd/lines.py) -----------------------------------------------------------------------------------------------------------
- * Per (T, P) node: k_lines_prepare writes nu_0', s = S(T) a / sqrt pi, a = sqrt(ln 2) / alpha_D and y = max(a gamma_L, 1e-8) of every
- * line; k_lines_sum gives a workgroup a tile of consecutive points nu_i = nu_first + i dnu and adds, per point and in the order of
- * the list, s K(a (nu_i - nu_0'), y) of the lines with |nu_i - nu_0'| <= cutoff, K = Re w(x + i y) in four regions of |z|.  The
- * host finds a tile's lines by binary search on nu_0, widened by cutoff + max |delta_air| P_atm.  No atomics.
+ * Per (T, P) node: k_lines_prepare_nodes writes nu_0', s = S(T) a / sqrt pi, a = sqrt(ln 2) / alpha_D and y = max(a gamma_L, 1e-8) of
+ * every line; k_lines_sum_nodes gives a workgroup a tile of consecutive points nu_i = nu_first + i dnu and adds, per point and in the
+ * order of the list, s K(a (nu_i - nu_0'), y) of the lines with |nu_i - nu_0'| <= cutoff, K = Re w(x + i y) in four regions of |z|.
+ * The host finds a tile's lines by binary search on nu_0, widened by cutoff + max |delta_air| P_atm.  No atomics.  The node is a grid
+ * dimension: a launch takes up to nodes_per_launch nodes into fp32 slabs that stay on the device, for a consumer there
+ * (hx_kt_run_device), and a row does not depend on the nodes beside it.
  *
- *   hx_lines_create     the largest number of lines and of spectral points the handle holds
+ *   hx_lines_create     the largest number of lines, of spectral points, of nodes per launch and of nodes the handle holds: params
+ *                       [nodes_per_launch][4][n_lines_max], the fp32 slabs [nodes_per_launch][n_points_max], with want_fp64 the
+ *                       same rows before rounding, and the records of n_nodes_max nodes.  An allocation the device does not give is
+ *                       refused with its byte count
  *   hx_lines_set_lines  the seven per-line arrays, sorted by nu0 (ties in any order the caller fixed); they stay resident.
  *                       Refused with HX_E_ARG and the line: a value that is not finite, nu0 <= 0, s_ref < 0, a list that is not
  *                       sorted, more lines than the handle holds
- *   hx_lines_run        one node: T [K], P [dyne cm^-2], Q(T), Q(296), the molar mass [g/mol], the self-broadening fraction, the
- *                       cut-off [cm^-1], nu of point 0, dnu, the number of points.  A grid larger than the handle holds or a
- *                       value out of range is refused before any launch.  Returns when the results are there
- *   hx_lines_get        "kappa64" (double per point, cm^2 g^-1), "kappa32" (float per point: kappa64 rounded once),
- *                       "line_params" (double[4][n_lines]: nu_0', s, a, y of the last node), "timing_ms" (double[2]: ms in
- *                       k_lines_prepare and in k_lines_sum, of the last run)
- *   hx_lines_voigt      the sum's own K(x, y) at n pairs of host arrays, for the tests
- *
- * Several nodes per launch, for a consumer on the device (hx_kt_run_device): k_lines_prepare_nodes and k_lines_sum_nodes take the
- * node as a grid dimension and apply the single-node kernels' statements; the sum stores fp32 only.  Every row of "slabs32" equals,
- * bit for bit, the "kappa32" hx_lines_run gives for that node alone.
- *
- *   hx_lines_create_nodes  a handle of hx_lines_create that also owns params [nodes_per_launch][4][n_lines_max], the fp32 slabs
- *                       [nodes_per_launch][n_points_max], the records of up to n_nodes_max nodes and the tiles' line ranges.  An
- *                       allocation the device does not give is refused with its byte count
- *   hx_lines_set_nodes  T, P, Q(T) per node and what the nodes share, checked as hx_lines_run checks them (a refusal names the
- *                       node and the value).  The tiles' line ranges are searched once per distinct pressure -- the reach is
- *                       cutoff + max |delta_air| P_atm -- and go to the device with the records: the only upload of a table
+ *   hx_lines_set_nodes  T [K], P [dyne cm^-2], Q(T) per node and what the nodes share: Q(296), the molar mass [g/mol], the
+ *                       self-broadening fraction, the cut-off [cm^-1], nu of point 0, dnu, the number of points.  A grid larger
+ *                       than the handle holds or a value out of range is refused, with the node and the value.  The tiles' line
+ *                       ranges are searched once per distinct pressure and go to the device with the records: the only upload of
+ *                       a table
  *   hx_lines_run_nodes  queues the prepare and the sum of the nodes first_node ... first_node + n_nodes - 1, n_nodes <=
  *                       nodes_per_launch, on the context's stream: slab rows 0 ... n_nodes - 1, row stride n_points.  No copy and
  *                       no wait; the timers settle in the next call or in hx_lines_get.  Nodes beyond hx_lines_set_nodes' count or
  *                       more than the handle holds per launch are refused before any launch, with the counts
  *   hx_lines_device_ptr "slabs32": the slab buffer's device address
- *   hx_lines_get        also "slabs32" (float [n_nodes of the last hx_lines_run_nodes][n_points]); after node runs "timing_ms" is
- *                       the ms in the two node kernels summed since hx_lines_set_nodes
+ *   hx_lines_get        of the rows of the last hx_lines_run_nodes: "slabs32" (float [rows][n_points], cm^2 g^-1), "kappa64" (double
+ *                       [rows][n_points], want_fp64 only: a slab is it rounded once), "line_params" (double [rows][4][n_lines]:
+ *                       nu_0', s, a, y); "timing_ms" (double[2]: ms in the two kernels summed since hx_lines_set_nodes)
+ *   hx_lines_voigt      the sum's own K(x, y) at n pairs of host arrays, for the tests
  */
 typedef struct hx_lines hx_lines;
-int hx_lines_create(hx_context* ctx, int n_lines_max, int n_points_max, hx_lines** out_lines);
+int hx_lines_create(hx_context* ctx, int n_lines_max, int n_points_max, int nodes_per_launch, int n_nodes_max, int want_fp64,
+                    hx_lines** out_lines);
 int hx_lines_destroy(hx_lines* lines);
 int hx_lines_set_lines(hx_lines* lines, int n_lines, const double* nu0, const double* s_ref, const double* gamma_air,
                        const double* gamma_self, const double* e_low, const double* n_air, const double* delta_air);
-int hx_lines_run(hx_lines* lines, double temp, double press, double q_t, double q_ref, double molar_mass, double x_self,
-                 double cutoff, double nu_first, double dnu, int n_points);
-int hx_lines_get(hx_lines* lines, const char* name, void* out, size_t out_bytes);
-int hx_lines_voigt(hx_context* ctx, int n, const double* x, const double* y, double* out);
-int hx_lines_create_nodes(hx_context* ctx, int n_lines_max, int n_points_max, int nodes_per_launch, int n_nodes_max,
-                          hx_lines** out_lines);
 int hx_lines_set_nodes(hx_lines* lines, int n_nodes, const double* temp, const double* press, const double* q_t, double q_ref,
                        double molar_mass, double x_self, double cutoff, double nu_first, double dnu, int n_points);
 int hx_lines_run_nodes(hx_lines* lines, int first_node, int n_nodes);
 int hx_lines_device_ptr(hx_lines* lines, const char* name, void** out_dptr);
+int hx_lines_get(hx_lines* lines, const char* name, void* out, size_t out_bytes);
+int hx_lines_voigt(hx_context* ctx, int n, const double* x, const double* y, double* out);
 
 /* ---- (12) Collision-induced absorption from the blocks of a HITRAN CIA file (csrc/cia.hip; the contract and the host side are
  * helios_amd/cia.py) -------------------------------------------------------------------------------------------------------------

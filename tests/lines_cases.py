@@ -60,6 +60,37 @@ def join(*lists):
     return dict((k, arr[k][order]) for k in lr.FIELDS)
 
 
+def parent_bit_cases():
+    """the cases of tests/golden/lines/parent_bits.npz, data only: per case the list, the nodes (T, P), x_self, the cut-off,
+    the grid, what the handle holds beyond the list and the grid, and the nodes per launch.  Case 4 is a call of
+    lines.line_opacity and brings `temps` and `press` in place of nodes"""
+    from helios_amd.lines import ATM, LDS_BLOCK, TILE_POINTS
+    nu0, dnu = 1000.0, 0.25
+    n2 = TILE_POINTS + 1
+    spread = synthetic_lines(LDS_BLOCK + 1, nu0 + 0.02 * TILE_POINTS * dnu, nu0 + 0.98 * TILE_POINTS * dnu, seed=n2)
+    last = nu0 + TILE_POINTS * dnu
+    far = one_line(last + 25.0 + 5.0, s_ref=1e-19, delta_air=-0.01)
+    return [
+        dict(name="case1", line=one_line(100.0), nodes=[(300.0, 1e5)], x_self=0.0, cutoff=25.0, grid=(100.0, 0.25, 1),
+             more_lines=0, more_points=0, per_launch=1),
+        dict(name="case2", line=join(spread, synthetic_lines(40, nu0, nu0 + n2 * dnu, seed=5)),
+             nodes=[(300.0, 1e3), (900.0, 1e6), (1500.0, 1e3)], x_self=0.25, cutoff=2.0, grid=(nu0, dnu, n2),
+             more_lines=5, more_points=3, per_launch=2),
+        dict(name="case3", line=join(synthetic_lines(LDS_BLOCK + 30, nu0, last - 60.0, seed=12), far),
+             nodes=[(300.0, 1e-4), (300.0, 1e3 * ATM), (1200.0, 1e5)], x_self=0.1, cutoff=25.0, grid=(nu0, dnu, n2),
+             more_lines=0, more_points=0, per_launch=3),
+        dict(name="case4", line=synthetic_lines(60, 995.0, 1030.0, seed=15), temps=[300.0, 1200.0], press=[1e2, 1e7], x_self=0.1,
+             cutoff=5.0, grid=(1000.0, 0.05, 500)),
+    ]
+
+
+def parent_bits():
+    if "parent_bits" not in _kept:
+        with np.load(os.path.join(HERE, "golden", "lines", "parent_bits.npz")) as f:
+            _kept["parent_bits"] = {k: f[k] for k in f.files}
+    return _kept["parent_bits"]
+
+
 def _fit(fmt, width, v):
     s = fmt % v
     if len(s) > width and s.startswith("0."):

@@ -1,5 +1,5 @@
-"""k_lines_prepare, k_lines_sum and the sum's K (csrc/lines.hip) through hx_lines and lines.py on the device, under the rule of
-tests/lines_cases.py: K at the goldens; point counts around the tile and line counts around the LDS block, derived from the
+"""k_lines_prepare_nodes, k_lines_sum_nodes_fp64 and the sum's K (csrc/lines.hip) through hx_lines and lines.py on the device,
+under the rule of tests/lines_cases.py: K at the goldens; point counts around the tile and line counts around the LDS block, derived from the
 constants the module exports; the placements at which the sum decides; and a species from its line list to a k-table."""
 import os
 
@@ -24,19 +24,19 @@ def ctx():
 
 
 def run_node(ctx, line, temp, press, grid, cutoff, x_self=0.0, molar_mass=lc.M_H2O, twice=True):
-    """(kappa64, kappa32, line_params, timing) of one node through a handle of its own; the node is run twice and the bits
-    compared"""
+    """(kappa64, kappa32, line_params, timing) of one node through a handle of its own, one node per launch with fp64 rows;
+    the node is run twice and the bits compared"""
     q = lc.q_table()
-    h = lines.LineOpacity(ctx, len(line["nu0"]), grid[2])
+    h = lines.LineOpacity(ctx, len(line["nu0"]), grid[2], 1, 1, with_fp64=True)
     try:
         h.set_lines(line)
-        args = (temp, press, lines.partition_value(q, temp), lines.partition_value(q, 296.0), molar_mass, x_self, cutoff) + grid
-        h.run(*args)
-        out = h.get("kappa64"), h.get("kappa32"), h.get("line_params"), h.get("timing_ms")
+        h.set_nodes([temp], [press], [lines.partition_value(q, temp)], lines.partition_value(q, 296.0), molar_mass, x_self, cutoff, *grid)
+        h.run_nodes(0, 1)
+        out = h.get("kappa64")[0], h.get("slabs32")[0], h.get("line_params")[0], h.get("timing_ms")
         if twice:
-            h.run(*args)
-            assert np.array_equal(h.get("kappa64").view(np.uint64), out[0].view(np.uint64))
-            assert np.array_equal(h.get("line_params").view(np.uint64), out[2].view(np.uint64))
+            h.run_nodes(0, 1)
+            assert np.array_equal(h.get("kappa64")[0].view(np.uint64), out[0].view(np.uint64))
+            assert np.array_equal(h.get("line_params")[0].view(np.uint64), out[2].view(np.uint64))
         return out
     finally:
         h.close()
@@ -77,7 +77,7 @@ def test_the_kernels_k_against_mpmath(ctx, reg):
     assert dev.max() <= lc.GOLDEN_BOUND
 
 
-# ---- sizes at which k_lines_sum changes path ------------------------------------------------------------------------------
+# ---- sizes at which the sum changes path ------------------------------------------------------------------------------
 DNU, CUTOFF = 0.25, 2.0                       # a tile is TILE / 4 cm^-1 wide, a line reaches 17 points
 
 
@@ -181,30 +181,31 @@ def test_both_loops_in_one_tile_and_a_wavefront_across_all_four_regions(ctx):
 def test_refusals_name_the_count_and_leave_the_handle_usable(ctx):
     line = lc.synthetic_lines(20, 1000.0, 1050.0, seed=2)
     q = lc.q_table()
-    node = (700.0, 1e5, lines.partition_value(q, 700.0), lines.partition_value(q, 296.0), lc.M_H2O, 0.0, CUTOFF)
-    h = lines.LineOpacity(ctx, 19, 300)
+    node = ([700.0], [1e5], [lines.partition_value(q, 700.0)], lines.partition_value(q, 296.0), lc.M_H2O, 0.0, CUTOFF)
+    h = lines.LineOpacity(ctx, 19, 300, 1, 1, with_fp64=True)
     try:
         with pytest.raises(HeliosHipError, match=r"20 lines, the handle holds 1 \.\.\. 19") as e:
             h.set_lines(line)
         assert "status 1:" in str(e.value)
         with pytest.raises(HeliosHipError, match="no line list"):
-            h.run(*(node + (1000.0, DNU, 200)))
+            h.set_nodes(*(node + (1000.0, DNU, 200)))
         fewer = dict((k, line[k][:19]) for k in lr.FIELDS)
         h.set_lines(fewer)
-        with pytest.raises(HeliosHipError, match="no node has been run"):
+        with pytest.raises(HeliosHipError, match="no nodes have been run"):
             h.get("kappa64")
         with pytest.raises(HeliosHipError, match=r"301 spectral points, the handle holds 1 \.\.\. 300"):
-            h.run(*(node + (1000.0, DNU, 301)))
+            h.set_nodes(*(node + (1000.0, DNU, 301)))
         with pytest.raises(HeliosHipError, match=r"T = -700 is not a finite number > 0"):
-            h.run(*((-700.0,) + node[1:] + (1000.0, DNU, 200)))
+            h.set_nodes(*(([-700.0],) + node[1:] + (1000.0, DNU, 200)))
         with pytest.raises(HeliosHipError, match=r"x_self = 1\.5 lies outside \[0, 1\]"):
-            h.run(*(node[:5] + (1.5, CUTOFF, 1000.0, DNU, 200)))
+            h.set_nodes(*(node[:5] + (1.5, CUTOFF, 1000.0, DNU, 200)))
         unsorted = dict((k, fewer[k][::-1].copy()) for k in lr.FIELDS)
         with pytest.raises(HeliosHipError, match=r"line 1: nu0 = .* lies below line 0's .*: the list is sorted"):
             h.set_lines(unsorted)
         h.set_lines(fewer)
-        h.run(*(node + (1000.0, DNU, 200)))
-        got = h.get("kappa64")
+        h.set_nodes(*(node + (1000.0, DNU, 200)))
+        h.run_nodes(0, 1)
+        got = h.get("kappa64")[0]
     finally:
         h.close()
     ld, f64 = lc.restated(fewer, 700.0, 1e5, 0.0, CUTOFF, 1000.0, DNU, 200)

@@ -1,6 +1,6 @@
 """Several nodes per launch (k_lines_prepare_nodes, k_lines_sum_nodes) and the k-table built from their slabs on the device
 (hx_kt_run_device, lines.line_ktable, `lines.py -ktable yes`).  Every comparison is bit for bit: a row of "slabs32" against the
-"kappa32" LineOpacity.run gives for that node alone, a table against lines.py (files) followed by ktable.build_species."""
+"slabs32" of that node run alone through a handle for one node, a table against lines.py (files) followed by ktable.build_species."""
 import os
 
 import numpy as np
@@ -31,15 +31,15 @@ def q_of(temps):
 
 
 def alone(ctx, line, nodes, cutoff, grid):
-    """kappa32 [node][n_points] of LineOpacity.run, node after node, through a single-node handle"""
-    q_t, q_ref = q_of([n[0] for n in nodes])
-    h = lines.LineOpacity(ctx, len(line["nu0"]), grid[2])
+    """slabs32 [node][n_points], each node through a one-node handle by itself: a plain handle, and a set_nodes of the one node"""
+    h = lines.LineOpacity(ctx, len(line["nu0"]), grid[2], 1, 1)
     try:
         h.set_lines(line)
         rows = []
-        for (t, p), q in zip(nodes, q_t):
-            h.run(t, p, q, q_ref, lc.M_H2O, X_SELF, cutoff, *grid)
-            rows.append(h.get("kappa32"))
+        for node in nodes:
+            set_nodes(h, [node], cutoff, grid)
+            h.run_nodes(0, 1)
+            rows.append(h.get("slabs32")[0])
         return np.stack(rows)
     finally:
         h.close()
@@ -140,14 +140,6 @@ def test_batch_sizes_and_refusals(ctx):
         assert np.all(h.get("timing_ms") > 0)
     finally:
         h.close()
-    single = lines.LineOpacity(ctx, 10, 10)
-    try:
-        with pytest.raises(HeliosHipError, match="the handle runs one node at a time"):
-            set_nodes(single, nodes[:1], CUTOFF, (NU0, DNU, 10))
-        with pytest.raises(HeliosHipError, match="the handle holds no slabs"):
-            single.slab_pointer()
-    finally:
-        single.close()
 
 
 def test_unlike_nodes_in_one_launch(ctx):
@@ -186,10 +178,12 @@ def test_no_dependence_on_what_ran_before(ctx):
         set_nodes(h, nodes_b, 5.0, grid_b)
         h.run_nodes(0, 2)
         same_bits(h.get("slabs32"), alone(ctx, line, nodes_b, 5.0, grid_b), "grid b on the same handle")
-        h.run(400.0, 1e4, q_of([400.0])[0][0], q_of([400.0])[1], lc.M_H2O, X_SELF, 5.0, *grid_b)      # the single node next to them
-        assert h.get("kappa32").shape == (grid_b[2],) and h.get("timing_ms")[1] > 0
+        set_nodes(h, [(400.0, 1e4)], 5.0, grid_b)                             # one other node between the two runs
+        h.run_nodes(0, 1)
+        assert h.get("slabs32").shape == (1, grid_b[2]) and h.get("timing_ms")[1] > 0
+        set_nodes(h, nodes_b, 5.0, grid_b)
         h.run_nodes(1, 1)
-        same_bits(h.get("slabs32"), alone(ctx, line, nodes_b[1:], 5.0, grid_b), "after a single-node run")
+        same_bits(h.get("slabs32"), alone(ctx, line, nodes_b[1:], 5.0, grid_b), "after a run of one other node")
     finally:
         h.close()
 

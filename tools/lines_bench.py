@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Writes profiles/lines_bench.json: a synthetic list of 1e5 lines over 0 - 30000 cm^-1 at dnu = 0.01 cm^-1 with a cut-off of
-25 cm^-1, at one low-pressure and one high-pressure node.  k_lines_prepare and k_lines_sum by HIP events
-(hx_lines_get("timing_ms")), the median of seven runs behind a warm-up, in one process; the pairs (line, point) evaluated, which
+25 cm^-1, at one low-pressure and one high-pressure node, one node per launch with fp64 rows.  k_lines_prepare_nodes and
+k_lines_sum_nodes_fp64 by HIP events (hx_lines_get("timing_ms"); the keys keep the names k_lines_prepare_ms and k_lines_sum_ms of
+the single-node kernels they replace), the median of seven runs behind a warm-up, in one process; the pairs (line, point) evaluated, which
 is arithmetic, and from them the pairs per second; the numpy backend on the same node with OMP_NUM_THREADS as set, which also
 counts the pairs per region of |z|.
 
@@ -44,19 +45,20 @@ def main(argv):
            "points": GRID[2], "runs": RUNS, "tile_points": lines.TILE_POINTS, "lds_block": lines.LDS_BLOCK, "nodes": {}}
     ctx = Context(int(os.environ.get("HELIOS_DEVICE", "0")))
     out["device"] = ctx.name()
-    h = lines.LineOpacity(ctx, n_lines, GRID[2])
+    h = lines.LineOpacity(ctx, n_lines, GRID[2], 1, 1, with_fp64=True)
     kept = {}
     try:
         h.set_lines(line)
         for label, temp, press in NODES:
             q_t = lines.partition_value(q_table, temp)
             ms = []
-            for r in range(RUNS + 1):                 # the first run is the warm-up
-                h.run(temp, press, q_t, q_ref, MOLAR_MASS, 0.0, CUTOFF, *GRID)
+            for r in range(RUNS + 1):                 # the first run is the warm-up; set_nodes sets the times to zero
+                h.set_nodes([temp], [press], [q_t], q_ref, MOLAR_MASS, 0.0, CUTOFF, *GRID)
+                h.run_nodes(0, 1)
                 ms.append(h.get("timing_ms"))
             ms = np.array(ms)
-            pairs = lines.count_pairs(h.get("line_params")[0], GRID[0], GRID[1], GRID[2], CUTOFF)
-            kept[label] = h.get("kappa64")
+            pairs = lines.count_pairs(h.get("line_params")[0][0], GRID[0], GRID[1], GRID[2], CUTOFF)
+            kept[label] = h.get("kappa64")[0]
             med = np.median(ms[1:], axis=0)
             out["nodes"][label] = {"temperature": temp, "pressure": press, "pairs": pairs,
                                    "k_lines_prepare_ms": {"median": float(med[0]), "min": float(ms[1:, 0].min()),

@@ -5,9 +5,10 @@ dnu = 0.01 cm^-1 (3e6 points, cut-off 25 cm^-1), 322 bins x 20 Gauss points, 4 t
 route puts 16 files of 12 MB, 192 MB, into the machine's temporary directory; they are removed at the end.
 
 One process.  (a) the whole routes, lines.main + ktable.main against lines.main -ktable yes, by the wall clock, alternating,
-medians of five behind a warm-up of each; both read the same `.par` file, whose parsing is part of both.  (b) k_lines_sum per
-node (hx_lines_run, the 16 nodes one after the other) and k_lines_sum_nodes per node (four nodes per launch) by HIP events, seven
-repeats behind a warm-up, and the spread of k_lines_sum's repeats.  (c) the bytes each route moves across PCIe and the disk:
+medians of five behind a warm-up of each; both read the same `.par` file, whose parsing is part of both.  (b) k_lines_sum_nodes_fp64
+per node (one node per launch, the 16 nodes one after the other; the keys keep the name k_lines_sum of the single-node kernel it
+replaces) and k_lines_sum_nodes per node (four nodes per launch) by HIP events, seven repeats behind a warm-up, and the spread of
+the former's repeats.  (c) the bytes each route moves across PCIe and the disk:
 arithmetic on the array shapes, not a measurement.  (d) whether the two routes' tables are equal to the bit.
 
     python tools/lines_ktable_bench.py [--out FILE] [--lines N]
@@ -110,23 +111,28 @@ def main(argv):
         nodes = [(float(tt), p, lines.partition_value(q_table, tt)) for tt in sorted(temps) for p in press]
         ctx = Context(int(os.environ.get("HELIOS_DEVICE", "0")))
         out["device"] = ctx.name()
-        h = lines.LineOpacity(ctx, len(line["nu0"]), n_points, PER_LAUNCH, n_nodes)
+        single, batch = np.zeros((KERNEL_RUNS + 1, n_nodes, 2)), np.zeros((KERNEL_RUNS + 1, 2))
         try:
-            h.set_lines(line)
-            single = np.zeros((KERNEL_RUNS + 1, n_nodes, 2))
-            for r in range(KERNEL_RUNS + 1):               # the first repeat is the warm-up
-                for k, (tt, p, q) in enumerate(nodes):
-                    h.run(tt, p, q, q_ref, MOLAR_MASS, 0.0, CUTOFF, 0.0, DNU, n_points)
-                    single[r, k] = h.get("timing_ms")
-            batch = np.zeros((KERNEL_RUNS + 1, 2))
-            for r in range(KERNEL_RUNS + 1):
-                h.set_nodes([n[0] for n in nodes], [n[1] for n in nodes], [n[2] for n in nodes], q_ref, MOLAR_MASS, 0.0, CUTOFF, 0.0,
-                            DNU, n_points)
-                for first in range(0, n_nodes, PER_LAUNCH):
-                    h.run_nodes(first, min(PER_LAUNCH, n_nodes - first))
-                batch[r] = h.get("timing_ms") / n_nodes
+            h = lines.LineOpacity.of(ctx, line, n_points, 1, 1, True)
+            try:
+                for r in range(KERNEL_RUNS + 1):               # the first repeat is the warm-up
+                    for k, (tt, p, q) in enumerate(nodes):
+                        h.set_nodes([tt], [p], [q], q_ref, MOLAR_MASS, 0.0, CUTOFF, 0.0, DNU, n_points)
+                        h.run_nodes(0, 1)
+                        single[r, k] = h.get("timing_ms")
+            finally:
+                h.close()
+            h = lines.LineOpacity.of(ctx, line, n_points, PER_LAUNCH, n_nodes)
+            try:
+                for r in range(KERNEL_RUNS + 1):
+                    h.set_nodes([n[0] for n in nodes], [n[1] for n in nodes], [n[2] for n in nodes], q_ref, MOLAR_MASS, 0.0, CUTOFF,
+                                0.0, DNU, n_points)
+                    for first in range(0, n_nodes, PER_LAUNCH):
+                        h.run_nodes(first, min(PER_LAUNCH, n_nodes - first))
+                    batch[r] = h.get("timing_ms") / n_nodes
+            finally:
+                h.close()
         finally:
-            h.close()
             ctx.close()
         per_repeat = single[1:, :, 1].mean(axis=1)          # ms per node, the 16 nodes averaged, per repeat
         out["k_lines_sum_ms_per_node"] = {"median": float(np.median(per_repeat)), "min": float(per_repeat.min()),
