@@ -948,6 +948,37 @@ static int launch_nodes(hx_rt* rt, const KArgs& a) {
     return 0;
 }
 
+extern "C++" {
+// ---- the look-ups of the batch (tp_lookup.h).  The layers' and the interfaces' levels of every column on the premixed tables'
+// grid, at the temperatures given ([C][L + 1], [C][I]) and the current pressures
+static TPLevels batch_levels(const hx_rt* rt, const double* T_lay, const double* T_int) {
+    TPLevels v{};
+    v.temp[0] = T_lay; v.temp[1] = T_int; v.temp_col[0] = rt->L + 1; v.temp_col[1] = rt->I;
+    v.press[0] = rt->p_lay; v.press[1] = rt->p_int; v.press_col[0] = rt->L; v.press_col[1] = rt->I;
+    v.tgrid = rt->ktemp; v.pgrid = rt->kpress; v.ntemp = rt->d.ntemp; v.npress = rt->d.npress;
+    return v;
+}
+
+// each column's table: member M of its record in the device's TableSet array
+template <const double* TableSet::*M>
+struct SetTable {
+    const TableSet* sets;
+    __device__ const double* of(int col) const { return sets[col].*M; }
+};
+
+// one launch for all columns: `nc` values per level from each column's table, for the layers (out_lay) and the interfaces
+// (out_int) or for one of them (the other null)
+template <class Tab>
+static TPLaunch<Tab> batch_lookup(const hx_rt* rt, Tab tab, double* out_lay, double* out_int, size_t out_col, size_t nc, int npress) {
+    TPLaunch<Tab> q{};
+    q.tab = tab;
+    q.out[0] = out_lay; q.out[1] = out_int; q.out_col = out_col;
+    q.nlev[0] = out_lay ? rt->L : 0; q.nlev[1] = out_int ? rt->I : 0;
+    q.nc = nc; q.npress = npress; q.ncol = rt->C;
+    return q;
+}
+}  // extern "C++"
+
 int hx_rt_refresh(hx_rt* rt) {
     if (!rt) return HX_E_ARG;  // e.g. a call after hx_rt_destroy
     RT_NEED_LOOP(rt);
@@ -981,20 +1012,27 @@ int hx_rt_refresh(hx_rt* rt) {
     if (const char* e = getenv("HELIOS_RT_FUSED_LOOKUP")) fused_lookup = fused_lookup && atoi(e) != 0;
     rt->opac_stale = fused_lookup;
     if (rt->d.nspecies == 0) {
-        k_rt_tp_index<<<dim3(hx_cdiv(I, 64), C), 64, 0, ctx->stream>>>(a, (TPIndex*)rt->tp_lay, (TPIndex*)rt->tp_int);
-        k_rt_scat_interp<<<dim3(hx_cdiv(X, 256), I, C), 256, 0, ctx->stream>>>(a, rt->scat_cross_lay, rt->scat_cross_int);
-        k_rt_mmm_table<<<dim3(hx_cdiv(I, 64), C), 64, 0, ctx->stream>>>(a, rt->mmm_lay, rt->mmm_int);
+        const int np = rt->d.npress;
+        k_rt_tp_index<<<dim3(hx_cdiv(I, 64), C), 64, 0, ctx->stream>>>(TPLocate<true, false>{batch_levels(rt, rt->T_lay, rt->T_int)},
+                                                                      (TPIndex*)rt->tp_lay, (TPIndex*)rt->tp_int, L, I, rt->done);
         HX_LAUNCH_CHECK(ctx);
+        const TPStored stored{{(const TPIndex*)rt->tp_lay, (const TPIndex*)rt->tp_int}, (size_t)I, rt->done};
+        rc = launch_tp_spectral<false, false>(ctx, stored, batch_lookup(rt, SetTable<&TableSet::scat_cross>{rt->coltab}, rt->scat_cross_lay,
+                                                                        rt->scat_cross_int, (size_t)X * I, X, np));
+        if (!rc)
+            rc = launch_tp_scalar(ctx, stored, batch_lookup(rt, SetTable<&TableSet::meanmass>{rt->coltab}, rt->mmm_lay, rt->mmm_int, I, 1, np));
+        if (rc) return rc;
         if (fused_lookup) {
             // opacities are interpolated inside k_rt_coef; remember the temperatures this refresh used, so that
             // the arrays can be rebuilt on demand
             k_rt_keep_ref_T<<<dim3(hx_cdiv(I + 1, 64), C), 64, 0, ctx->stream>>>(a, rt->T_lay_ref, rt->T_int_ref, rt->coltab_ref);
+            HX_LAUNCH_CHECK(ctx);
         } else {
             ProfScope ps(rt, "opac_interpol");
-            const int chunks = (int)std::min<long long>(hx_cdiv((long long)nc, 256), 1024);
-            k_rt_opac_table<<<dim3(chunks, I, C), 256, 0, ctx->stream>>>(a, rt->opac_wg_lay, rt->opac_wg_int);
+            rc = launch_tp_spectral<false, false>(ctx, stored, batch_lookup(rt, SetTable<&TableSet::k>{rt->coltab}, rt->opac_wg_lay,
+                                                                            rt->opac_wg_int, nc * I, nc, np));
+            if (rc) return rc;
         }
-        HX_LAUNCH_CHECK(ctx);
     } else {
         rc = refresh_species(rt);
         if (rc) return rc;
@@ -1181,23 +1219,15 @@ int kappa_cp_from_table(hx_rt* rt, bool refresh_T_int, bool time_stepped_only) {
         k_rt_tint<<<dim3(hx_cdiv(I, 64), rt->C), 64, 0, ctx->stream>>>(rt->T_lay, rt->T_int, L, rt->done);
         HX_LAUNCH_CHECK(ctx);
     }
-    for (int c = 0; c < rt->C; c++) {
-        if (time_stepped_only && rt->cols[c].physical_tstep == 0) continue;
-        const double* T_lay = rt->T_lay + (size_t)c * (L + 1);
-        const double* T_int = rt->T_int + (size_t)c * I;
-        const double* p_lay = rt->p_lay + (size_t)c * L;
-        const double* p_int = rt->p_int + (size_t)c * I;
-        int rc = hx_kappa_interpol(ctx, T_lay, rt->entr_temp, p_lay, rt->entr_press, rt->kappa_lay + (size_t)c * L,
-                                   rt->entr_kappa, rt->entr_npress, rt->entr_ntemp, L);
-        if (rc) return rc;
-        rc = hx_kappa_interpol(ctx, T_int, rt->entr_temp, p_int, rt->entr_press, rt->kappa_int + (size_t)c * I,
-                               rt->entr_kappa, rt->entr_npress, rt->entr_ntemp, I);
-        if (rc) return rc;
-        rc = hx_cp_interpol(ctx, T_lay, rt->entr_temp, p_lay, rt->entr_press, rt->c_p_lay + (size_t)c * L,
-                            rt->entr_c_p, rt->entr_npress, rt->entr_ntemp, L);
-        if (rc) return rc;
-    }
-    return 0;
+    // three launches for the batch, every column finished or not: kappa_lay, kappa_int, c_p_lay (log10 T)
+    TPLevels src = batch_levels(rt, rt->T_lay, rt->T_int);
+    src.tgrid = rt->entr_temp; src.pgrid = rt->entr_press; src.ntemp = rt->entr_ntemp; src.npress = rt->entr_npress;
+    if (time_stepped_only) src.time_stepped = rt->colpar;
+    const int np = rt->entr_npress;
+    int rc = launch_scalar_table(ctx, src, false, batch_lookup(rt, OneTable{rt->entr_kappa}, rt->kappa_lay, nullptr, L, 1, np));
+    if (!rc) rc = launch_scalar_table(ctx, src, false, batch_lookup(rt, OneTable{rt->entr_kappa}, nullptr, rt->kappa_int, I, 1, np));
+    if (!rc) rc = launch_scalar_table(ctx, src, true, batch_lookup(rt, OneTable{rt->entr_c_p}, rt->c_p_lay, nullptr, L, 1, np));
+    return rc;
 }
 
 }  // namespace
@@ -1238,13 +1268,10 @@ int hx_rt_conv_adjust(hx_rt* rt, int itervalue) {
     HX_REQUIRE(ctx, rt->have_grid && rt->have_tables, HX_E_STATE, "hx_rt_conv_adjust before the tables are set");
     if (itervalue % 10 == 0) {   // computation.py:1030-1036: mu of the profile BEFORE the adjustment
         if (rt->d.nspecies == 0) {
-            for (int c = 0; c < rt->C; c++) {
-                int rc = hx_meanmolmass_interpol(ctx, rt->T_lay + (size_t)c * (rt->L + 1), rt->ktemp,
-                                                 rt->mmm_lay + (size_t)c * rt->I, rt->tables[rt->col_table[c]].meanmass,
-                                                 rt->p_lay + (size_t)c * rt->L, rt->kpress, rt->d.npress,
-                                                 rt->d.ntemp, rt->L);
-                if (rc) return rc;
-            }
+            // one launch: the layers of every column, finished or not, in the column's current table set
+            int rc = launch_tp_scalar(ctx, TPLocate<true, false>{batch_levels(rt, rt->T_lay, nullptr)},
+                                      batch_lookup(rt, SetTable<&TableSet::meanmass>{rt->coltab}, rt->mmm_lay, nullptr, rt->I, 1, rt->d.npress));
+            if (rc) return rc;
         } else {
             int rc = upload_species_table(rt);
             if (rc) return rc;
@@ -1497,22 +1524,13 @@ int get_flux_wg(hx_rt* rt, int col, const double* tiles, const double* bc, bool 
 static int materialize_opac(hx_rt* rt) {
     if (!rt->opac_stale) return 0;
     hx_context* ctx = rt->ctx;
-    const size_t nc = (size_t)rt->X * rt->Y, wgI = nc * rt->I, bandI = (size_t)rt->X * rt->I;
-    // the set each column's last refresh read (a set assigned since then is in effect from the NEXT refresh)
-    std::vector<TableSet> used(rt->C);
-    int rc0 = hx_d2h(ctx, used.data(), rt->coltab_ref, used.size() * sizeof(TableSet));
-    if (rc0) return rc0;
-    for (int c = 0; c < rt->C; c++) {
-        const TableSet& t = used[c];
-        int rc = hx_opac_interpol(ctx, rt->T_lay_ref + (size_t)c * (rt->L + 1), rt->ktemp, rt->p_lay + (size_t)c * rt->L,
-                                  rt->kpress, t.k, rt->opac_wg_lay + c * wgI, t.scat_cross,
-                                  rt->scat_cross_lay + c * bandI, rt->d.npress, rt->d.ntemp, rt->Y, rt->X, rt->L);
-        if (rc) return rc;
-        rc = hx_opac_interpol(ctx, rt->T_int_ref + (size_t)c * rt->I, rt->ktemp, rt->p_int + (size_t)c * rt->I,
-                              rt->kpress, t.k, rt->opac_wg_int + c * wgI, t.scat_cross,
-                              rt->scat_cross_int + c * bandI, rt->d.npress, rt->d.ntemp, rt->Y, rt->X, rt->I);
-        if (rc) return rc;
-    }
+    // one launch, every column finished or not: the temperatures and the set each column's last refresh read (a set assigned
+    // since then is in effect from the NEXT refresh), the current pressures.  scat_cross_* are the refresh's own
+    const size_t nc = (size_t)rt->X * rt->Y;
+    int rc = launch_tp_spectral<false, false>(ctx, TPLocate<true, false>{batch_levels(rt, rt->T_lay_ref, rt->T_int_ref)},
+                                              batch_lookup(rt, SetTable<&TableSet::k>{rt->coltab_ref}, rt->opac_wg_lay, rt->opac_wg_int,
+                                                           nc * rt->I, nc, rt->d.npress));
+    if (rc) return rc;
     rt->opac_stale = false;
     return 0;
 }

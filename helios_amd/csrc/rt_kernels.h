@@ -1014,65 +1014,14 @@ __global__ void __launch_bounds__(256) k_rt_fdir_band(const double* __restrict__
     }
 }
 
-// fractional (T, log10 P) table indices of every layer and interface of every column
-__global__ void k_rt_tp_index(KArgs a, TPIndex* tp_lay, TPIndex* tp_int) {
-    const int col = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.I || a.done[col]) return;
-    const double* T = a.T_lay + (size_t)col * (a.L + 1);
-    tp_int[(size_t)col * a.I + i] = locate_tp(interface_T(T, i, a.L), a.p_int[(size_t)col * a.I + i], a.ktemp,
-                                              a.ntemp, a.kpress, a.npress, true, false);
-    if (i < a.L)
-        tp_lay[(size_t)col * a.I + i] = locate_tp(T[i], a.p_lay[(size_t)col * a.L + i], a.ktemp, a.ntemp, a.kpress,
-                                                  a.npress, true, false);
-}
-
-// Rayleigh cross-sections of the premixed table at every level (the [x + X*level] half of opac_interpol)
-__global__ void __launch_bounds__(256) k_rt_scat_interp(KArgs a, double* scat_lay, double* scat_int) {
-    const int col = blockIdx.z, lev = blockIdx.y;
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    if (x >= a.X || a.done[col]) return;
-    const size_t cp = a.X, ct = (size_t)a.X * a.npress, bandI = (size_t)a.X * a.I;
-    const double* crosstable = a.coltab[col].scat_cross;   // this column's table set
-    for (int pass = 0; pass < 2; pass++) {
-        if (pass == 0 && lev >= a.L) continue;
-        const TPIndex k = (pass == 0 ? a.tp_lay : a.tp_int)[(size_t)col * a.I + lev];
-        const double* t0 = crosstable + x + ct * k.tdown;
-        const double* t1 = crosstable + x + ct * k.tup;
-        (pass == 0 ? scat_lay : scat_int)[col * bandI + x + (size_t)a.X * lev] =
-            blend_tp(t0[cp * k.pdown], t0[cp * k.pup], t1[cp * k.pdown], t1[cp * k.pup], k, false);
-    }
-}
-
 // ---- per refresh, all columns at once (a column whose loop has ended is skipped on the device) -------------------
-// mean molecular mass of a premixed table at every level (meanmolmass_interpol, kernels.cu:649-699) from the table
-// indices k_rt_tp_index left behind, in the table of the column's own set
-__global__ void k_rt_mmm_table(KArgs a, double* mmm_lay, double* mmm_int) {
+// fractional (T, log10 P) table indices of every layer and interface of every column (src: layer temperatures and the
+// interface temperatures k_rt_nodes has just written), for the look-up launches of the refresh (tp_lookup.h) and k_rt_coef
+__global__ void k_rt_tp_index(TPLocate<true, false> src, TPIndex* tp_lay, TPIndex* tp_int, int L, int I, const int* done) {
     const int col = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.I || a.done[col]) return;
-    const double* __restrict__ table = a.coltab[col].meanmass;
-    for (int pass = 0; pass < 2; pass++) {
-        if (pass == 0 && i >= a.L) continue;
-        const TPIndex k = (pass == 0 ? a.tp_lay : a.tp_int)[(size_t)col * a.I + i];
-        (pass == 0 ? mmm_lay : mmm_int)[(size_t)col * a.I + i] =
-            blend_tp(table[k.pdown + a.npress * k.tdown], table[k.pup + a.npress * k.tdown],
-                     table[k.pdown + a.npress * k.tup], table[k.pup + a.npress * k.tup], k, false);
-    }
-}
-
-// premixed k-table look-up into opac_wg_lay / opac_wg_int (opac_interpol, kernels.cu:524-610); grid (chunks, I, C)
-__global__ void __launch_bounds__(256) k_rt_opac_table(KArgs a, double* opac_lay, double* opac_int) {
-    const int col = blockIdx.z, lev = blockIdx.y;
-    if (a.done[col]) return;
-    const size_t nc = (size_t)a.Y * a.X, sp = nc, st = nc * a.npress, wgI = nc * a.I;
-    const double* ktable = a.coltab[col].k;   // this column's table set
-    for (int pass = 0; pass < 2; pass++) {
-        if (pass == 0 && lev >= a.L) continue;
-        const TPIndex k = (pass == 0 ? a.tp_lay : a.tp_int)[(size_t)col * a.I + lev];
-        double* out = (pass == 0 ? opac_lay : opac_int) + col * wgI + nc * lev;
-        for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < nc; c += (size_t)gridDim.x * blockDim.x)
-            out[c] = blend_tp(ktable[c + sp * k.pdown + st * k.tdown], ktable[c + sp * k.pup + st * k.tdown],
-                              ktable[c + sp * k.pdown + st * k.tup], ktable[c + sp * k.pup + st * k.tup], k, false);
-    }
+    if (i >= I || done[col]) return;
+    tp_int[(size_t)col * I + i] = src.at(col, 1, i);
+    if (i < L) tp_lay[(size_t)col * I + i] = src.at(col, 0, i);
 }
 
 // layer heights (calc_delta_z, kernels.cu:1247-1261)

@@ -83,6 +83,24 @@ constexpr int MIX_MAX_ABSORBERS = 48;  // LDS images of the species list: 1 KB n
 int launch_mix_species(hx_context* ctx, MixArgs m, const int* abs_list, int nabs_all, bool any_ro);
 
 #ifndef HX_SPECIES_DECLARATIONS_ONLY  // (premix.hip: the structures and vmr_from_table, not a second copy of the kernels)
+// Level i of a column at (T, P): the mixing ratios of the species that come with a (T, P) table follow the temperatures, on
+// the device (calculate_vmr_for_all_species, host_functions.py:874-901; `vmr` is the column's [S][I] block), then the mean
+// molecular mass of the level (host_functions.py:927-959), which is returned
+__device__ __forceinline__ double level_vmr_and_mmm(const SpeciesDev* __restrict__ sp, int S, double* vmr, int I, int i, int col,
+                                                    double T, double P, const double* ktemp, int ntemp, const double* kpress,
+                                                    int npress) {
+    for (int s = 0; s < S; s++)
+        if (sp[s].vmr_tab)
+            vmr[(size_t)s * I + i] = vmr_from_table(sp[s].vmr_tab + (size_t)col * ntemp * npress, T, P, ktemp, ntemp, kpress, npress);
+    double num = 0.0, tot = 0.0;
+    for (int s = 0; s < S; s++)
+        if (sp[s].in_mu) {
+            num += vmr[(size_t)s * I + i] * sp[s].weight;
+            tot += vmr[(size_t)s * I + i];
+        }
+    return num / tot * HX_AMU;
+}
+
 __global__ void k_rt_species_prep(MixArgs a) {
     const int col = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.I || a.done[col]) return;
@@ -92,19 +110,7 @@ __global__ void k_rt_species_prep(MixArgs a) {
         double* vmr = const_cast<double*>(lay ? a.vmr_lay : a.vmr_int) + (size_t)col * a.S * a.I;
         const double T = lay ? a.T_lay[(size_t)col * (a.L + 1) + i] : a.T_int[(size_t)col * a.I + i];
         const double P = lay ? a.p_lay[(size_t)col * a.L + i] : a.p_int[(size_t)col * a.I + i];
-        // calculate_vmr_for_all_species (host_functions.py:874-901) for the species that come with a (T, P) table: the
-        // profile follows the temperatures of this refresh, on the device
-        for (int s = 0; s < a.S; s++)
-            if (a.sp[s].vmr_tab)
-                vmr[(size_t)s * a.I + i] = vmr_from_table(a.sp[s].vmr_tab + (size_t)col * a.ntemp * a.npress, T, P, a.ktemp, a.ntemp,
-                                                          a.kpress, a.npress);
-        double num = 0.0, tot = 0.0;  // host_functions.py:927-959
-        for (int s = 0; s < a.S; s++)
-            if (a.sp[s].in_mu) {
-                num += vmr[(size_t)s * a.I + i] * a.sp[s].weight;
-                tot += vmr[(size_t)s * a.I + i];
-            }
-        const double mmm = num / tot * HX_AMU;
+        const double mmm = level_vmr_and_mmm(a.sp, a.S, vmr, a.I, i, col, T, P, a.ktemp, a.ntemp, a.kpress, a.npress);
         (lay ? a.mmm_lay : a.mmm_int)[(size_t)col * a.I + i] = mmm;
         (lay ? a.tp_lay : a.tp_int)[(size_t)col * a.I + i] = locate_tp(T, P, a.ktemp, a.ntemp, a.kpress, a.npress, false, false);
         double* fac = (lay ? a.fac_lay : a.fac_int) + ((size_t)col * a.I + i) * a.S;
@@ -115,26 +121,16 @@ __global__ void k_rt_species_prep(MixArgs a) {
     }
 }
 
-// mean molecular mass of the layers only (the convection loop refreshes it ahead of the adjustment, computation.py:1030-1036)
-// (the mixing ratios of tabulated species are brought up to the present layer temperatures first, :1035)
+// mean molecular mass of the layers only (the convection loop refreshes it ahead of the adjustment, computation.py:1030-1036),
+// of finished columns too (the mixing ratios of tabulated species are brought up to the present layer temperatures first, :1035)
 __global__ void k_rt_mmm_from_vmr(const SpeciesDev* __restrict__ sp, int S, double* __restrict__ vmr_lay,
                                   double* __restrict__ mmm_lay, int L, int I, const double* __restrict__ T_lay,
                                   const double* __restrict__ p_lay, const double* __restrict__ ktemp, int ntemp,
                                   const double* __restrict__ kpress, int npress) {
     const int col = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= L) return;
-    double* vmr = vmr_lay + (size_t)col * S * I;
-    for (int s = 0; s < S; s++)
-        if (sp[s].vmr_tab)
-            vmr[(size_t)s * I + i] = vmr_from_table(sp[s].vmr_tab + (size_t)col * ntemp * npress, T_lay[(size_t)col * (L + 1) + i],
-                                                    p_lay[(size_t)col * L + i], ktemp, ntemp, kpress, npress);
-    double num = 0.0, tot = 0.0;
-    for (int s = 0; s < S; s++)
-        if (sp[s].in_mu) {
-            num += vmr[(size_t)s * I + i] * sp[s].weight;
-            tot += vmr[(size_t)s * I + i];
-        }
-    mmm_lay[(size_t)col * I + i] = num / tot * HX_AMU;
+    mmm_lay[(size_t)col * I + i] = level_vmr_and_mmm(sp, S, vmr_lay + (size_t)col * S * I, I, i, col, T_lay[(size_t)col * (L + 1) + i],
+                                                     p_lay[(size_t)col * L + i], ktemp, ntemp, kpress, npress);
 }
 
 // ro::mix keeps this kernel within 7.9 KB of LDS and 96 VGPRs: five wavefronts per SIMD (tests/test_abi.py)

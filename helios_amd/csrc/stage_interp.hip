@@ -235,48 +235,39 @@ k_planck_interpol(const double* __restrict__ temp, double* __restrict__ out,
     }
 }
 
-// k-table look-up (premixed: kernels.cu:524-610, per species: :3209-3259).  One thread per
-// (c = y + ny*x, level): the four table corners and the output are contiguous in c.
-template <bool SPECIES>
-__global__ void __launch_bounds__(256)
-k_opac_interpol(const double* __restrict__ temp, const double* __restrict__ opactemp,
-                const double* __restrict__ press, const double* __restrict__ opacpress,
-                const double* __restrict__ ktable, double* __restrict__ opac,
-                const double* __restrict__ crosstable, double* __restrict__ scat_cross, int npress,
-                int ntemp, int ny, int nbin, int nlev) {
-    const int i = blockIdx.y;
-    const size_t nc = (size_t)ny * nbin;
-    const TPIndex k = locate_tp(temp[i], press[i], opactemp, ntemp, opacpress, npress, !SPECIES, false);
-    const size_t sp = nc, st = nc * npress;
-    for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < nc;
-         c += (size_t)gridDim.x * blockDim.x) {
-        opac[c + nc * i] =
-            blend_tp(ktable[c + sp * k.pdown + st * k.tdown], ktable[c + sp * k.pup + st * k.tdown],
-                     ktable[c + sp * k.pdown + st * k.tup], ktable[c + sp * k.pup + st * k.tup], k,
-                     SPECIES);
-        if (!SPECIES && c < (size_t)nbin) {
-            const size_t x = c, cp = nbin, ct = (size_t)nbin * npress;
-            scat_cross[x + (size_t)nbin * i] = blend_tp(
-                crosstable[x + cp * k.pdown + ct * k.tdown], crosstable[x + cp * k.pup + ct * k.tdown],
-                crosstable[x + cp * k.pdown + ct * k.tup], crosstable[x + cp * k.pup + ct * k.tup], k,
-                false);
-        }
-    }
+// a stage call: one column, one level set of n levels
+TPLevels stage_levels(const double* temp, const double* tgrid, int ntemp, const double* press, const double* pgrid, int npress) {
+    TPLevels v{};
+    v.temp[0] = temp;
+    v.press[0] = press;
+    v.tgrid = tgrid;
+    v.pgrid = pgrid;
+    v.ntemp = ntemp;
+    v.npress = npress;
+    return v;
 }
 
-// scalar tables (mean molecular mass :649, kappa :703, c_p :761)
-__global__ void k_scalar_table(const double* __restrict__ temp, const double* __restrict__ tgrid,
-                               const double* __restrict__ press, const double* __restrict__ pgrid,
-                               double* __restrict__ out, const double* __restrict__ table, int npress,
-                               int ntemp, int nlev, int log_t) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nlev) return;
-    const TPIndex k = locate_tp(temp[i], press[i], tgrid, ntemp, pgrid, npress, true, log_t != 0);
-    out[i] = blend_tp(table[k.pdown + npress * k.tdown], table[k.pup + npress * k.tdown],
-                      table[k.pdown + npress * k.tup], table[k.pup + npress * k.tup], k, false);
+TPLaunch<OneTable> stage_launch(const double* table, double* out, size_t nc, int npress, int n) {
+    TPLaunch<OneTable> q{};
+    q.tab.t = table;
+    q.out[0] = out;
+    q.nc = nc;
+    q.npress = npress;
+    q.nlev[0] = n;
+    q.ncol = 1;
+    return q;
+}
+
+int stage_scalar(hx_context* ctx, const double* temp, const double* tgrid, const double* press, const double* pgrid, double* out,
+                 const double* table, int npress, int ntemp, int n, bool log_t) {
+    return launch_scalar_table(ctx, stage_levels(temp, tgrid, ntemp, press, pgrid, npress), log_t, stage_launch(table, out, 1, npress, n));
 }
 
 }  // namespace
+
+int hx::launch_scalar_table(hx_context* ctx, const TPLevels& levels, bool log_t, const TPLaunch<OneTable>& q) {
+    return log_t ? launch_tp_scalar(ctx, TPLocate<true, true>{levels}, q) : launch_tp_scalar(ctx, TPLocate<true, false>{levels}, q);
+}
 
 extern "C" {
 
@@ -358,71 +349,50 @@ int hx_opac_interpol(hx_context* ctx, const double* temp, const double* opactemp
                      const double* press, const double* opacpress, const double* ktable,
                      double* opac, const double* crosstable, double* scat_cross, int npress,
                      int ntemp, int ny, int nbin, int nlay_or_nint) {
-    const long long nc = (long long)ny * nbin;
-    dim3 grid((unsigned)min((long long)hx_cdiv(nc, 256), 4096LL), nlay_or_nint);
-    k_opac_interpol<false><<<grid, 256, 0, ctx->stream>>>(temp, opactemp, press, opacpress, ktable,
-                                                         opac, crosstable, scat_cross, npress, ntemp,
-                                                         ny, nbin, nlay_or_nint);
-    HX_LAUNCH_CHECK(ctx);
-    return 0;
+    TPSecond x{};
+    x.tab = crosstable;
+    x.out[0] = scat_cross;
+    x.nx = nbin;
+    return launch_tp_spectral<false, true>(ctx, TPLocate<true, false>{stage_levels(temp, opactemp, ntemp, press, opacpress, npress)},
+                                           stage_launch(ktable, opac, (size_t)ny * nbin, npress, nlay_or_nint), x);
 }
 
 int hx_opac_species_interpol(hx_context* ctx, const double* temp, const double* opactemp,
                              const double* press, const double* opacpress,
                              const double* opac_opacity_pretab, double* opac_spec_wg, int npress,
                              int ntemp, int ny, int nbin, int nlay_or_nint) {
-    const long long nc = (long long)ny * nbin;
-    dim3 grid((unsigned)min((long long)hx_cdiv(nc, 256), 4096LL), nlay_or_nint);
-    k_opac_interpol<true><<<grid, 256, 0, ctx->stream>>>(temp, opactemp, press, opacpress,
-                                                        opac_opacity_pretab, opac_spec_wg, nullptr,
-                                                        nullptr, npress, ntemp, ny, nbin, nlay_or_nint);
-    HX_LAUNCH_CHECK(ctx);
-    return 0;
+    return launch_tp_spectral<true, false>(ctx, TPLocate<false, false>{stage_levels(temp, opactemp, ntemp, press, opacpress, npress)},
+                                           stage_launch(opac_opacity_pretab, opac_spec_wg, (size_t)ny * nbin, npress, nlay_or_nint));
 }
 
 int hx_meanmolmass_interpol(hx_context* ctx, const double* temp, const double* opactemp,
                             double* meanmolmass, const double* opac_meanmass, const double* press,
                             const double* opacpress, int npress, int ntemp, int ninterface) {
-    k_scalar_table<<<hx_cdiv(ninterface, 64), 64, 0, ctx->stream>>>(
-        temp, opactemp, press, opacpress, meanmolmass, opac_meanmass, npress, ntemp, ninterface, 0);
-    HX_LAUNCH_CHECK(ctx);
-    return 0;
+    return stage_scalar(ctx, temp, opactemp, press, opacpress, meanmolmass, opac_meanmass, npress, ntemp, ninterface, false);
 }
 
 int hx_kappa_interpol(hx_context* ctx, const double* temp, const double* entr_temp,
                       const double* press, const double* entr_press, double* kappa,
                       const double* entr_kappa, int entr_npress, int entr_ntemp, int nlay_or_nint) {
-    k_scalar_table<<<hx_cdiv(nlay_or_nint, 64), 64, 0, ctx->stream>>>(
-        temp, entr_temp, press, entr_press, kappa, entr_kappa, entr_npress, entr_ntemp, nlay_or_nint, 0);
-    HX_LAUNCH_CHECK(ctx);
-    return 0;
+    return stage_scalar(ctx, temp, entr_temp, press, entr_press, kappa, entr_kappa, entr_npress, entr_ntemp, nlay_or_nint, false);
 }
 
 int hx_cp_interpol(hx_context* ctx, const double* temp, const double* entr_temp,
                    const double* press, const double* entr_press, double* cp_lay,
                    const double* entr_cp, int entr_npress, int entr_ntemp, int nlayer) {
-    k_scalar_table<<<hx_cdiv(nlayer, 64), 64, 0, ctx->stream>>>(
-        temp, entr_temp, press, entr_press, cp_lay, entr_cp, entr_npress, entr_ntemp, nlayer, 1);
-    HX_LAUNCH_CHECK(ctx);
-    return 0;
+    return stage_scalar(ctx, temp, entr_temp, press, entr_press, cp_lay, entr_cp, entr_npress, entr_ntemp, nlayer, true);
 }
 
 int hx_entropy_interpol(hx_context* ctx, const double* temp, const double* entr_temp,
                         const double* press, const double* entr_press, double* entropy,
                         const double* entr_entropy, int entr_npress, int entr_ntemp, int nlayer) {
-    k_scalar_table<<<hx_cdiv(nlayer, 64), 64, 0, ctx->stream>>>(
-        temp, entr_temp, press, entr_press, entropy, entr_entropy, entr_npress, entr_ntemp, nlayer, 1);
-    HX_LAUNCH_CHECK(ctx);
-    return 0;
+    return stage_scalar(ctx, temp, entr_temp, press, entr_press, entropy, entr_entropy, entr_npress, entr_ntemp, nlayer, true);
 }
 
 int hx_phase_number_interpol(hx_context* ctx, const double* temp, const double* entr_temp,
                              const double* press, const double* entr_press, double* state,
                              const double* entr_state, int entr_npress, int entr_ntemp, int nlayer) {
-    k_scalar_table<<<hx_cdiv(nlayer, 64), 64, 0, ctx->stream>>>(
-        temp, entr_temp, press, entr_press, state, entr_state, entr_npress, entr_ntemp, nlayer, 0);
-    HX_LAUNCH_CHECK(ctx);
-    return 0;
+    return stage_scalar(ctx, temp, entr_temp, press, entr_press, state, entr_state, entr_npress, entr_ntemp, nlayer, false);
 }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 // source/kernels.cu:109-290).  Shared by the per-stage kernels and the fused path.
 #pragma once
 #include "hx_common.h"
+#include "tp_lookup.h"
 
 namespace hx {
 
@@ -88,56 +89,6 @@ __device__ __forceinline__ double single_scat_albedo(double scat, double absorb,
 }
 
 __device__ __forceinline__ double tiny_abs(double F) { return fabs(F) < 1e-100 ? fabs(F) : F; }
-
-// fractional table index on a uniform (T, log10 P) grid; margin 0.001 (premixed, :545-559) or 0
-// (per-species tables, :3228-3241)
-struct TPIndex {
-    double t, p;
-    int tdown, tup, pdown, pup;
-};
-
-__device__ __forceinline__ TPIndex locate_tp(double temp, double press, const double* tgrid,
-                                             int ntemp, const double* pgrid, int npress,
-                                             bool margin, bool log_t) {
-    TPIndex k;
-    double t;
-    if (log_t) {
-        const double dt = (log10(tgrid[ntemp - 1]) - log10(tgrid[0])) / (ntemp - 1.0);
-        t = (log10(temp) - log10(tgrid[0])) / dt;
-    } else {
-        const double dt = (tgrid[ntemp - 1] - tgrid[0]) / (ntemp - 1.0);
-        t = (temp - tgrid[0]) / dt;
-    }
-    const double dp = (log10(pgrid[npress - 1]) - log10(pgrid[0])) / (npress - 1.0);
-    double p = (log10(press) - log10(pgrid[0])) / dp;
-    if (margin) {
-        t = dmin(ntemp - 1.001, dmax(0.001, t));
-        p = dmin(npress - 1.001, dmax(0.001, p));
-    } else {
-        t = dmin(ntemp - 1.0, dmax(0.0, t));
-        p = dmin(npress - 1.0, dmax(0.0, p));
-    }
-    k.t = t;
-    k.p = p;
-    k.tdown = (int)floor(t);
-    k.tup = (int)ceil(t);
-    k.pdown = (int)floor(p);
-    k.pup = (int)ceil(p);
-    return k;
-}
-
-// four-case bilinear blend (:561-608); `species` selects the term order of :637-640
-__device__ __forceinline__ double blend_tp(double dd, double ud, double du, double uu,
-                                           const TPIndex& k, bool species) {
-    if (k.pdown != k.pup && k.tdown != k.tup)
-        return dd * (k.pup - k.p) * (k.tup - k.t) + ud * (k.p - k.pdown) * (k.tup - k.t) +
-               du * (k.pup - k.p) * (k.t - k.tdown) + uu * (k.p - k.pdown) * (k.t - k.tdown);
-    if (k.tdown == k.tup && k.pdown != k.pup) return dd * (k.pup - k.p) + ud * (k.p - k.pdown);
-    if (k.pdown == k.pup && k.tdown != k.tup)
-        return species ? du * (k.t - k.tdown) + dd * (k.tup - k.t)
-                       : dd * (k.tup - k.t) + du * (k.t - k.tdown);
-    return dd;
-}
 
 // Planck-table look-up (:956-974): rows at T = 1 + step*r, clamp to [0.001, dim-1.001]
 __device__ __forceinline__ double planck_lookup(const double* planck_grid, double T, int x,

@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE: crafted tables and columns that put the levels of the (T, log10 P) table look-up on its edges.  No GPU
 here: tests/test_lookup_cases.py proves on the restatement (tests/lookup_reference.py) and the CPU oracle that every case takes
-the branches it is named for, tests/test_gpu_lookup_edges.py runs the same cases through the five copies of the look-up.
+the branches it is named for, tests/test_gpu_lookup_edges.py runs the same cases through the three copies of the look-up.
 
 The grid.  Nodes that fp64 holds exactly: ktemp = 100 + 250 i (i = 0 ... 6: dt = 250 exactly, so t is exact wherever T - 100 is
 a multiple of 250 / 2^n), kpress = 10^(2 j) (j = 0 ... 5).
@@ -193,6 +193,34 @@ def species_ladder():
         c.name = "species_ladder"
         _kept["species"] = c
     return _kept["species"].copy()
+
+
+COLUMN_LAYERS = (2, 65)                 # the column batch: the shortest column, and one level past a 64-thread block
+ENTR_TEMP, ENTR_PRESS = np.linspace(100.0, 4000.0, 8), np.logspace(0, 11, 7)
+
+
+def column_batch(L):
+    """three columns whose per-column inputs all differ: temperatures (one walk pattern each), the premixed table set
+    (c.second_set = (k, Rayleigh, mean mass) from another seed, read by column 1 alone: c.col_set) and the time step (column 1
+    has physical_tstep == 0: c.columns); a kappa / c_p table on a grid of its own (c.entr_*)"""
+    key = ("columns", L)
+    if key not in _kept:
+        c = _frame(L, 0)
+        nodes = 10.0 ** (9.9 - 9.6 * np.arange(2 * L + 1) / (2.0 * L))
+        _set_pressures(c, nodes[1::2], nodes[0::2])
+        c.T_cols = np.array([walk_temperatures(p, L) for p in ("zigzag", "node_above", "on_node")])
+        c.T_lay = c.T_cols[0].copy()
+        other = _frame(L, 0, seed=SEED + 7)
+        c.second_set = (other.opac_k, other.opac_scat_cross, other.opac_meanmass)
+        c.col_set = (0, 1, 0)
+        c.columns = [dict(physical_tstep=2e-3), dict(physical_tstep=0.0), dict(physical_tstep=1e-3)]
+        tt, pp = np.meshgrid(ENTR_TEMP, ENTR_PRESS, indexing="ij")
+        c.entr_temp, c.entr_press = ENTR_TEMP.copy(), ENTR_PRESS.copy()
+        c.entr_kappa = (0.2 + 0.1 * tt / 4000.0 + 0.005 * np.log10(pp)).reshape(-1)
+        c.entr_c_p = (3.5 * pc.R_UNIV * (1.0 + 0.5 * tt / 4000.0 + 0.005 * np.log10(pp))).reshape(-1)
+        c.name, c.env = "columns_L%d" % L, {}
+        _kept[key] = c
+    return _kept[key].copy()
 
 
 _first_p = LADDER_P_LAY.index(1.0)

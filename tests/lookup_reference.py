@@ -28,13 +28,19 @@ def log10_libm(v):
     return np.array([math.log10(x) for x in np.asarray(v, np.float64).reshape(-1)])
 
 
-def locate(temp, press, ktemp, kpress, margin=True, log10p=None):
-    """locate_tp at arrays of levels, in fp64: dict of t, p (fp64) and tdown, tup, pdown, pup (int64)"""
+def locate(temp, press, ktemp, kpress, margin=True, log10p=None, log_t=False):
+    """locate_tp at arrays of levels, in fp64: dict of t, p (fp64) and tdown, tup, pdown, pup (int64); `log_t`: the temperature
+    axis in log10 T too (the c_p and entropy tables)"""
     temp = np.asarray(temp, np.float64).reshape(-1)
     ktemp, kpress = np.asarray(ktemp, np.float64), np.asarray(kpress, np.float64)
     nt, npr = len(ktemp), len(kpress)
-    dt = (ktemp[nt - 1] - ktemp[0]) / (nt - 1.0)
-    t = (temp - ktemp[0]) / dt
+    if log_t:
+        lt = log10_libm(ktemp)
+        dt = (lt[nt - 1] - lt[0]) / (nt - 1.0)
+        t = (log10_libm(temp) - lt[0]) / dt
+    else:
+        dt = (ktemp[nt - 1] - ktemp[0]) / (nt - 1.0)
+        t = (temp - ktemp[0]) / dt
     lp = log10_libm(press) if log10p is None else np.asarray(log10p, np.float64).reshape(-1)
     lk = log10_libm(kpress)
     dp = (lk[npr - 1] - lk[0]) / (npr - 1.0)
@@ -75,9 +81,9 @@ def corners(table, k):
     return (table[k["tdown"], k["pdown"]], table[k["tdown"], k["pup"]], table[k["tup"], k["pdown"]], table[k["tup"], k["pup"]])
 
 
-def look_up(fmt, table, temp, press, ktemp, kpress, margin=True, species=False, log10p=None):
+def look_up(fmt, table, temp, press, ktemp, kpress, margin=True, species=False, log10p=None, log_t=False):
     """a table shaped [t][p][...] at arrays of levels: [level][...] in `fmt`"""
-    k = locate(temp, press, ktemp, kpress, margin, log10p)
+    k = locate(temp, press, ktemp, kpress, margin, log10p, log_t)
     return blend(*corners(np.asarray(table, np.float64), k), k, fmt, species)
 
 

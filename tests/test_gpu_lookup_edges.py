@@ -1,11 +1,12 @@
-"""The five copies of the bilinear (T, log10 P) table look-up on the crafted tables and columns of tests/lookup_cases.py, held
-to the long-double restatement of tests/lookup_reference.py:
+"""The three copies of the bilinear (T, log10 P) table look-up on the crafted tables and columns of tests/lookup_cases.py, held
+to the long-double restatement of tests/lookup_reference.py.  One copy is k_tp_spectral / k_tp_scalar (tp_lookup.h, through
+its gather_tp); the cases take it by three routes, A, B and D.  C and E are the other two copies:
 
-  A  k_opac_interpol, k_scalar_table (stage_interp.hip): the stage API, and what rebuilds opac_wg_* on the fused-look-up path
-  B  k_rt_tp_index + k_rt_opac_table: batches with HELIOS_RT_FUSED_LOOKUP=0
+  A  the stage API (one column, indices computed from T and P), and what rebuilds opac_wg_* on the fused-look-up path
+  B  k_rt_tp_index + k_tp_spectral on the stored indices: batches with HELIOS_RT_FUSED_LOOKUP=0
   C  the look-up fused into the coefficient kernels (rt_coef_kernel.inc), whose opacities never reach memory: its planes are
      held to B's planes byte for byte -- both apply the same blend_tp to the same TPIndex without contraction
-  D  k_rt_scat_interp, k_rt_mmm_table: Rayleigh cross-sections and mean molecular mass from the indices B leaves
+  D  k_tp_spectral on the Rayleigh table, k_tp_scalar on the mean-mass table: from the indices B leaves
   E  k_rt_species_prep + the blend written out in rt_mix_species_kernel.inc: on-the-fly mixing
 
 The tolerance is lines_cases.check_rule, unchanged: max(1e-13, 8 eps) relative, eps the fp64 twin's own deviation.  The device's
@@ -230,7 +231,7 @@ def test_fused_lookup_equals_the_unfused_batch_byte_for_byte(ctx, name):
     ref = _run(ctx, name, UNFUSED)
     run = _run(ctx, name)
     assert run["tiling"] == ref["tiling"] and run["bytes"] == 8
-    _hold(c, name, run, "D", "", ("scat_cross", "meanmolmass"))    # before the rebuild: k_rt_scat_interp's, k_rt_mmm_table's own
+    _hold(c, name, run, "D", "", ("scat_cross", "meanmolmass"))    # before the rebuild: the refresh's own (route D)
     _hold(c, name, run, "A", "_after", ("opac_wg", "scat_cross"))
     for key in ref:
         if key not in ("tiling", "bytes"):

@@ -19,7 +19,7 @@ BASE = ["-parameter_file", "/nonexistent", "-opacity_mixing", "premixed", "-numb
 T_INTERN = ("100", "700")
 VARIANTS = {
     "fused_lookup": ["-convective_adjustment", "no"],                      # no beam: the look-up inside k_rt_coef
-    "direct_beam": ["-convective_adjustment", "no", "-direct_irradiation_beam", "yes"],   # k_rt_opac_table, k_rt_dtau_halves
+    "direct_beam": ["-convective_adjustment", "no", "-direct_irradiation_beam", "yes"],   # k_tp_spectral on the stored indices, k_rt_dtau_halves
     "isothermal": ["-convective_adjustment", "no", "-isothermal_layers", "yes"],
     "matrix": ["-convective_adjustment", "no", "-flux_calculation_method", "matrix", "-surface_albedo", "0.1"],
     "single": ["-convective_adjustment", "no", "-precision", "single"],    # fp32 planes in the sweep and in the single runs
@@ -147,7 +147,7 @@ def _three_table_batch(ctx, ncol=6):
 def test_first_refresh_looks_every_column_up_in_its_own_table(ctx, port, monkeypatch, fused_lookup):
     """opacities, Rayleigh cross-sections and mean molecular mass of every column of a three-table batch after the first
     refresh against the CPU oracle's opac_interpol / meanmolmass_interpol in THAT column's table: with the look-up fused
-    into k_rt_coef (the arrays are rebuilt on demand for hx_rt_get) and with HELIOS_RT_FUSED_LOOKUP=0 (k_rt_opac_table)"""
+    into k_rt_coef (the arrays are rebuilt on demand for hx_rt_get) and with HELIOS_RT_FUSED_LOOKUP=0 (k_tp_spectral on the stored indices)"""
     if fused_lookup:
         monkeypatch.delenv("HELIOS_RT_FUSED_LOOKUP", raising=False)
     else:
