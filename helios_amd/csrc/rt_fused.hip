@@ -1598,6 +1598,8 @@ extern "C++" std::vector<hx_column_array> rt_arrays(hx_rt* rt, HostValues& host)
         // [ndecks][3][nbin] of the column's last hx_rt_set_column_cloud_decks
         dev("cloud_deck_spectra", rt->cloud_spec, deck, deck, G, no_decks),
         dev("g_0_tot_lay", rt->g0_tot_lay, XI, X * L, G), dev("g_0_tot_int", rt->g0_tot_int, XI, XI, G),
+        // the surface-emission factor (1 - w0) / (E - w0) of the bottom half-layer per spectral point [y + ny x] (k_rt_coef)
+        dev("boa_source_factor", rt->boaK, X * Y, X * Y, G),
         dev("iters_done", rt->iters_done, 1, 1, G), dev("done", rt->done, 1, 1, GS), dev("dampara", rt->dampara, 1, 1, HX_SET),
         dev("conv_layer", rt->conv_layer, L + 1, L + 1, GS), dev("conv_unstable", rt->conv_unstable, L + 1, L + 1, GS),
         dev("marked_red", rt->marked_red, L + 1, L + 1, G), dev("F_smooth_sum", rt->F_smooth_sum, L, L, G),

@@ -262,7 +262,7 @@ class RTBatch(object):
             "scat_cross_lay": (X * L, np.float64), "scat_cross_int": (X * I, np.float64),
             "meanmolmass_lay": (L, np.float64), "meanmolmass_int": (I, np.float64),
             "g_0_tot_lay": (X * L, np.float64), "g_0_tot_int": (X * I, np.float64),
-            "delta_z_lay": (L, np.float64), "z_lay": (L, np.float64),
+            "delta_z_lay": (L, np.float64), "z_lay": (L, np.float64), "boa_source_factor": (Y * X, np.float64),
             "F_up_wg": (wg, np.float64), "F_down_wg": (wg, np.float64), "Fc_up_wg": (wg, np.float64),
             "Fc_down_wg": (wg, np.float64), "F_dir_wg": (wg, np.float64), "Fc_dir_wg": (wg, np.float64),
             "iters_done": (1, np.int32), "done": (1, np.int32), "premixed_table": (1, np.int32), "premixed_table_count": (1, np.int32), "flux_launch_policy": (2, np.float64), "graph_replays": (3, np.float64), "graph_builds": (2, np.float64),

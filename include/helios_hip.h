@@ -505,7 +505,9 @@ int hx_rt_converged_layers(hx_rt* rt, int* out_counts);
  * "opac_wg_lay","opac_wg_int","scat_cross_lay","scat_cross_int","meanmolmass_lay",
  * "meanmolmass_int","F_up_wg","F_down_wg","Fc_up_wg","Fc_down_wg","F_dir_wg","Fc_dir_wg","abort",
  * "delta_z_lay","z_lay","g_0_tot_lay","g_0_tot_int","delta_t_prefactor","T_store","F_smooth_sum",
- * "conv_layer","conv_unstable","marked_red" (int32[nlayer+1]),"done","iters_done"; host-side, any column (-1):
+ * "conv_layer","conv_unstable","marked_red" (int32[nlayer+1]),"done","iters_done","boa_source_factor" (the surface-emission
+ * factor (1 - w0) / (E - w0) of the bottom half-layer per spectral point, [y + ny x], as the last refresh left it);
+ * host-side, any column (-1):
  * "totals_chunks" (int32, the number of bin chunks the wavelength totals are summed in).
  * `out` is a HOST buffer of `out_bytes`; returns HX_E_ARG if the name is unknown or the size wrong. */
 int hx_rt_get(hx_rt* rt, int col, const char* name, void* out, size_t out_bytes);

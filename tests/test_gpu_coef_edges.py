@@ -19,6 +19,7 @@ import coef_reference as cr
 import fused_helpers as fh
 import lines_cases
 from plane_coding import decode_slot, encode_planes
+from sweep_reference import planes_of as _planes_of, slots as _slots
 
 pytestmark = pytest.mark.gpu
 KNOBS = ("HELIOS_RT_K", "HELIOS_RT_GENERIC_SCANS", "HELIOS_RT_MAXTHREADS", "HELIOS_RT_COEF_TPB", "HELIOS_RT_CLOUD_LDS")
@@ -84,22 +85,6 @@ def _base(ctx, flagset, shape):
     return _kept[key]
 
 
-def _slots(t, nbin, ny, H):
-    """(x, y, h, padding) per slot, each (tiles, ROWS, 64): plane_coding.decode_slot's arithmetic on whole arrays"""
-    ntiles = -(-nbin // t["nxb"]) * t["nparts"] * t["NW"]
-    tile = np.arange(ntiles)[:, None, None]
-    row = np.arange(t["ROWS"])[None, :, None]
-    lane = np.arange(64)[None, None, :]
-    wv, part, bx = tile % t["NW"], (tile // t["NW"]) % t["nparts"], tile // (t["NW"] * t["nparts"])
-    s_local = (wv * 64 + lane) // t["k"]
-    xl, yl = s_local // t["ypb"], s_local % t["ypb"]
-    x, y = bx * t["nxb"] + xl, part * t["ypb"] + yl
-    h = (lane % t["k"]) * t["ROWS"] + row
-    pad = (s_local >= t["nxb"] * t["ypb"]) | (x >= nbin) | (y >= ny) | (h >= H)
-    shape = np.broadcast(x, y, h).shape
-    return tuple(np.broadcast_to(a, shape) for a in (x, y, h, pad))
-
-
 def _stored(c, run):
     """the stored planes by (plane, half-layer, bin, Gauss point): what two tilings of one column must agree on bit for bit"""
     t, p = run["tiling"], run["planes"]
@@ -107,15 +92,6 @@ def _stored(c, run):
     x, y, h, pad = _slots(t, c.nbin, c.ny, H)
     out = np.zeros((t["nplane"], H * c.nbin * c.ny), p.dtype)
     out[:, ((h * c.nbin + x) * c.ny + y)[~pad]] = p.transpose(1, 0, 2, 3)[:, ~pad]
-    return out
-
-
-def _planes_of(c, t, p64):
-    """the six planes per slot as k_rt_flux reads them: v' from its plane, or 2 pi epsi ((1 - alpha) - beta) - u'"""
-    out = dict(alpha=p64[:, 0], beta=p64[:, 1], up=p64[:, 2])
-    out["vp"] = p64[:, t["pl_vp"]] if t["has_vp"] else 2.0 * np.pi * c.epsi * ((1.0 - out["alpha"]) - out["beta"]) - out["up"]
-    if c.dir_beam:
-        out["dd"], out["du"] = p64[:, t["pl_dd"]], p64[:, t["pl_dd"] + 1]
     return out
 
 

@@ -67,7 +67,8 @@ def shape_keys(rt):
             continue
         if s not in keys:
             keys.append(s)
-    assert len(keys) >= 57 and "T_lay" in keys and "cloud_deck_spectra" in keys and "vmr_int" in keys, keys
+    assert len(keys) >= 58 and "T_lay" in keys and "cloud_deck_spectra" in keys and "vmr_int" in keys, keys
+    assert "boa_source_factor" in keys
     return keys
 
 
@@ -87,6 +88,8 @@ class Batch(object):
         self.kind = kind
         if kind == "premixed":
             c = cases.make_case(nbin=3, ny=2, nlayer=2, clouds=1, dir_beam=1, albedo=0.25)
+        elif kind == "i2s":       # (not one of KINDS: test_boa_source_factor_per_column's, where E != 1 can occur)
+            c = cases.make_case(nbin=3, ny=2, nlayer=2, clouds=1, scat_corr=1, g_0=0.2, dir_beam=1, albedo=0.25)
         elif kind == "onthefly":
             # (two species: one absorber and the scatterer add_species appends)
             c = cases.add_species(cases.make_case(nbin=3, ny=20, nlayer=2, albedo=0.25), nspecies=1, with_h2o=False)
@@ -195,9 +198,49 @@ def test_every_name_reads_back_at_its_size_in_both_columns(batch):
             assert np.array_equal(got["vmr_lay"][col].reshape(S, I)[:, :L], vl * f)
     if not c.dir_beam:   # no beam: zeros of the reference's size
         assert not got["F_dir_wg"][1].any() and not got["Fc_dir_wg"][0].any()
+    # without the I2S correction E = 1 and the surface-emission factor (1 - w0) / (1 - w0) is exactly 1, in either method
+    for col in (0, 1):
+        assert got["boa_source_factor"][col].size == c.nbin * c.ny and np.all(got["boa_source_factor"][col] == 1.0)
     assert [int(rt.get(k, -1)[0]) for k in ("premixed_table_count", "mie_table_count")] == [0 if c.get("species") else 1, 0]
     assert rt.coef_plane_bytes() == 8 and rt.totals_chunks() >= 1 and rt.flux_tiling()["ROWS"] >= 1
     assert rt.coef_planes(1).shape == rt.coef_planes(0).shape and not np.array_equal(rt.coef_planes(0), rt.coef_planes(1))
+
+
+def test_boa_source_factor_per_column(ctx):
+    """boa_source_factor with the I2S correction on: ny * nbin values per column, get-only; column 1 of the batch is
+    column 0 of a batch of one that is given column 1's inputs, bit for bit (the column stride), and the two columns
+    differ at every spectral point where either scatters enough for E != 1 (elsewhere both are exactly 1)"""
+    from helios_amd.rt import batch_from_case
+    b = Batch(ctx, "i2s")
+    try:
+        rt, c = b.rt, b.c
+        n = c.nbin * c.ny
+        assert rt._shape("boa_source_factor") == (n, np.float64)
+        boa = [rt.get("boa_source_factor", col) for col in (0, 1)]
+        for col in (0, 1):
+            assert b.raw_get(col, "boa_source_factor", n * 8)[0] == 0
+            assert b.raw_get(col, "boa_source_factor", (n - 1) * 8)[0] == 1 and b.raw_get(col, "boa_source_factor", (n + 1) * 8)[0] == 1
+        assert b.raw_get(-1, "boa_source_factor", n * 8)[0] == 1 and b.raw_get(2, "boa_source_factor", n * 8)[0] == 1
+        assert b.raw_set(0, "boa_source_factor", np.ones(n))[0] == 1 and b.raw_ptr(0, "boa_source_factor")[0] == 1
+        for a in boa:
+            assert np.all(np.isfinite(a)) and np.all(a > 0.0) and np.all(a <= 1.0)
+        corrected = (boa[0] != 1.0) | (boa[1] != 1.0)
+        assert corrected.any(), "no spectral point with E != 1: the case does not test the stride"
+        assert np.all(boa[0][corrected] != boa[1][corrected])
+        one = batch_from_case(ctx, c, ncol=1)
+        try:
+            p_lay, p_int, T_lay, albedo = column_inputs(c, 1)
+            one.set_column_profile(0, p_lay, p_int, T_lay, albedo, c.starflux)
+            one.set_column_clouds(0, c.abs_cross_all_clouds_lay * 0.5, c.abs_cross_all_clouds_int * 0.5,
+                                  c.scat_cross_all_clouds_lay * 0.25, c.scat_cross_all_clouds_int * 0.25,
+                                  c.g_0_all_clouds_lay * 0.5, c.g_0_all_clouds_int * 0.5)
+            one.build_planck_table(1)
+            one.step(0)
+            np.testing.assert_array_equal(one.get("boa_source_factor", 0).view(np.uint64), boa[1].view(np.uint64))
+        finally:
+            one.close()
+    finally:
+        b.rt.close()
 
 
 def test_wrong_sizes_unknown_names_and_columns_are_refused(batch):
