@@ -3,10 +3,11 @@
 Counterpart of the reference's `Compute` (source/computation.py).  Every per-stage method keeps its
 reference name and calls the matching `hx_<kernel>` entry point of libhelios_hip.so with the `Store`'s
 device arrays in the reference kernel's argument order -- no block/grid arguments, no synchronize after
-each launch (calls are ordered on one stream).  `radiation_loop` / `convection_loop` keep the reference's
-control flow but run the iteration body through the fused path (hx_rt_*) whenever the
-configuration allows (non-isothermal layers, iterative flux solver -- the defaults), polling the
-device-side convergence count instead of copying flags back every iteration.
+each launch (calls are ordered on one stream).  `radiation_loop` / `convection_loop` choose between two paths: the
+device-resident loops (hx_rt_run, hx_rt_conv_run) whenever the configuration allows (`_why_not_fused`), paced by the
+one host driver of helios_amd/loops.py, which a sweep's batches go through as well -- a single run is a batch of one;
+these methods add the single run's progress lines, its abort and the copy back onto the Store -- or else the per-stage
+loops, which keep the reference's control flow line by line.
 """
 import ctypes
 
@@ -16,6 +17,7 @@ import numpy as np
 
 from . import _lib
 from . import host_functions as hsfunc
+from . import loops
 from . import phys_const as pc
 from .device import Context
 from .rt import RTBatch
@@ -445,21 +447,19 @@ class Compute(object):
         self.calculate_direct_beamflux(quant)
 
     @staticmethod
-    def _stop_for_coupling_output(quant, it, nxt):
-        """coupled runs may ask for the current T-P profile every n iterations (computation.py:967-971): end the chunk
-        where the reference would write it"""
-        n = int(getattr(quant, "coupl_tp_write_interval", 0) or 0)
-        if quant.coupling == 1 and n > 0:
-            due = it + 1 + (n - 1 - (it + 1) % n) % n       # first iteration count > it with count % n == n - 1
-            nxt = min(nxt, due)
-        return nxt
-
-    @staticmethod
     def _coupling_output(quant, it, write, read):
         n = int(getattr(quant, "coupl_tp_write_interval", 0) or 0)
         if quant.coupling == 1 and n > 0 and it % n == n - 1 and write is not None:
-            quant.T_lay = quant.rt.get("T_lay") if quant.rt is not None else quant.dev_T_lay.get()
+            quant.T_lay = quant.rt.get("T_lay", int(getattr(quant, "rt_col", 0))) if quant.rt is not None else quant.dev_T_lay.get()
             write.write_tp_for_coupling(quant, read)
+
+    @staticmethod
+    def _abort_run(quant, write, read):
+        """a single run's answer to exceeding the iteration limit (computation.py:977-980)"""
+        if write is not None:
+            write.write_abort_file(quant, read)
+        print("\nRun exceeds allowed maximum allowed number of iteration steps. Aborting...")
+        raise SystemExit()
 
     def _refresh_additional_heating(self, quant):
         """heating flux of the layers from the heating density and the current layer heights, every 10th iteration
@@ -680,66 +680,10 @@ class Compute(object):
             return self._radiation_loop_stagewise(quant, write, read, rt_plot)
         if quant.rt is None:
             quant.rt = self._make_rt(quant)
-        rt = quant.rt
-        L = _i(quant.nlayer)
         self.ctx.timer_start()
-        if quant.singlewalk == 1:
-            # post-processing run type (computation.py:983-984): one pass -- refresh, 1000*scat+1 sweeps inside one
-            # launch of the flux kernel, quadrature -- and no temperature iteration
-            if quant.opacity_mixing == "on-the-fly":
-                self._push_vmr(quant)
-            rt.step(0, step_temperature=False)
-            self.report_diagnostics(quant)
-            ms = self.ctx.timer_stop_ms()
-            print("\nTime for radiative iteration [s]: {:.2f}".format(ms * 1e-3))
-            print("Total number of iterative steps: " + str(quant.iter_value))
-            self.sync_store_from_rt(quant)
-            return
-        it = 0
-        condition1 = condition2 = condition3 = True
-        while condition1 and condition2 and condition3:
-            # work up to the next host-visible event: a refresh that needs host VMRs, a criterion
-            # relaxation, the 100-iteration surface-temperature check, or the iteration limit
-            if quant.opacity_mixing == "on-the-fly" and it == 0:
-                self._push_vmr(quant)
-            nxt = min(it + (10 - it % 10), _i(quant.max_nr_iterations) + 1)
-            for r in quant.crit_relaxation_numbers:
-                if it < r < nxt:
-                    nxt = int(r)
-            # the reference looks at the surface temperature inside every iteration whose index is a multiple of 100
-            # (computation.py:946-952), i.e. after 1, 101, 201, ... completed iterations: end a chunk there
-            nxt = min(nxt, it + 1 + (100 - it % 100) % 100)
-            if quant.physical_tstep != 0:                        # computation.py:941-943, tested every iteration
-                nxt = min(nxt, max(it + 1, self._runtime_limit_iteration(quant)))
-            nxt = self._stop_for_coupling_output(quant, it, nxt)
-            rt.run(it, nxt - it)
-            self.report_diagnostics(quant)
-            it_prev, it = it, nxt
-            counts = rt.converged_layers()                       # blocks: one small D2H per <=10 iterations
-            done = int(rt.get("done")[0])
-            if quant.singlewalk == 0 and it_prev >= _i(quant.foreplay) and (it_prev % 100 == 0 or done):
-                print("\nWe are running \"" + str(quant.name) + "\" at iteration step nr. : " + str(it_prev))
-                print("Layers (& surface/BOA) converged: " + str(int(counts[0])) + " out of " + str(L + 1) + ".")
-            if done:
-                it = int(rt.get("iters_done")[0])                # the device froze the column exactly there
-                condition1 = False
-            if quant.physical_tstep != 0:
-                condition3 = it * quant.physical_tstep < quant.runtime_limit
-            if (it - 1) % 100 == 0:
-                T_surf = rt.get("T_lay")[L]                      # computation.py:946-952
-                condition2 = T_surf < quant.plancktable_dim * quant.plancktable_step - 2
-                if not condition2 and quant.iso == 0:            # (isothermal layers cannot be adjusted: see convection_loop)
-                    quant.convection = 1
-            self._coupling_output(quant, it, write, read)
-            if it in quant.crit_relaxation_numbers:
-                hsfunc.relax_radiative_convergence_criterion(quant)
-                rt.set_convergence_limit(0, quant.rad_convergence_limit)
-            if it > quant.max_nr_iterations:
-                if write is not None:
-                    write.write_abort_file(quant, read)
-                print("\nRun exceeds allowed maximum allowed number of iteration steps. Aborting...")
-                raise SystemExit()
-        quant.iter_value = np.int32(it)
+        loops.radiation(self, [quant], quant.rt, write, read, progress=True)
+        if getattr(quant, "aborted", False):
+            self._abort_run(quant, write, read)
         ms = self.ctx.timer_stop_ms()
         print("\nTime for radiative iteration [s]: {:.2f}".format(ms * 1e-3))
         print("Total number of iterative steps: " + str(quant.iter_value))
@@ -838,10 +782,7 @@ class Compute(object):
                 if quant.iter_value in quant.crit_relaxation_numbers:
                     hsfunc.relax_radiative_convergence_criterion(quant)
                 if quant.iter_value > quant.max_nr_iterations:
-                    if write is not None:
-                        write.write_abort_file(quant, read)
-                    print("\nRun exceeds allowed maximum allowed number of iteration steps. Aborting...")
-                    raise SystemExit()
+                    self._abort_run(quant, write, read)
             else:
                 condition1 = False
         ms = self.ctx.timer_stop_ms()
@@ -853,78 +794,6 @@ class Compute(object):
         for n in ("F_net", "F_up_tot", "F_down_tot", "F_net_diff", "T_lay", "meanmolmass_lay", "F_smooth_sum"):
             dev = getattr(quant, "dev_" + n)
             setattr(quant, n, dev.get())
-
-    def _convection_loop_fused(self, quant, write=None, read=None):
-        """the convection loop on the device-resident state: convective adjustment, sweeps, layer marking, equilibrium
-        test and temperature step all run on the GPU (hx_rt_conv_*); the host only paces the loop in chunks that end at
-        refresh boundaries, criterion relaxations and the iteration limit (reference computation.py:992-1174)"""
-        rt = quant.rt
-        L = _i(quant.nlayer)
-        for n in ("T_lay", "F_net", "F_up_tot", "F_down_tot"):
-            setattr(quant, n, rt.get(n))
-        quant.p_lay, quant.p_int = np.asarray(quant.p_lay, float), np.asarray(quant.p_int, float)
-        if self._kappa_from_table(quant):         # per-stage kernels on the Store's arrays (synced after the radiation loop)
-            self.interpolate_kappa_and_cp(quant)
-            quant.kappa_lay, quant.kappa_int = quant.dev_kappa_lay.get(), quant.dev_kappa_int.get()
-            quant.c_p_lay = quant.dev_c_p_lay.get()
-        hsfunc.conv_check(quant)
-        hsfunc.mark_convective_layers(quant, stitching=0)
-        condition = sum(quant.conv_unstable) > 0
-        quant.iter_value = np.int32(0)
-        if not condition:
-            print("\nAll layers convectively stable. No convective adjustment necessary.\n")
-            print("\nTime for rad.-conv. iteration [s]: {:.2f}".format(0.0))
-            print("Total number of iterative steps: " + str(quant.iter_value))
-            return
-        print("\nConvectively unstable layers found. Starting convective adjustment")
-        rt.set_state(0, "kappa_lay", np.asarray(quant.kappa_lay, np.float64))
-        rt.set_state(0, "kappa_int", np.asarray(quant.kappa_int, np.float64))
-        rt.set_state(0, "c_p_lay", np.asarray(quant.c_p_lay, np.float64))
-        rt.set_state(0, "conv_layer", np.asarray(quant.conv_layer, np.int32))
-        rt.set_state(0, "conv_unstable", np.asarray(quant.conv_unstable, np.int32))
-        dampara = -1.0 if quant.input_dampara == "automatic" else float(quant.input_dampara)
-        rt.set_state(0, "dampara", np.array([dampara], np.float64))
-        rt.set_state(0, "done", np.zeros(1, np.int32))
-        rt.set_convergence_limit(0, quant.rad_convergence_limit)
-        self.ctx.timer_start()
-        it, done = 0, 0
-        while not done:
-            if it % 100 == 0:
-                print("\nWe are running \"" + str(quant.name) + "\" at iteration step nr. : " + str(it))
-            nxt = min(it + (10 - it % 10), _i(quant.max_nr_iterations) + 1)
-            for r in quant.crit_relaxation_numbers:
-                if it < r < nxt:
-                    nxt = int(r)
-            nxt = self._stop_for_coupling_output(quant, it, nxt)
-            # (the mixing ratios of FastChem species follow the profile on the device: before the adjustment for the mean
-            # molecular mass, and for the adjusted profile in the refresh -- computation.py:1030-1036, :1056-1061)
-            rt.conv_run(it, nxt - it)
-            self.report_diagnostics(quant)
-            it = nxt
-            done = int(rt.get("done")[0])                        # one small D2H per <= 10 iterations
-            if done:
-                it = int(rt.get("iters_done")[0])
-            self._coupling_output(quant, it, write, read)
-            if it in quant.crit_relaxation_numbers:
-                hsfunc.relax_radiative_convergence_criterion(quant)
-                rt.set_convergence_limit(0, quant.rad_convergence_limit)
-            if it > quant.max_nr_iterations:
-                if write is not None:
-                    write.write_abort_file(quant, read)
-                print("\nRun exceeds allowed maximum allowed number of iteration steps. Aborting...")
-                raise SystemExit()
-        quant.iter_value = np.int32(it)
-        ms = self.ctx.timer_stop_ms()
-        quant.conv_layer = rt.get("conv_layer")
-        quant.conv_unstable = rt.get("conv_unstable")
-        quant.marked_red = rt.get("marked_red")
-        quant.dev_F_smooth_sum.set(rt.get("F_smooth_sum"))
-        for n in ("kappa_lay", "kappa_int", "c_p_lay"):
-            setattr(quant, n, rt.get(n))
-            getattr(quant, "dev_" + n).set(getattr(quant, n))
-        print("\nTime for rad.-conv. iteration [s]: {:.2f}".format(ms * 1e-3))
-        print("Total number of iterative steps: " + str(quant.iter_value))
-        self.sync_store_from_rt(quant)
 
     def convection_loop(self, quant, write=None, read=None, rt_plot=None):
         """alternate convective adjustment and radiative steps, reference computation.py:992-1174: on the fused,
@@ -938,7 +807,21 @@ class Compute(object):
             raise IOError("ERROR: convective adjustment needs non-isothermal layers (the reference cannot run this "
                           "combination either); set 'isothermal layers = no' or 'convective adjustment = no'")
         if self._fused_supported(quant) and quant.rt is not None and quant.physical_tstep == 0:
-            return self._convection_loop_fused(quant, write, read)
+            rt = quant.rt
+            self.ctx.timer_start()
+            convected = loops.convection(self, [quant], rt, write, read, progress=True)[0] > 0
+            if getattr(quant, "aborted", False):
+                self._abort_run(quant, write, read)
+            ms = self.ctx.timer_stop_ms()
+            print("\nTime for rad.-conv. iteration [s]: {:.2f}".format(ms * 1e-3))
+            print("Total number of iterative steps: " + str(quant.iter_value))
+            if convected or self._kappa_from_table(quant):      # kappa and c_p of the final profile, for the output files
+                for n in ("kappa_lay", "kappa_int", "c_p_lay"):
+                    getattr(quant, "dev_" + n).set(getattr(quant, n))
+            if convected:
+                quant.dev_F_smooth_sum.set(rt.get("F_smooth_sum"))
+                self.sync_store_from_rt(quant)
+            return
         self._tell_stagewise_is_double(quant)
         if quant.rt is not None:      # the per-stage loop continues from the fused state
             self.sync_store_from_rt(quant, flux_state=True)
@@ -1001,10 +884,7 @@ class Compute(object):
             if quant.iter_value in quant.crit_relaxation_numbers:
                 hsfunc.relax_radiative_convergence_criterion(quant)
             if quant.iter_value > quant.max_nr_iterations:
-                if write is not None:
-                    write.write_abort_file(quant, read)
-                print("\nRun exceeds allowed maximum allowed number of iteration steps. Aborting...")
-                raise SystemExit()
+                self._abort_run(quant, write, read)
         ms = self.ctx.timer_stop_ms()
         print("\nTime for rad.-conv. iteration [s]: {:.2f}".format(ms * 1e-3))
         print("Total number of iterative steps: " + str(quant.iter_value))

@@ -19,6 +19,7 @@ import numpy as np
 from . import additional_heating as add_heat
 from . import computation as comp
 from . import host_functions as hsfunc
+from . import loops
 from . import quantities as quant_mod
 from . import read as read_mod
 from . import write as write_mod
@@ -179,136 +180,6 @@ def _batch_signature(q):
             int(getattr(q, "real_star", 0)))      # (a flag of the whole batch: black-body stars and spectra from a file do not mix)
 
 
-def _radiation_loop(computer, quants, rt):
-    """Compute.radiation_loop for every column of the batch at once: a column that satisfies its criterion is frozen
-    on the device; the host paces the batch in chunks that end at refresh boundaries and criterion relaxations"""
-    q0 = quants[0]
-    ncol = len(quants)
-    done = np.zeros(ncol, bool)
-    iters = np.zeros(ncol, np.int64)
-    if q0.singlewalk == 1:
-        # post-processing run type (computation.py:983-984, Compute.radiation_loop): ONE pass over the given T-P profiles --
-        # refresh, 1000*scat+1 sweeps inside one launch of the flux kernel, quadrature -- and no temperature step
-        if q0.opacity_mixing == "on-the-fly":
-            for q in quants:
-                computer._push_vmr(q)
-        rt.step(0, step_temperature=False)
-        computer.report_diagnostics(q0)
-        for q in quants:
-            q.iter_value = np.int32(0)
-        return iters
-    it = 0
-    while not done.all():
-        # once per loop, as Compute.radiation_loop does: constant and file-given profiles never change, a FastChem species'
-        # profile is re-interpolated on the device at every refresh from ITS COLUMN's (T, P) table (make_rt_batch)
-        if q0.opacity_mixing == "on-the-fly" and it == 0:
-            for c in np.nonzero(~done)[0]:
-                computer._push_vmr(quants[c])
-        nxt = min(it + (10 - it % 10), int(q0.max_nr_iterations) + 1)
-        for r in q0.crit_relaxation_numbers:
-            if it < r < nxt:
-                nxt = int(r)
-        nxt = min(nxt, it + 1 + (100 - it % 100) % 100)      # the 100-iteration surface-temperature check
-        rt.run(it, nxt - it)
-        computer.report_diagnostics(quants[0])
-        it = nxt
-        for c in np.nonzero(~done)[0]:
-            if int(rt.get("done", c)[0]):
-                done[c] = True
-                iters[c] = int(rt.get("iters_done", c)[0])
-        if (it - 1) % 100 == 0:     # computation.py:946-952: a surface hotter than the Planck table ends the radiative loop
-            for c in np.nonzero(~done)[0]:
-                q = quants[c]
-                if not rt.get("T_lay", c)[int(q.nlayer)] < q.plancktable_dim * q.plancktable_step - 2:
-                    if q.iso == 0:
-                        q.convection = 1
-                    done[c] = True
-                    iters[c] = it
-                    rt.set_state(int(c), "done", np.ones(1, np.int32))
-        if it in q0.crit_relaxation_numbers:
-            for c in np.nonzero(~done)[0]:
-                hsfunc.relax_radiative_convergence_criterion(quants[c])
-                rt.set_convergence_limit(int(c), quants[c].rad_convergence_limit)
-        if it > q0.max_nr_iterations:
-            for c in np.nonzero(~done)[0]:      # give up on the rest; they are written with an abort marker
-                quants[c].aborted = True
-                iters[c] = it
-                done[c] = True
-            rt.set_state(-1, "done", np.ones(1, np.int32))
-    for c, q in enumerate(quants):
-        q.iter_value = np.int32(iters[c])
-    return iters
-
-
-def _convection_loop(computer, quants, rt):
-    """Compute._convection_loop_fused for the batch: columns without a super-adiabatic layer stay frozen, the others
-    run the device-side convection loop until their own loop condition turns false"""
-    q0 = quants[0]
-    ncol = len(quants)
-    active = np.zeros(ncol, bool)
-    iters = np.zeros(ncol, np.int64)
-    from_table = any(computer._kappa_from_table(q) for q in quants)
-    if from_table:    # kappa / c_p follow the profile the radiation loop left behind (computation.py:1037), as in a single run
-        rt.kappa_cp_refresh()
-    for c, q in enumerate(quants):
-        if not (q.singlewalk == 0 and q.convection == 1) or getattr(q, "aborted", False):
-            continue
-        for n in ("T_lay", "F_net", "F_up_tot", "F_down_tot"):
-            setattr(q, n, rt.get(n, c))
-        if from_table:
-            for n in ("kappa_lay", "kappa_int", "c_p_lay"):
-                setattr(q, n, rt.get(n, c))
-        q.p_lay, q.p_int = np.asarray(q.p_lay, float), np.asarray(q.p_int, float)
-        hsfunc.conv_check(q)
-        hsfunc.mark_convective_layers(q, stitching=0)
-        q.iter_value = np.int32(0)      # the convection loop counts from zero, also when it has nothing to do
-        if sum(q.conv_unstable) > 0:
-            active[c] = True
-            for name, v, dt in (("kappa_lay", q.kappa_lay, np.float64), ("kappa_int", q.kappa_int, np.float64),
-                                ("c_p_lay", q.c_p_lay, np.float64), ("conv_layer", q.conv_layer, np.int32),
-                                ("conv_unstable", q.conv_unstable, np.int32)):
-                rt.set_state(c, name, np.asarray(v, dt))
-            rt.set_state(c, "dampara", np.array([-1.0 if q.input_dampara == "automatic" else float(q.input_dampara)]))
-            rt.set_state(c, "done", np.zeros(1, np.int32))
-            rt.set_convergence_limit(c, q.rad_convergence_limit)
-    if not active.any():
-        return iters
-    running = active.copy()
-    it = 0
-    while running.any():
-        nxt = min(it + (10 - it % 10), int(q0.max_nr_iterations) + 1)
-        for r in q0.crit_relaxation_numbers:
-            if it < r < nxt:
-                nxt = int(r)
-        # (tabulated chemistry follows the temperatures on the device, ahead of the adjustment and for the adjusted profile:
-        # k_rt_mmm_from_vmr and the refresh, computation.py:1030-1036, :1056-1061 -- no host step per decade)
-        rt.conv_run(it, nxt - it)
-        computer.report_diagnostics(quants[0])
-        it = nxt
-        for c in np.nonzero(running)[0]:
-            if int(rt.get("done", c)[0]):
-                running[c] = False
-                iters[c] = int(rt.get("iters_done", c)[0])
-        if it in q0.crit_relaxation_numbers:
-            for c in np.nonzero(running)[0]:
-                hsfunc.relax_radiative_convergence_criterion(quants[c])
-                rt.set_convergence_limit(int(c), quants[c].rad_convergence_limit)
-        if it > q0.max_nr_iterations:
-            for c in np.nonzero(running)[0]:
-                quants[c].aborted = True
-                iters[c] = it
-            rt.set_state(-1, "done", np.ones(1, np.int32))
-            break
-    for c in np.nonzero(active)[0]:
-        q = quants[c]
-        q.iter_value = np.int32(iters[c])
-        q.conv_layer, q.conv_unstable = rt.get("conv_layer", c), rt.get("conv_unstable", c)
-        q.marked_red = rt.get("marked_red", c)
-        for n in ("kappa_lay", "kappa_int", "c_p_lay"):      # what the output files report, as in a single run
-            setattr(q, n, rt.get(n, c))
-    return iters
-
-
 def _finish_column(computer, q, reader, writer):
     """post-loop diagnostics and output files of one column (helios.py:88-126), on the Store's own device arrays"""
     if getattr(q, "cloud_decks", None) is not None and q.clouds == 1:
@@ -380,8 +251,8 @@ def _run_columns(base_argv, overrides_list, cols, computer, writer, shared, colu
         rt = computer.make_rt_batch(quants)
         computer.ctx.synchronize()
         t1 = time.perf_counter()
-        _radiation_loop(computer, quants, rt)
-        _convection_loop(computer, quants, rt)
+        loops.radiation(computer, quants, rt)      # (no writer: a sweep hands no profile over during the run, and an
+        loops.convection(computer, quants, rt)     # aborted column gets its marker file in _finish_column)
         computer.ctx.synchronize()
         t2 = time.perf_counter()
         timing["batch"] += t1 - t0

@@ -335,7 +335,7 @@ def test_fused_convection_loop_golden(ctx, name):
                     assert n_rad < 40000
                 if done:
                     n_rad = int(rt.get("iters_done")[0])
-            # entry of the loop, computation.py:998-1009 (what Compute._convection_loop_fused does)
+            # entry of the loop, computation.py:998-1009 (what helios_amd.loops.convection does)
             q = ld.conv_quant(c, s, kappa)
             q.T_lay = rt.get("T_lay")
             hs.conv_check(q)
