@@ -60,6 +60,8 @@ def run_helios(argv=None):
     computer.integrate_optdepth_transmission(keeper)
     if keeper.transit_depth_spectrum == 1:
         computer.calculate_transit_depth(keeper)
+    if keeper.emission_angles > 0:
+        computer.calculate_emission_angles(keeper)
     computer.calculate_contribution_function(keeper)
     if keeper.convection == 1:
         computer.interpolate_entropy(keeper)

@@ -199,6 +199,7 @@ class Compute(object):
     # ---- flux solve ----------------------------------------------------------------------------------
     def populate_spectral_flux_iteratively(self, quant):
         q = quant
+        q.spectral_fluxes_current = True
         nscat_step = 3 if q.singlewalk == 0 else 1000          # computation.py:531-537
         for _ in range(nscat_step * _i(q.scat) + 1):
             if q.iso == 1:
@@ -224,6 +225,7 @@ class Compute(object):
     def solve_for_spectral_fluxes_via_matrix(self, quant):
         """source/computation.py:625-710: one tridiagonal solve per spectral point instead of the sweeps"""
         q = quant
+        q.spectral_fluxes_current = True
         work = (q.dev_alpha.d, q.dev_beta.d, q.dev_source_term_down.d, q.dev_source_term_up.d,
                 q.dev_c_prime.d, q.dev_d_prime.d, q.dev_scat_trigger.i)
         if q.iso == 1:
@@ -398,6 +400,60 @@ class Compute(object):
         if worst > 1e-3:
             print("\nWARNING: the deepest transit chord transmits up to %.3g of the star light in a bin: the bottom of the "
                   "model is not opaque there, and the transit radius of such a bin is a lower limit." % worst)
+
+    @staticmethod
+    def emission_quadrature(N):
+        """(mu, w, 1 / mu) of the N emission angles: the Gauss-Legendre nodes and weights mapped onto [0, 1], ascending in mu"""
+        x, w = np.polynomial.legendre.leggauss(int(N))
+        mu = (x + 1.0) / 2.0
+        return mu, w / 2.0, 1.0 / mu
+
+    def calculate_emission_angles(self, quant):
+        """the intensity leaving the top of the atmosphere along `emission angles` directions and its disc sum per bin
+        (hx_emission_angles; README, "Angular emission spectrum").  Fills quant.emission_mu, emission_weight,
+        emission_intensity [N][nbin] and emission_angular_flux [nbin].
+
+        The kernel reads the spectral fluxes of the Store.  After the per-stage loops they are those of the last flux solve
+        (`spectral_fluxes_current`, also when a per-stage loop continued from the device-resident state).  After the
+        device-resident loop the Store holds none: the loop's up-flux state is brought over and the run's own flux solve runs
+        once through the per-stage entry points, at the final temperatures.  It writes the spectral flux arrays only, which
+        no output file reads -- no integrate_flux, no temperature step."""
+        q = quant
+        ctx = self._ctx_of(q)
+        X, Y, L, N = _i(q.nbin), _i(q.ny), _i(q.nlayer), _i(q.emission_angles)
+        if q.rt is not None and not q.spectral_fluxes_current:
+            self._flux_state_from_rt(q)
+            if q.flux_calc_method == "matrix":
+                self.solve_for_spectral_fluxes_via_matrix(q)
+            else:
+                self.populate_spectral_flux_iteratively(q)
+        mu, weight, mu_inv = self.emission_quadrature(N)
+        beam = q.dir_beam == 1
+        beta = 1.0 / (4.0 * np.pi * abs(_f(q.mu_star))) if beam else 0.0
+        null = ctypes.POINTER(ctypes.c_double)()
+        dir_of = lambda dev: dev.d if beam else null
+        if q.iso == 1:
+            shells = (q.dev_delta_tau_wg.d, null, q.dev_delta_tau_all_clouds.d, null, q.dev_w_0.d, null)
+            planck = (q.dev_planckband_lay.d, null)
+            centres = (null, null, null)
+        else:
+            shells = (q.dev_delta_tau_wg_lower.d, q.dev_delta_tau_wg_upper.d, q.dev_delta_tau_all_clouds_lower.d,
+                      q.dev_delta_tau_all_clouds_upper.d, q.dev_w_0_lower.d, q.dev_w_0_upper.d)
+            planck = (q.dev_planckband_lay.d, q.dev_planckband_int.d)
+            centres = (q.dev_Fc_up_wg.d, q.dev_Fc_down_wg.d, dir_of(q.dev_Fc_dir_wg))
+        dev_mu_inv = ctx.to_gpu(mu_inv)
+        dev_I = ctx.empty(N * X)
+        self._call("hx_emission_angles", *shells, *planck, q.dev_F_up_wg.d, q.dev_F_down_wg.d, dir_of(q.dev_F_dir_wg),
+                   *centres, q.dev_gauss_weight.d, dev_mu_inv.d, beta, X, Y, L, N, dev_I.d, null)
+        I = dev_I.get().reshape(N, X)
+        for d in (dev_mu_inv, dev_I):
+            d.free()
+        acc = np.zeros(X)
+        for m in range(N):
+            acc = acc + (weight[m] * mu[m]) * I[m]
+        q.emission_mu, q.emission_weight = mu, weight
+        q.emission_intensity = I
+        q.emission_angular_flux = (2.0 * np.pi) * acc
 
     def calculate_contribution_function(self, quant):
         q = quant
@@ -694,6 +750,7 @@ class Compute(object):
         the persistent up-flux state (decoded from the tiles on the host) only when a per-stage loop is going to continue
         from it (`flux_state`)."""
         rt, col = quant.rt, int(getattr(quant, "rt_col", 0))
+        quant.spectral_fluxes_current = False      # the loop's state is newer than any per-stage solve on the Store
         X, Y, L, I = _i(quant.nbin), _i(quant.ny), _i(quant.nlayer), _i(quant.ninterface)
         for n in ("T_lay", "T_int", "F_up_band", "F_down_band", "F_dir_band", "F_up_tot", "F_down_tot", "F_net",
                   "F_net_diff", "planckband_lay", "planckband_int", "scat_cross_lay", "scat_cross_int",
@@ -716,12 +773,7 @@ class Compute(object):
             quant.dev_F_dir_wg.fill_zero()
             quant.dev_Fc_dir_wg.fill_zero()
         if flux_state:
-            for n in ("F_up_wg",) + (("Fc_up_wg",) if quant.iso == 0 else ()):
-                v = rt.get(n, col)
-                dev = getattr(quant, "dev_" + n)
-                buf = np.zeros(dev.size)
-                buf[:v.size] = v
-                dev.set(buf)
+            self._flux_state_from_rt(quant)
         if quant.add_heating == 1:
             for n in ("F_add_heat_lay", "F_add_heat_sum"):
                 setattr(quant, n, rt.get(n, col))
@@ -734,6 +786,17 @@ class Compute(object):
             self._pull_vmr(quant)
         # transmission arrays for the post-loop diagnostics come from the per-stage kernel
         self.calculate_transmission(quant)
+
+    @staticmethod
+    def _flux_state_from_rt(quant):
+        """the device-resident loop's persistent up-flux state (decoded from the tiles on the host) onto the Store"""
+        rt, col = quant.rt, int(getattr(quant, "rt_col", 0))
+        for n in ("F_up_wg",) + (("Fc_up_wg",) if quant.iso == 0 else ()):
+            v = rt.get(n, col)
+            dev = getattr(quant, "dev_" + n)
+            buf = np.zeros(dev.size)
+            buf[:v.size] = v
+            dev.set(buf)
 
     def _radiation_loop_stagewise(self, quant, write=None, read=None, rt_plot=None):
         """the reference's loop, stage by stage (isothermal layers, post-processing run type, ...)"""

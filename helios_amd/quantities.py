@@ -75,6 +75,14 @@ class Store(object):
         self.transit_floor_transmission = None
         self.transit_area = None          # A_x [cm^2]: the occulting area above the lowest boundary, divided by pi
         self.transit_zb = None            # the ascending shell boundaries the spectrum was integrated on [cm]
+        # TOA intensities along the emission angles (Compute.calculate_emission_angles; None unless `emission angles` > 0)
+        self.emission_angles = np.int32(0)
+        self.emission_mu = None
+        self.emission_weight = None
+        self.emission_intensity = None     # [N][nbin], per steradian, in the units of F_up_band
+        self.emission_angular_flux = None  # [nbin]: 2 pi sum_m w_m mu_m I_m
+        # whether dev_F_*_wg / dev_Fc_*_wg hold a per-stage flux solve newer than the device-resident loop's state
+        self.spectral_fluxes_current = False
         self.rt = None          # helios_amd.rt.RTBatch of the fused path, created by Compute
 
     # ---------------------------------------------------------------------------------------------

@@ -110,6 +110,8 @@ _OPTIONS = [
     ("synthetic --> bins layers-are-set-above ntemp npress seed", "synthetic_spec", "synthetic", "300 30 20 20241"),
     # the same column seen in transit (not in the reference; README, "Transit depth spectrum")
     ("transit depth spectrum", "transit_depth_spectrum", "transit_depth_spectrum", "no"),
+    # TOA intensities along N emission angles (not in the reference; README, "Angular emission spectrum"); 0 = off
+    ("emission angles", "emission_angles", "emission_angles", "0"),
 ]
 
 
@@ -117,6 +119,17 @@ def _yes_no(v):
     if v in ("yes", "no"):
         return np.int32(1 if v == "yes" else 0)
     raise IOError("ERROR: expected 'yes' or 'no', got %r" % (v,))
+
+
+def _emission_angles(v):
+    """the number of emission angles: an integer 0 ... 16"""
+    try:
+        n = int(str(v).strip())
+    except ValueError:
+        n = -1
+    if not 0 <= n <= 16 or str(n) != str(v).strip().lstrip("+"):
+        raise IOError("ERROR: emission angles must be an integer 0 ... 16, got %r" % (v,))
+    return np.int32(n)
 
 
 class Species(object):
@@ -356,6 +369,7 @@ class Read(object):
         quant.realtime_plot = i32(0)
         self.synthetic_spec = val["synthetic_spec"]
         quant.transit_depth_spectrum = _yes_no(val["transit_depth_spectrum"])
+        quant.emission_angles = _emission_angles(val["emission_angles"])
 
         # ---- derived settings (read.py:884-985) ----
         # `single` stores the device-resident loop's coefficient planes in fp32 (hx_rt_flags.coef_fp32); every other

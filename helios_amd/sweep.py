@@ -201,6 +201,8 @@ def _finish_column(computer, q, reader, writer):
     computer.integrate_optdepth_transmission(q)
     if q.transit_depth_spectrum == 1:
         computer.calculate_transit_depth(q)
+    if q.emission_angles > 0:
+        computer.calculate_emission_angles(q)
     computer.calculate_contribution_function(q)
     if q.convection == 1:
         computer.interpolate_entropy(q)

@@ -446,6 +446,28 @@ class Write(object):
                     x, quant.opac_wave[x] * 1e4, quant.transit_radius[x], quant.transit_depth[x],
                     quant.transit_floor_transmission[x]))
 
+    @staticmethod
+    def write_emission_angles(quant, read):
+        """only with `emission angles` > 0: the intensities leaving the top of the atmosphere (README, "Angular emission
+        spectrum").  The result columns carry 17 significant digits: they are compared, not only plotted."""
+        N = int(getattr(quant, "emission_angles", 0))
+        if N < 1 or quant.emission_intensity is None:
+            return
+        X, L = int(quant.nbin), int(quant.nlayer)
+        num = lambda v: " ".join("{:.17g}".format(float(a)) for a in v)
+        with open(Write._path(quant, read, "_emission_angles.dat"), "w") as f:
+            f.write("This file contains the intensity leaving TOA along {:d} emission angles [erg s^-1 cm^-3 sr^-1], its disc "
+                    "sum angular_flux = 2 pi sum_m w_m mu_m I(mu_m) and, for comparison, the two-stream F_up at TOA "
+                    "[erg s^-1 cm^-3].".format(N))
+            f.write("\nmu: " + num(quant.emission_mu))
+            f.write("\nweight: " + num(quant.emission_weight))
+            f.write("\n{:<8}{:<18}{:<26}{:<26}".format("bin", "cent_lambda[um]", "angular_flux", "two_stream_flux"))
+            f.write("".join("{:<26}".format("I(mu_%d)" % m) for m in range(N)))
+            for x in range(X):
+                f.write("\n{:<8g}{:<18.9g}{:<26.17g}{:<26.17g}".format(
+                    x, quant.opac_wave[x] * 1e4, quant.emission_angular_flux[x], quant.F_up_band[x + L * X]))
+                f.write("".join("{:<26.17g}".format(quant.emission_intensity[m][x]) for m in range(N)))
+
     # ---- photochemical-kinetics coupling: the T-P profile handed to the chemistry code (write.py:717-771) ---------
     @staticmethod
     def _coupling_tp_path(quant, read, step, previous=False):
@@ -491,3 +513,5 @@ class Write(object):
                   self.write_mean_extinction, Write.write_flux_ratio_only, Write.write_phase_state,
                   Write.write_surface_albedo, Write.write_criterion_warning_file, Write.write_transit_depth):
             w(quant, read)
+        if int(getattr(quant, "emission_angles", 0)) > 0:
+            Write.write_emission_angles(quant, read)

@@ -325,6 +325,24 @@ int hx_transit_depth(hx_context* ctx, const double* delta_tau_wg, const double* 
                      const double* delta_tau_clouds, const double* delta_tau_clouds_upper, const double* zb,
                      const double* gauss_weight, double R0, int nbin, int ny, int nshell, double* work, double* A,
                      double* T_floor, double* T_band);
+/* Angular emission spectrum of a column (csrc/stage_emission.hip; not in the reference -- the contract is README, "Angular
+ * emission spectrum"): the intensity leaving the top of the atmosphere along `nangle` emission angles, by the formal solution
+ * with a source linear in tau per shell, built from the Planck values and the run's own spectral fluxes.
+ *   isothermal layers:  one shell per layer; delta_tau_wg[c + ny*nbin*i] (c = y + ny*x), delta_tau_clouds[x + nbin*i],
+ *                       w_0[c + ny*nbin*i]; the three `_upper` pointers, planckband_int and the Fc_* pointers null
+ *   otherwise:          two shells per layer: delta_tau_wg, delta_tau_clouds, w_0 are the `_lower` arrays of the run, the
+ *                       `_upper` pointers its `_upper` arrays; Fc_*[c + ny*nbin*i] the fluxes at the layer centres
+ * planckband_lay[i + x*(nlayer+2)], planckband_int[i + x*(nlayer+1)]; F_*_wg[c + ny*nbin*i] at the nlayer + 1 interfaces.
+ * F_dir_wg (and Fc_dir_wg) null: no beam, `beta` is ignored.  mu_inv[m] = 1 / mu_m, m < nangle <= 16.
+ * Out: I_band[x + nbin*m] and, unless null, I_wg[c + ny*nbin*m] before the Gauss sum.  1 <= ny <= 256.  All pointers are
+ * device pointers. */
+int hx_emission_angles(hx_context* ctx, const double* delta_tau_wg, const double* delta_tau_wg_upper,
+                       const double* delta_tau_clouds, const double* delta_tau_clouds_upper, const double* w_0,
+                       const double* w_0_upper, const double* planckband_lay, const double* planckband_int,
+                       const double* F_up_wg, const double* F_down_wg, const double* F_dir_wg, const double* Fc_up_wg,
+                       const double* Fc_down_wg, const double* Fc_dir_wg, const double* gauss_weight,
+                       const double* mu_inv, double beta, int nbin, int ny, int nlayer, int nangle, double* I_band,
+                       double* I_wg);
 
 /* ---- (4) fused fast path --------------------------------------------------------------------
  * One hx_rt object = one batch of `ncol` independent atmosphere columns (planets / T-P profiles of
